@@ -22,6 +22,10 @@ the transformer still runs on that step, nothing is skipped.
 Multi-GPU: one process per GPU, one image per rank (the path shards per image; SURVEY.md section
 8e), weights replicated, no collective on the data path; the final latents are all-gathered to
 every rank over RCCL inside the timed region (512 KB per image).
+
+`--dump-outputs DIR` writes those gathered final latents of the last timed edit to DIR/final_latents.npy
+(float32, [images, L, 64]); every input is generated from fixed seeds, so two builds run with the same
+arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -36,8 +40,9 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-PEAK_BF16_TFLOPS = 2500.0          # MI355X dense bf16 MFMA, /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_BF16_TFLOPS = 2500.0          # MI355X dense bf16 MFMA
 N_STEPS = 28
+DUMP_LIMIT_BYTES = 64 << 20        # --dump-outputs: all arrays together
 # counter summaries of THIS command under rocprofv3 --pmc (tools/probes/measure_counters.sh); quoted only when their csrc_sha16 is the
 # hash of the kernel sources this process runs (load_stamped)
 PMC_TRAFFIC_FILE = "profiles/r06_pmc_traffic.json"
@@ -264,6 +269,23 @@ def load_stamped(rel_path, stamp=None):
     return d if d.get("csrc_sha16") == (stamp or csrc_hash()) else {}
 
 
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each array as out_dir/<name>.npy in float32.  When the arrays together exceed `limit` bytes, each one keeps the same
+    fixed share of its rows along axis 1 (the token axis of the latents), chosen by a seeded generator and kept in order, so
+    that two builds run with the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit:
+            n = a.shape[1]
+            keep = max(1, n * limit // total)
+            rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+            a = np.ascontiguousarray(a[:, rows])
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def build_pipeline(cfg, device, seed):
     from regione_amd import synth
     from regione_amd.harness import flux as H
@@ -406,14 +428,19 @@ def main():
     ap.add_argument("--force-collectives", action="store_true",
                     help="initialise the process group and run barrier / all_gather / MAX-reduce even with ONE rank (launch under "
                          "torch.distributed.run --nproc-per-node 1): RCCL executes on a one-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final latents of the last timed edit (every image, in image order) as DIR/final_latents.npy "
+                         "(float32, at most 64 MB: a fixed seeded sample of the token rows beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1 and args.gpus > 1 and "RANK" not in os.environ:
-        # plain `python bench.py --gpus N`: become the launcher (one process per GPU, rendezvous on 127.0.0.1 - the container hostname
-        # may not resolve); under torch.distributed.run this branch is never taken.  One JSON line either way (rank 0 prints it).
+        # plain `python bench.py --gpus N`: start the launcher as a child (one process per GPU, rendezvous on 127.0.0.1 - the container
+        # hostname may not resolve); under torch.distributed.run this branch is never taken.  One JSON line either way (rank 0 prints it).
         import socket
         with socket.socket() as s_:
             s_.bind(("127.0.0.1", 0))
@@ -423,7 +450,8 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        import subprocess
+        raise SystemExit(subprocess.call(cmd))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch one process per GPU (torch.distributed.run --nproc-per-node "
                          f"{args.gpus}) or run plain `python bench.py --gpus {args.gpus}`, which launches them itself")
@@ -507,6 +535,7 @@ def main():
         out = edit()
         D.gather_latents([out], [rank], world, dist, force=force)   # warm the collective too (communicator / channel setup)
     timer = KernelTimer()
+    last_outputs = []                    # what the last timed edit hands its caller: every image's final latents
 
     def job():
         for k in range(args.steps):
@@ -529,7 +558,10 @@ def main():
             got = D.gather_latents([o], [rank], world, dist, force=force)
             if force:
                 assert len(got) == world and all(g is not None and g.shape == o.shape for g in got)
+            last_outputs[:] = got
     elapsed = D.timed(job, torch.cuda.synchronize, dist, force=force)       # barrier + sync both sides, MAX over ranks
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"final_latents": torch.cat(last_outputs).float().cpu().numpy()})
 
     # characterise the run (untimed): step kinds, K_e
     trace = {}

@@ -129,7 +129,7 @@ def test_bench_two_ranks_share_the_gpu(extra):
 
 def test_bench_plain_command_launches_its_own_ranks():
     """`python bench.py --gpus 2 ...` WITHOUT torch.distributed.run (the way the driver starts the 1-GPU
-    line) must not exit with an error: it re-executes itself under torch.distributed.run (127.0.0.1 rendezvous, one process per
+    line) must not exit with an error: it runs itself under torch.distributed.run in a child process (127.0.0.1 rendezvous, one process per
     GPU) and rank 0 prints the one JSON line."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -145,32 +145,37 @@ def test_bench_plain_command_launches_its_own_ranks():
 
 
 @pytest.mark.parametrize("extra", [[], ["--true-cfg", "6.0"]])
-def test_bench_eight_ranks_share_the_gpu(extra):
-    """BASELINE configs[3]'s launch shape without an 8-GPU node: EIGHT ranks (gloo, all on cuda:0,
-    toy trunk, 256 px) under torch.distributed.run exactly as the driver launches `--gpus 8`: per-rank K_e cycling
-    5 / 15 / 25 / 50 % twice, the 8-way gather of the final latents inside the timed region, the MAX-over-ranks clock, ONE
-    JSON line from rank 0 with 8 `per_rank` rows and value = 28 * steps * 8 / elapsed."""
+def test_bench_four_ranks_share_the_gpu(extra, tmp_path):
+    """BASELINE configs[3]'s multi-rank launch shape on one shared GPU: FOUR ranks (gloo, all on cuda:0,
+    toy trunk, 256 px) under torch.distributed.run exactly as the driver launches `--gpus N`.  Four ranks keep the test parent, the
+    launcher and the ranks at six processes with the GPU open.  Three edit fractions for four ranks: rank 3 wraps round to rank 0's
+    5 %, so per-rank K_e cycling is checked across the wrap.  The 4-way gather of the final latents inside the timed region, the
+    MAX-over-ranks clock, ONE JSON line from rank 0 with 4 `per_rank` rows and value = 28 * steps * 4 / elapsed; rank 0 dumps
+    the gathered latents of all four images."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     port = 30400 + (os.getpid() % 400) + (11 if extra else 0)
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), "bench.py", "--gpus", "8", "--steps", "1", "--warmup", "1", "--toy", "--size", "256",
-           "--share-gpu", "--dist-backend", "gloo", "--no-cpu-baseline", "--no-vanilla"] + extra
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), "bench.py", "--gpus", "4", "--steps", "1", "--warmup", "1", "--toy", "--size", "256",
+           "--edit-fracs", "0.05,0.15,0.25", "--share-gpu", "--dist-backend", "gloo", "--no-cpu-baseline", "--no-vanilla",
+           "--dump-outputs", str(tmp_path)] + extra
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                               # rank 0 only
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 8 and d["scaling"] == "weak" and d["unit"] == "steps/s" and d["steps"] == 1
+    assert d["n_gpus"] == 4 and d["scaling"] == "weak" and d["unit"] == "steps/s" and d["steps"] == 1
     pr = d["per_rank"]
-    assert [p["rank"] for p in pr] == list(range(8))
-    assert [p["edit_frac"] for p in pr] == [0.05, 0.15, 0.25, 0.50] * 2
+    assert [p["rank"] for p in pr] == list(range(4))
+    assert [p["edit_frac"] for p in pr] == [0.05, 0.15, 0.25, 0.05]
     assert all(p["edit_s"] > 0 and p["K_e"] > 0 for p in pr)
-    assert [p["K_e"] for p in pr[:4]] == [p["K_e"] for p in pr[4:]] and pr[0]["K_e"] < pr[1]["K_e"] < pr[2]["K_e"] < pr[3]["K_e"]
+    assert pr[3]["K_e"] == pr[0]["K_e"] and pr[0]["K_e"] < pr[1]["K_e"] < pr[2]["K_e"]
     assert ("true CFG 6.0" in d["config"]["workload"]) == bool(extra)
     elapsed = d["ms_per_step"] * 1e-3 * d["steps"]
-    assert abs(d["value"] - 28 * d["steps"] * 8 / elapsed) < 1e-6 * d["value"]
+    assert abs(d["value"] - 28 * d["steps"] * 4 / elapsed) < 1e-6 * d["value"]
     assert elapsed >= max(p["edit_s"] for p in pr) * 0.999               # the job clock is the slowest rank's (plus the gather)
+    lat = np.load(tmp_path / "final_latents.npy")
+    assert lat.dtype == np.float32 and lat.shape == (4, 256, 64) and np.isfinite(lat).all()
 
 
 def test_cfg_branch_pairs_world_four_share_the_gpu():
@@ -241,3 +246,18 @@ def test_bench_json_contract_single_gpu():
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "steps/s" and cb["value"] > 0 and cb["cores"] >= 1 and cb["sample"]
     assert abs(d["value"] - 28 * d["steps"] / (d["ms_per_step"] * 1e-3 * d["steps"])) < 1e-6 * d["value"]
+
+
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: the final latents of the last of `--steps` timed edits as DIR/final_latents.npy (float32, one row per
+    image), and the result line reports the steps it timed and the milliseconds per step."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--toy", "--no-cpu-baseline",
+                        "--no-vanilla", "--no-5pct", "--dump-outputs", str(tmp_path)], cwd=root, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(r.stdout.strip())
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["final_latents.npy"]
+    lat = np.load(tmp_path / "final_latents.npy")
+    assert lat.dtype == np.float32 and lat.shape == (1, 4096, 64) and np.isfinite(lat).all() and lat.std() > 0
