@@ -398,6 +398,14 @@ int rgn_softmax_rows(void* S, int ld, int Hp, int Wp, float scale, void* stream)
  * the first Co channels of a padded image with row stride ld -> [Co, H, W] bf16. */
 int rgn_nchw_to_padded(const void* Z, void* Y, int Cz, int H, int W, int Cpad, void* stream);
 int rgn_padded_to_nchw(const void* X, int ld, void* O, int Co, int H, int W, void* stream);
+/* The same conversion for the Qwen-Image VAE's outputs: clamp_unit != 0 clamps to [-1, 1] (the decoded image, `torch.clamp(out, -1, 1)`);
+ * out_fp32 != 0 stores fp32, else bf16 (the host VAE's dtype). */
+int rgn_padded_to_nchw_cvt(const void* X, int ld, void* O, int Co, int H, int W, int clamp_unit, int out_fp32, void* stream);
+/* Qwen-Image (Wan-2.1) VAE `RMS_norm` (bias-free) per pixel over the channels, optional SiLU:
+ * Y = silu(X / max(||X[:C_valid]||_2, 1e-12) * sqrt(C_valid) * gamma), on a padded image [Hp * Wp, C_pad] (C_pad = row stride, a multiple of
+ * 64, <= 512; C_valid <= C_pad, e.g. the 96-channel level stored at 128).  fp32 sum of squares folded in a fixed order (bit-reproducible), one
+ * bf16 rounding of the output; border rows and channels >= C_valid of Y are written as zeros.  gamma: [C_pad] bf16, 16-byte aligned. */
+int rgn_rms_norm_silu(const void* X, void* Y, int Hp, int Wp, int C_valid, int C_pad, const void* gamma, int silu, void* stream);
 
 /* Device properties the host side needs for roofline reporting (no torch types). */
 int rgn_device_info(int* cu_count, int* clock_khz, size_t* hbm_bytes);

@@ -119,6 +119,8 @@ SIGNATURES = {
     "rgn_softmax_rows": [_c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p],
     "rgn_nchw_to_padded": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p],
     "rgn_padded_to_nchw": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
+    "rgn_padded_to_nchw_cvt": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p],
+    "rgn_rms_norm_silu": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p],
 }
 _RESTYPE = {"rgn_last_error": C.c_char_p, "rgn_abi_struct_bytes": C.c_size_t, "rgn_attention_workspace_bytes": C.c_size_t,
             "rgn_gemm_workspace_bytes": C.c_size_t, "rgn_groupnorm_workspace_bytes": C.c_size_t,

@@ -24,10 +24,12 @@ diffusers is not installed in the build image: the call sequence follows the ref
 from __future__ import annotations
 
 import re
+import warnings
 from typing import Dict, Iterable, Iterator, Optional, Tuple
 
 import torch
 
+from . import _lib
 from .synth import FluxConfig, flux_param_shapes
 
 # host parameter name -> engine (FLUX-layout) parameter name, per family; applied as ordered regex substitutions
@@ -200,10 +202,59 @@ def _loop_extras(kw: dict, sigmas, callback_on_step_end, callback_on_step_end_te
 _NO_HIP_VAE = object()
 
 
+def _is_qwen_vae(vae) -> bool:
+    """The [EXT] AutoencoderKLQwenImage layout (3-D causal VAE of the Qwen-Image pipelines): RMS_norm `norm_out`, a Wan-style config."""
+    cfg = getattr(vae, "config", None)
+    return all(getattr(getattr(vae, p, None), "norm_out", None) is not None for p in ("decoder", "encoder")) and \
+        getattr(cfg, "base_dim", None) is not None and getattr(cfg, "z_dim", None) is not None and hasattr(vae, "state_dict")
+
+
+def _adopt_qwen_vae(host, dev):
+    """Both halves of a Qwen-Image VAE onto the HIP kernels (regione_amd/qwen_vae.py), once per host pipeline.  Whatever the kernels do not
+    cover (another config, unknown or missing parameters, a dtype other than bf16 / fp32) keeps the host module, with one warning naming
+    the reason: (None, None)."""
+    from . import qwen_vae as Q
+    vae = host.vae
+    cfg, want = vae.config, Q.QWEN_VAE_CONFIG
+    got = {k: (tuple(getattr(cfg, k)) if isinstance(want[k], tuple) else getattr(cfg, k)) if hasattr(cfg, k) else None for k in want}
+    why = None
+    if got != want:
+        why = f"config {got} (the kernels cover {want})"
+    else:
+        try:
+            sd = vae.state_dict()
+            return Q.HipQwenVaeDecoder(sd, dev, out_dtype=vae.dtype), Q.HipQwenVaeEncoder(sd, dev, out_dtype=vae.dtype)
+        except _lib.RegionEHipError as e:
+            why = str(e)
+    warnings.warn(f"Qwen-Image VAE kept on the host module: {why}", RuntimeWarning, stacklevel=3)
+    return None, None
+
+
+def _qwen_vae_refusal(vae, x, kind: str, kw=None) -> Optional[str]:
+    """Why the HIP Qwen-Image VAE does not serve this `vae.decode(z)` / `vae.encode(x)` call (None: it does)."""
+    from . import qwen_vae as Q
+    if kw:
+        return f"{kind} arguments {sorted(kw)}"
+    if getattr(vae, "use_tiling", False) or getattr(vae, "use_slicing", False):
+        return "vae.use_tiling / use_slicing is set"
+    if not isinstance(x, torch.Tensor) or x.dim() != 5:
+        return f"{kind} of a {getattr(x, 'dim', lambda: '?')()}-D input (one [1, C, 1, H, W] frame is covered)"
+    if x.shape[0] != 1:
+        return f"batch {x.shape[0]} > 1"
+    if x.shape[2] != 1:
+        return f"T = {x.shape[2]} frames (single images are covered)"
+    if kind == "encode" and (x.shape[1] != 3 or x.shape[3] % 8 or x.shape[4] % 8):
+        return f"image {tuple(x.shape)} (3 channels, H and W multiples of 8 are covered)"
+    h, w = (x.shape[3], x.shape[4]) if kind == "decode" else (x.shape[3] // 8, x.shape[4] // 8)
+    if (h + 2) * (w + 2) > Q.SOFTMAX_MAX_ROWS:
+        return f"latent {h} x {w}: (h + 2) (w + 2) > {Q.SOFTMAX_MAX_ROWS}, the mid-block softmax's limit"
+    return None
+
+
 def hip_vae_for(host, dev):
     """The host's AutoencoderKL decoder adopted onto the HIP kernels (regione_amd/vae.py) - once per host pipeline,
-    kept on it as `_regione_hip_vae`.  None when the host's VAE is not of that layout (Qwen-Image's 3-D causal VAE, a module with a
-    post_quant_conv): the host module then decodes, exactly as in the reference (`self.vae.decode`, FluxKontext/inplace.py:396-402).  A VAE
+    kept on it as `_regione_hip_vae`; Qwen-Image's 3-D causal VAE goes to regione_amd/qwen_vae.py (`_adopt_qwen_vae`, both halves at once).
+    None when the host's VAE is of neither layout (e.g. a module with a post_quant_conv): the host module then decodes, exactly as in the reference (`self.vae.decode`, FluxKontext/inplace.py:396-402).  A VAE
     that HAS the layout but cannot be adopted (unknown parameters, other widths) raises instead of silently running the slower module;
     `pipe._regione_hip_vae = False` before the first call keeps the host module on purpose."""
     cached = host.__dict__.get("_regione_hip_vae", _NO_HIP_VAE)
@@ -212,6 +263,9 @@ def hip_vae_for(host, dev):
     if cached is not _NO_HIP_VAE:
         return cached
     vae = getattr(host, "vae", None)
+    if _is_qwen_vae(vae):
+        host._regione_hip_vae, host._regione_hip_vae_encoder = _adopt_qwen_vae(host, dev)
+        return host._regione_hip_vae
     dec = getattr(vae, "decoder", None)
     ok = dec is not None and all(hasattr(dec, n) for n in ("conv_in", "mid_block", "up_blocks", "conv_norm_out", "conv_out")) and \
         getattr(vae, "post_quant_conv", None) is None and hasattr(dec, "state_dict")
@@ -238,6 +292,10 @@ def hip_vae_encoder_for(host, dev):
     if cached is not _NO_HIP_VAE:
         return cached
     vae = getattr(host, "vae", None)
+    if _is_qwen_vae(vae):
+        if "_regione_hip_vae" not in host.__dict__:
+            hip_vae_for(host, dev)
+        return host._regione_hip_vae_encoder
     enc = getattr(vae, "encoder", None)
     ok = enc is not None and all(hasattr(enc, n) for n in ("conv_in", "down_blocks", "mid_block", "conv_norm_out", "conv_out")) and \
         getattr(vae, "quant_conv", None) is None and hasattr(enc, "state_dict")
@@ -270,8 +328,16 @@ class _hip_vae_encode:
         vae, enc, dev = self.host.vae, self.enc, self.dev
         self.orig = vae.__dict__.get("encode", _NO_HIP_VAE)
         own = vae.encode
+        qwen = _is_qwen_vae(vae)
 
         def encode(x, return_dict=True, **kw):
+            if qwen:
+                why = _qwen_vae_refusal(vae, x, "encode", kw)
+                if why is None:
+                    out = enc.encode_dist(x.to(dev))
+                    return out if return_dict else (out.latent_dist,)
+                warnings.warn(f"Qwen-Image VAE encode on the host module: {why}", RuntimeWarning, stacklevel=2)
+                return own(x, return_dict=return_dict, **kw)
             if isinstance(x, torch.Tensor) and x.dim() == 4 and x.shape[0] == 1 and x.shape[1] == 3 and not kw:
                 out = enc.encode_dist(x.to(dev))
                 return out if return_dict else (out.latent_dist,)
@@ -294,6 +360,19 @@ def _decode_image(host, vae, lat, dev):
     if hv is not None and lat.dim() == 4 and lat.shape[0] == 1:
         return hv.decode(lat.to(dev))
     return vae.decode(lat, return_dict=False)[0]
+
+
+def _decode_qwen_image(host, vae, z, dev):
+    """`vae.decode(z, return_dict=False)[0][:, :, 0]` of the Qwen pipelines (QwenImageEdit/inplace.py:437-451) - on the HIP decoder when the
+    host's VAE was adopted and the call is one it covers, else on the host module (with a warning naming the reason)."""
+    from . import qwen_vae as Q
+    hv = hip_vae_for(host, dev)
+    if isinstance(hv, Q.HipQwenVaeDecoder):
+        why = _qwen_vae_refusal(vae, z, "decode")
+        if why is None:
+            return hv.decode(z.to(dev))[:, :, 0]
+        warnings.warn(f"Qwen-Image VAE decode on the host module: {why}", RuntimeWarning, stacklevel=3)
+    return vae.decode(z, return_dict=False)[0][:, :, 0]
 
 
 class _Clock:
@@ -564,8 +643,9 @@ def _hosted_qwen(host, eng, image=None, prompt=None, negative_prompt=None, true_
     prompt_embeds, prompt_embeds_mask = enc(prompt, prompt_embeds, prompt_embeds_mask)
     if do_true_cfg:
         negative_prompt_embeds, negative_prompt_embeds_mask = enc(negative_prompt, negative_prompt_embeds, negative_prompt_embeds_mask)
-    latents, image_latents = host.prepare_latents(image, 1, eng.transformer.cfg_model.in_channels // 4, height, width,
-                                                  prompt_embeds.dtype, exec_dev, generator, latents)
+    with _hip_vae_encode(host, dev):                       # vae.encode of the condition images on the HIP encoder (Qwen VAE: one frame each)
+        latents, image_latents = host.prepare_latents(image, 1, eng.transformer.cfg_model.in_channels // 4, height, width,
+                                                      prompt_embeds.dtype, exec_dev, generator, latents)
     clk.mark("encode_s")
     kw = dict(image=_bf(image_latents, dev), prompt_embeds=_bf(prompt_embeds, dev),
               negative_prompt_embeds=_bf(negative_prompt_embeds, dev) if do_true_cfg else None, height=height, width=width,
@@ -582,7 +662,7 @@ def _hosted_qwen(host, eng, image=None, prompt=None, negative_prompt=None, true_
         lat = host._unpack_latents(latents, height, width, host.vae_scale_factor).to(vae.dtype)
         mean = torch.tensor(vae.config.latents_mean).view(1, vae.config.z_dim, 1, 1, 1).to(lat.device, lat.dtype)
         inv_std = 1.0 / torch.tensor(vae.config.latents_std).view(1, vae.config.z_dim, 1, 1, 1).to(lat.device, lat.dtype)
-        out = host.image_processor.postprocess(vae.decode(lat / inv_std + mean, return_dict=False)[0][:, :, 0], output_type=output_type)
+        out = host.image_processor.postprocess(_decode_qwen_image(host, vae, lat / inv_std + mean, dev), output_type=output_type)
     if hasattr(host, "maybe_free_model_hooks"):
         host.maybe_free_model_hooks()
     clk.mark("decode_s")

@@ -10,6 +10,7 @@
 //   gn_apply_kernel                         y = (x - mean) * rstd * gamma + beta, optional SiLU, border rows -> 0
 //   upsample2x_kernel                       nearest-neighbour 2 x upsample into the next level's padded image
 //   softmax_rows_kernel                     mid-block attention: P = softmax(scale * S) per row over the valid (non-border) key columns
+//   rms_norm_kernel                         channel RMS-norm (+ SiLU) per pixel: the Qwen-Image (Wan-2.1) VAE's RMS_norm
 //   nchw_to_padded_kernel / padded_to_nchw_kernel   the host tensor layouts on either side of the decoder
 #include "common.h"
 
@@ -191,6 +192,51 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(uint16_t* __restrict_
     }
 }
 
+// ---- channel RMS-norm of the Qwen-Image VAE: y = x / max(||x||_2, 1e-12) * sqrt(C_valid) * gamma (+ SiLU) per pixel ---------------------
+// One pixel row = `lanes` threads of a wave (the power of two >= C_pad / 8; 16 / 32 / 64 for 128 / 192 / 384 channels), one 8-channel
+// vector per thread; the sum of squares is folded by xor shuffles inside those lanes (fixed order, no atomics: bit-reproducible).  Channels
+// >= C_valid and border rows are written as zeros.
+__global__ __launch_bounds__(256) void rms_norm_kernel(const uint16_t* __restrict__ X, uint16_t* __restrict__ Y, int Hp, int Wp, int C_valid,
+                                                       int C_pad, const uint16_t* __restrict__ gamma, float scale, int lanes_log2, int silu) {
+    const int lanes = 1 << lanes_log2, rpb = 256 >> lanes_log2, rows = Hp * Wp, vpr = C_pad >> 3;
+    const int tid = threadIdx.x, v = tid & (lanes - 1), rl = tid >> lanes_log2;
+    const bool vec = v < vpr;
+    float ga[8];
+    {
+        uint4 gw = make_uint4(0u, 0u, 0u, 0u);
+        if (vec) gw = *(const uint4*)(gamma + v * 8);
+        const uint32_t gws[4] = {gw.x, gw.y, gw.z, gw.w};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ga[e] = (v * 8 + e < C_valid) ? ((e & 1) ? hi_bf(gws[e >> 1]) : lo_bf(gws[e >> 1])) * scale : 0.f;
+    }
+    for (int r0 = blockIdx.x * rpb; r0 < rows; r0 += gridDim.x * rpb) {
+        const int r = r0 + rl;
+        const bool in = r < rows;
+        const int py = r / Wp, px = r - py * Wp;
+        const bool valid = in && px != 0 && px != Wp - 1 && py != 0 && py != Hp - 1;
+        uint4 w = make_uint4(0u, 0u, 0u, 0u);
+        if (valid && vec) w = *(const uint4*)(X + (size_t)r * C_pad + v * 8);
+        const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+        float x[8], ss = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            x[e] = (e & 1) ? hi_bf(ws[e >> 1]) : lo_bf(ws[e >> 1]);
+            ss = __builtin_fmaf(x[e], x[e], ss);
+        }
+        for (int o = lanes >> 1; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);          // every lane of the row group takes part
+        const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+        float y[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float t = x[e] * inv * ga[e];
+            if (silu) t = t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * t));
+            y[e] = valid ? t : 0.f;
+        }
+        if (in && vec)
+            *(uint4*)(Y + (size_t)r * C_pad + v * 8) = make_uint4(pk_bf16(y[0], y[1]), pk_bf16(y[2], y[3]), pk_bf16(y[4], y[5]), pk_bf16(y[6], y[7]));
+    }
+}
+
 // ---- host layouts ---------------------------------------------------------------------------------------------------------------
 // z [Cz, H, W] (bf16, NCHW of one image) -> padded pixel-major [Hp * Wp, Cpad] with channels [Cz, Cpad) and the border zero
 __global__ __launch_bounds__(256) void nchw_to_padded_kernel(const uint16_t* __restrict__ Z, uint16_t* __restrict__ Y, int Cz, int H, int W, int Cpad) {
@@ -211,6 +257,21 @@ __global__ __launch_bounds__(256) void padded_to_nchw_kernel(const uint16_t* __r
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
         const int t = (int)(i / (uint32_t)W), x = (int)(i - (uint32_t)t * W), c = t / H, y = t - c * H;
         O[i] = X[((size_t)(y + 1) * Wp + (x + 1)) * ld + c];
+    }
+}
+
+// the same, clamped to [-1, 1] (the decoder's image) when clamp_unit != 0, stored as bf16 or fp32 (the host VAE's dtype)
+template <bool F32>
+__global__ __launch_bounds__(256) void padded_to_nchw_cvt_kernel(const uint16_t* __restrict__ X, int ld, void* __restrict__ O, int Co, int H, int W,
+                                                                 int clamp_unit) {
+    const int Wp = W + 2;
+    const uint32_t total = (uint32_t)Co * H * W;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+        const int t = (int)(i / (uint32_t)W), x = (int)(i - (uint32_t)t * W), c = t / H, y = t - c * H;
+        float f = __uint_as_float((uint32_t)X[((size_t)(y + 1) * Wp + (x + 1)) * ld + c] << 16);
+        if (clamp_unit) f = fminf(fmaxf(f, -1.0f), 1.0f);
+        if (F32) ((float*)O)[i] = f;
+        else ((uint16_t*)O)[i] = (uint16_t)(__float_as_uint(f) >> 16);              // a clamped bf16 value is a bf16 value: no rounding
     }
 }
 
@@ -285,6 +346,33 @@ int rgn_padded_to_nchw(const void* X, int ld, void* O, int Co, int H, int W, voi
     hipLaunchKernelGGL(padded_to_nchw_kernel, dim3(grid_for(total, 256 * 4, 8192)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)X,
                        ld, (uint16_t*)O, Co, H, W);
     return check_launch("padded_to_nchw_kernel");
+}
+
+int rgn_rms_norm_silu(const void* X, void* Y, int Hp, int Wp, int C_valid, int C_pad, const void* gamma, int silu, void* stream) {
+    if (!X || !Y || !gamma || Hp < 3 || Wp < 3 || C_valid <= 0 || C_pad <= 0) return fail(RGN_E_BADARG, "rms_norm: bad argument");
+    if (C_valid > C_pad) return fail(RGN_E_BADARG, "rms_norm: C_valid > C_pad");
+    if ((C_pad % 64) || C_pad > 512) return fail(RGN_E_UNSUPPORTED, "rms_norm: C_pad must be a multiple of 64, at most 512");
+    if ((((uintptr_t)X | (uintptr_t)Y | (uintptr_t)gamma) & 15) != 0) return fail(RGN_E_UNSUPPORTED, "rms_norm: pointers must be 16-byte aligned");
+    if ((long long)Hp * Wp >= (1ll << 31)) return fail(RGN_E_UNSUPPORTED, "rms_norm: image too large");
+    const int vpr = C_pad / 8;
+    int lg = 0;
+    while ((1 << lg) < vpr) ++lg;
+    const int rows = Hp * Wp, rpb = 256 >> lg;
+    hipLaunchKernelGGL(rms_norm_kernel, dim3(grid_for((size_t)rows, rpb * 4, 8192)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)X,
+                       (uint16_t*)Y, Hp, Wp, C_valid, C_pad, (const uint16_t*)gamma, sqrtf((float)C_valid), lg, silu);
+    return check_launch("rms_norm_kernel");
+}
+
+int rgn_padded_to_nchw_cvt(const void* X, int ld, void* O, int Co, int H, int W, int clamp_unit, int out_fp32, void* stream) {
+    if (!X || !O || Co <= 0 || H <= 0 || W <= 0 || ld < Co) return fail(RGN_E_BADARG, "padded_to_nchw_cvt: bad argument");
+    const size_t total = (size_t)Co * H * W;
+    if (total >= ((size_t)1 << 32)) return fail(RGN_E_UNSUPPORTED, "padded_to_nchw_cvt: image too large");
+    const dim3 g(grid_for(total, 256 * 4, 8192));
+    if (out_fp32)
+        hipLaunchKernelGGL(padded_to_nchw_cvt_kernel<true>, g, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)X, ld, O, Co, H, W, clamp_unit);
+    else
+        hipLaunchKernelGGL(padded_to_nchw_cvt_kernel<false>, g, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)X, ld, O, Co, H, W, clamp_unit);
+    return check_launch("padded_to_nchw_cvt_kernel");
 }
 
 }  // extern "C"

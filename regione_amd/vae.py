@@ -356,12 +356,17 @@ class _KLBase:
             self._conv(prefix + ".conv_shortcut")
 
     # -- blocks -------------------------------------------------------------------------------------------------------------------
+    _attn_norm = "group_norm"
+
+    def _norm(self, x: PaddedImage, name: str, out: PaddedImage, silu: bool = True) -> PaddedImage:
+        return groupnorm_silu(x, self.p[name + ".weight"], self.p[name + ".bias"], out, silu=silu, eps=self.eps)
+
     def _run_resnet(self, x: PaddedImage, prefix: str, cout: int) -> PaddedImage:
-        P, Cv, pool = self.p, self.c, self.pool
-        n = groupnorm_silu(x, P[prefix + ".norm1.weight"], P[prefix + ".norm1.bias"], pool.get(x.H, x.W, x.C), eps=self.eps)
+        Cv, pool = self.c, self.pool
+        n = self._norm(x, prefix + ".norm1", pool.get(x.H, x.W, x.C))
         h = conv(n, Cv[prefix + ".conv1"], pool.get(x.H, x.W, cout), gn=self.fuse_gn)
         pool.put(n)
-        n2 = groupnorm_silu(h, P[prefix + ".norm2.weight"], P[prefix + ".norm2.bias"], pool.get(x.H, x.W, cout), eps=self.eps)
+        n2 = self._norm(h, prefix + ".norm2", pool.get(x.H, x.W, cout))
         skip = x
         if prefix + ".conv_shortcut" in Cv:
             skip = conv(x, Cv[prefix + ".conv_shortcut"], pool.get(x.H, x.W, cout))
@@ -383,7 +388,7 @@ class _KLBase:
             self._attn_buf[key] = (torch.zeros((rows, ldp), dtype=torch.bfloat16, device=self.device),       # S / P
                                    torch.zeros((C, ldp), dtype=torch.bfloat16, device=self.device))          # V^T (padding columns stay 0)
         S, vt = self._attn_buf[key]
-        n = groupnorm_silu(x, P[a + "group_norm.weight"], P[a + "group_norm.bias"], pool.get(x.H, x.W, C), silu=False, eps=self.eps)
+        n = self._norm(x, a + self._attn_norm, pool.get(x.H, x.W, C), silu=False)
         q = conv(n, Cv[a + "to_q"], pool.get(x.H, x.W, C))
         k = conv(n, Cv[a + "to_k"], pool.get(x.H, x.W, C))
         ops.gemm(P[a + "to_v.weight"], n.t, None, vt[:, :rows])                  # V^T = W_v X^T; b_v is added behind P V (rows of P sum to 1)
