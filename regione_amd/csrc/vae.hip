@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void rms_norm_kernel(const uint16_t* __restric
         float x[8], ss = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            x[e] = (e & 1) ? hi_bf(ws[e >> 1]) : lo_bf(ws[e >> 1]);
+            x[e] = (v * 8 + e < C_valid) ? ((e & 1) ? hi_bf(ws[e >> 1]) : lo_bf(ws[e >> 1])) : 0.f;   // the norm covers X[:C_valid] only
             ss = __builtin_fmaf(x[e], x[e], ss);
         }
         for (int o = lanes >> 1; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);          // every lane of the row group takes part
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(256) void padded_to_nchw_cvt_kernel(const uint16_t*
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
         const int t = (int)(i / (uint32_t)W), x = (int)(i - (uint32_t)t * W), c = t / H, y = t - c * H;
         float f = __uint_as_float((uint32_t)X[((size_t)(y + 1) * Wp + (x + 1)) * ld + c] << 16);
-        if (clamp_unit) f = fminf(fmaxf(f, -1.0f), 1.0f);
+        if (clamp_unit && f == f) f = fminf(fmaxf(f, -1.0f), 1.0f);                      // NaN passes through, as torch.clamp keeps it
         if (F32) ((float*)O)[i] = f;
         else ((uint16_t*)O)[i] = (uint16_t)(__float_as_uint(f) >> 16);              // a clamped bf16 value is a bf16 value: no rounding
     }
