@@ -394,6 +394,14 @@ int rgn_upsample2x(const void* X, void* Y, int Hp, int Wp, int C, void* stream);
  * padded image; in place P = softmax(scale * S) per row over the VALID key columns (border pixels and the padding columns
  * [Hp * Wp, ld) get probability 0).  ld % 8 == 0, ld <= 24576. */
 int rgn_softmax_rows(void* S, int ld, int Hp, int Wp, float scale, void* stream);
+/* Mid-block attention fused (no score matrix in memory): O = softmax(scale * Q K^T) V + b_v over the VALID pixels of a zero-bordered,
+ * pixel-major image.  Q, K, V, O: [Hp * Wp, C] bf16 (row stride C, 16-byte aligned), C in {384, 512}; b_v: [C] bf16 or NULL.  Border
+ * pixels are never keys (their K and V rows are not read); border rows of O are NOT written (the `to_out` convolution zeroes them).
+ * O may be Q itself (a query's Q row is read before its O row is written, by the same block); it may not overlap K or V.
+ * S in fp32 from bf16 operands, online softmax in fp32 (running max, exp2), P rounded to bf16 for the P V MFMA, O accumulated in fp32
+ * and rounded to bf16 once; fixed reduction order: a repeated call is bit-identical.  Any Hp, Wp >= 3 (64-bit addressing). */
+int rgn_vae_attention_bf16(const void* Q, const void* K, const void* V, const void* b_v, void* O, int Hp, int Wp, int C, float scale,
+                           void* stream);
 /* z [Cz, H, W] bf16 (one NCHW image) -> padded pixel-major [Hp * Wp, Cpad], channels [Cz, Cpad) and the border zero; and back:
  * the first Co channels of a padded image with row stride ld -> [Co, H, W] bf16. */
 int rgn_nchw_to_padded(const void* Z, void* Y, int Cz, int H, int W, int Cpad, void* stream);

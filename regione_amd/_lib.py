@@ -117,6 +117,7 @@ SIGNATURES = {
     "rgn_groupnorm_silu": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_float, _c_int, _c_void_p, _c_int, _c_void_p],
     "rgn_upsample2x": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
     "rgn_softmax_rows": [_c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p],
+    "rgn_vae_attention_bf16": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p],
     "rgn_nchw_to_padded": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p],
     "rgn_padded_to_nchw": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
     "rgn_padded_to_nchw_cvt": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p],

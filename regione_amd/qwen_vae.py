@@ -31,13 +31,14 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .vae import EncoderOutput, PaddedImage, UpConvWeights, _KLBase, conv, conv_s2, conv_up2, downsample_rows, upsample_rows
+from .vae import (EncoderOutput, PaddedImage, UpConvWeights, _KLBase, check_image_size, conv, conv_s2, conv_up2, downsample_rows,
+                  upsample_rows)
 
 _p, _stream = ops._p, ops._stream
 
 # the configuration the kernels are built for (AutoencoderKLQwenImage of Qwen-Image / -Edit / -Edit-Plus)
 QWEN_VAE_CONFIG = dict(base_dim=96, z_dim=16, dim_mult=(1, 2, 4, 4), num_res_blocks=2, attn_scales=(), temperal_downsample=(False, True, True))
-SOFTMAX_MAX_ROWS = 24576              # rgn_softmax_rows: (h + 2) (w + 2) of the mid-block image
+SOFTMAX_MAX_ROWS = 24576              # rgn_softmax_rows: (h + 2) (w + 2) of the mid-block image (the adapter's hosted-path threshold)
 
 
 def cs(c: int) -> int:
@@ -252,8 +253,7 @@ class HipQwenVaeDecoder(_QwenBase):
         if not z.is_cuda or z.dim() != 5 or z.shape[0] != 1 or z.shape[1] != self.zc or z.shape[2] != 1:
             raise _lib.RegionEHipError(f"HipQwenVaeDecoder.decode: one latent frame [1, {self.zc}, 1, h, w] on the GPU, got {tuple(z.shape)} on {z.device}")
         h, w = z.shape[3], z.shape[4]
-        if (h + 2) * (w + 2) > SOFTMAX_MAX_ROWS:
-            raise _lib.RegionEHipError(f"HipQwenVaeDecoder.decode: latent {h} x {w}: the mid-block softmax covers (h + 2) (w + 2) <= {SOFTMAX_MAX_ROWS}")
+        check_image_size(8 * h, 8 * w, "HipQwenVaeDecoder.decode")
         z = z[:, :, 0].to(torch.bfloat16).contiguous()
         Cv, pool, L = self.c, self.pool, _lib.lib()
         zin = pool.get(h, w, 64)
@@ -338,8 +338,7 @@ class HipQwenVaeEncoder(_QwenBase):
         if not x.is_cuda or x.dim() != 5 or x.shape[0] != 1 or x.shape[1] != 3 or x.shape[2] != 1 or x.shape[3] % 8 or x.shape[4] % 8:
             raise _lib.RegionEHipError(f"HipQwenVaeEncoder.encode: one frame [1, 3, 1, H, W] on the GPU, H and W multiples of 8; got {tuple(x.shape)} on {x.device}")
         H, W = x.shape[3], x.shape[4]
-        if (H // 8 + 2) * (W // 8 + 2) > SOFTMAX_MAX_ROWS:
-            raise _lib.RegionEHipError(f"HipQwenVaeEncoder.encode: image {H} x {W}: the mid-block softmax covers (H / 8 + 2) (W / 8 + 2) <= {SOFTMAX_MAX_ROWS}")
+        check_image_size(H, W, "HipQwenVaeEncoder.encode")
         x = x[:, :, 0].to(torch.bfloat16).contiguous()
         Cv, pool, L = self.c, self.pool, _lib.lib()
         xin = pool.get(H, W, 64)

@@ -14,7 +14,8 @@ same architecture (tests/host_vae.py) instead of the oracle.
   * every convolution = rgn_conv_bf16: an implicit GEMM on the hand-scheduled 256 x 256 MFMA loop over a zero-bordered, pixel-major
     activation image (csrc/vae.hip header), bias / ResNet skip / border zeroing in its epilogue;
   * GroupNorm(32) + SiLU = rgn_groupnorm_silu (statistics pass + apply pass, bit-reproducible);
-  * the mid-block attention = three GEMMs + rgn_softmax_rows;
+  * the mid-block attention = three GEMMs + rgn_softmax_rows while its score matrix fits that pass (attention_path), else the fused
+    flash-style rgn_vae_attention_bf16 (no score matrix in memory);
   * nearest upsample, NCHW <-> padded pixel-major conversions = row kernels.
 
 No CPU / eager fallback: a missing library raises RegionEHipError like every other op of the package.
@@ -29,6 +30,32 @@ import torch
 from . import _lib, ops
 
 _p, _stream = ops._p, ops._stream
+
+SOFTMAX_MAX_ROWS = 24576              # rgn_softmax_rows: (h + 2) (w + 2) of the mid-block image, the materialised attention's limit
+# the largest image either VAE family (this module and qwen_vae.py) decodes or encodes: H * W <= 2048^2 and each side <= 4096 (the
+# biggest activation, 256 channels at full resolution, then stays below the 2^32-byte reach of the convolution's buffer offsets)
+MAX_IMAGE_PIXELS = 2048 * 2048
+MAX_IMAGE_SIDE = 4096
+ATTENTION_MODES = ("auto", "fused", "materialized")
+
+
+def check_image_size(H: int, W: int, what: str):
+    """Raise RegionEHipError, before anything is allocated or launched, for an image (pixels, not latents) past the documented maximum."""
+    if H * W > MAX_IMAGE_PIXELS or H > MAX_IMAGE_SIDE or W > MAX_IMAGE_SIDE:
+        raise _lib.RegionEHipError(f"{what}: image {H} x {W} is past the HIP VAE's maximum (H * W <= {MAX_IMAGE_PIXELS} = 2048^2, "
+                                   f"each side <= {MAX_IMAGE_SIDE})")
+
+
+def attention_path(mode: str, rows: int) -> str:
+    """Which mid-block attention runs on a padded image of `rows` rows: "materialized" (three GEMMs + rgn_softmax_rows over a score
+    matrix S [rows, rows]) or "fused" (rgn_vae_attention_bf16, no S).  "auto" keeps the materialised path wherever it runs."""
+    if mode not in ATTENTION_MODES:
+        raise _lib.RegionEHipError(f"attention = {mode!r}: one of {ATTENTION_MODES}")
+    if mode == "auto":
+        return "materialized" if rows <= SOFTMAX_MAX_ROWS else "fused"
+    if mode == "materialized" and rows > SOFTMAX_MAX_ROWS:
+        raise _lib.RegionEHipError(f"attention = 'materialized': {rows} rows, rgn_softmax_rows covers at most {SOFTMAX_MAX_ROWS}")
+    return mode
 
 
 class PaddedImage:
@@ -310,6 +337,8 @@ class _KLBase:
         self.c: Dict[str, ConvWeights] = {}
         self.pixel_groups = pixel_groups
         self.fuse_gn = True              # GroupNorm statistics in the producing convolution's epilogue (False: the standalone statistics pass)
+        self.attention = "auto"          # mid-block attention: "auto" | "fused" | "materialized" (attention_path)
+        self._v_conv = None              # to_v as a 1 x 1 convolution (bias-free: b_v is added by the fused kernel), built at first use
         self.pool = _Pool(self.device)
         self._attn_buf = {}
 
@@ -382,6 +411,8 @@ class _KLBase:
         pixels of the padded image are masked out as keys by the softmax pass and zeroed as outputs by the last projection's epilogue."""
         P, Cv, pool, a = self.p, self.c, self.pool, "mid_block.attentions.0."
         C, rows = x.C, x.rows
+        if attention_path(self.attention, rows) == "fused":
+            return self._run_attention_fused(x)
         ldp = ops.padded(rows, 64)
         key = (rows, C)
         if key not in self._attn_buf:
@@ -398,6 +429,24 @@ class _KLBase:
         ops.gemm(S, vt, P[a + "to_v.bias"], o.t)
         out = conv(o, Cv[a + "to_out.0"], k, resid=x, gn=self.fuse_gn)       # k is dead
         pool.put(n); pool.put(o); pool.put(x)
+        return out
+
+    def _run_attention_fused(self, x: PaddedImage) -> PaddedImage:
+        """The same block with Q, K, V as 1 x 1 convolutions and one rgn_vae_attention_bf16 launch: no score matrix in memory."""
+        P, Cv, pool, a = self.p, self.c, self.pool, "mid_block.attentions.0."
+        C = x.C
+        if self._v_conv is None:
+            wv = P[a + "to_v.weight"]
+            self._v_conv = ConvWeights(wv.float().reshape(C, 1, 1, C), torch.zeros(C, device=self.device))
+        n = self._norm(x, a + self._attn_norm, pool.get(x.H, x.W, C), silu=False)
+        q = conv(n, Cv[a + "to_q"], pool.get(x.H, x.W, C))
+        k = conv(n, Cv[a + "to_k"], pool.get(x.H, x.W, C))
+        v = conv(n, self._v_conv, pool.get(x.H, x.W, C))
+        o = q                                                                     # O overwrites Q (include/regione_hip.h allows it)
+        _lib.check(_lib.lib().rgn_vae_attention_bf16(q.ptr(), k.ptr(), v.ptr(), _p(P[a + "to_v.bias"]), o.ptr(), x.Hp, x.Wp, C,
+                                                     1.0 / math.sqrt(C), _stream()), "rgn_vae_attention_bf16")
+        out = conv(o, Cv[a + "to_out.0"], k, resid=x, gn=self.fuse_gn)           # k is dead; border rows of o are zeroed here
+        pool.put(n); pool.put(o); pool.put(v); pool.put(x)
         return out
 
 
@@ -444,8 +493,9 @@ class HipVaeDecoder(_KLBase):
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         if not z.is_cuda or z.dim() != 4 or z.shape[0] != 1 or z.shape[1] != self.zc:
             raise _lib.RegionEHipError(f"HipVaeDecoder.decode: one latent image [1, {self.zc}, h, w] on the GPU, got {tuple(z.shape)} on {z.device}")
-        z = z.to(torch.bfloat16).contiguous()
         h, w = z.shape[2], z.shape[3]
+        check_image_size(8 * h, 8 * w, "HipVaeDecoder.decode")
+        z = z.to(torch.bfloat16).contiguous()
         P, Cv, pool, L = self.p, self.c, self.pool, _lib.lib()
         zin = pool.get(h, w, 64)
         _lib.check(L.rgn_nchw_to_padded(_p(z), zin.ptr(), self.zc, h, w, 64, _stream()), "rgn_nchw_to_padded")
@@ -562,8 +612,9 @@ class HipVaeEncoder(_KLBase):
     def encode(self, x: torch.Tensor) -> torch.Tensor:
         if not x.is_cuda or x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 3 or x.shape[2] % 8 or x.shape[3] % 8:
             raise _lib.RegionEHipError(f"HipVaeEncoder.encode: one image [1, 3, H, W] on the GPU, H and W multiples of 8; got {tuple(x.shape)} on {x.device}")
-        x = x.to(torch.bfloat16).contiguous()
         H, W = x.shape[2], x.shape[3]
+        check_image_size(H, W, "HipVaeEncoder.encode")
+        x = x.to(torch.bfloat16).contiguous()
         P, Cv, pool, L = self.p, self.c, self.pool, _lib.lib()
         xin = pool.get(H, W, 64)
         _lib.check(L.rgn_nchw_to_padded(_p(x), xin.ptr(), 3, H, W, 64, _stream()), "rgn_nchw_to_padded")
