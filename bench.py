@@ -26,6 +26,12 @@ every rank over RCCL inside the timed region (512 KB per image).
 `--dump-outputs DIR` writes those gathered final latents of the last timed edit to DIR/final_latents.npy
 (float32, [images, L, 64]); every input is generated from fixed seeds, so two builds run with the same
 arguments can be compared output for output.
+
+A plain run does what the headline needs: it builds the model, runs the `--warmup` and `--steps` edits,
+writes `--dump-outputs` and prints the line, with the per-launch roofline figures of the last timed edit.
+`--full` adds the untimed legs that take runs of their own (about 50 s more at full size): per-kind step
+times and the F/R/C plan, the K_e = 5 % leg, full-token denoising and the speed-up over it, the VAE
+end-to-end leg, the committed parity reports and the CPU oracle baseline.
 """
 from __future__ import annotations
 
@@ -419,10 +425,13 @@ def main():
                     help="true CFG scale (> 1: a cond and an uncond forward per computed step, one K/V cache per branch): "
                          "`--gpus 8 --true-cfg 6.0` is BASELINE.json configs[3]")
     ap.add_argument("--toy", action="store_true", help="toy model (debugging only; result is not a valid bench line)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-5pct", action="store_true", help="profiling runs: skip the untimed K_e = 5 %% leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed edits, also run the untimed legs: per-kind step times and the plan, the K_e = 5 %% leg, "
+                         "full-token denoising, the VAE end-to-end leg, the parity reports and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-5pct", action="store_true", help="with --full: skip the untimed K_e = 5 %% leg")
     ap.add_argument("--no-ktimer", action="store_true", help="profiling runs: no per-launch HIP events (drops the roofline objects)")
-    ap.add_argument("--no-vanilla", action="store_true")
+    ap.add_argument("--no-vanilla", action="store_true", help="with --full: skip the full-token and VAE end-to-end legs")
     ap.add_argument("--dist-backend", default="nccl", help="debugging: 'gloo' lets several ranks share ONE GPU (with --share-gpu)")
     ap.add_argument("--share-gpu", action="store_true", help="debugging: every rank uses cuda:0 (single-GPU box smoke of the multi-rank path)")
     ap.add_argument("--force-collectives", action="store_true",
@@ -465,7 +474,6 @@ def main():
     dist = D.init(args.dist_backend, device) if (world > 1 or force) else None
 
     from regione_amd import RegionEHelper, synth, ops
-    from oracle import regione_oracle as O            # checker / cpu_baseline leg only
 
     cfg = synth.FluxConfig(**synth.TOY) if args.toy else synth.FluxConfig()
     T = 32 if args.toy else 512
@@ -563,14 +571,16 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, {"final_latents": torch.cat(last_outputs).float().cpu().numpy()})
 
-    # characterise the run (untimed): step kinds, K_e
-    trace = {}
-    out, step_ms = step_times(trace)
-    kinds = "".join(trace["kind"])
-    K_e = int(pipe._regione_manager.edited_ids.shape[1])
-    f_full, f_reg = algorithmic_flops(cfg, T, N, K_e)
-    n_full, n_reg, n_cache = kinds.count("F"), kinds.count("R"), kinds.count("C")
-    flops_edit = (n_full * f_full + n_reg * f_reg) * (2 if args.true_cfg > 1 else 1)
+    K_e = int(pipe._regione_manager.edited_ids.shape[1])      # the region the timed edits partitioned
+    kinds = None
+    if args.full:
+        # characterise the run (untimed): step kinds, per-kind step times
+        trace = {}
+        out, step_ms = step_times(trace)
+        kinds = "".join(trace["kind"])
+        f_full, f_reg = algorithmic_flops(cfg, T, N, K_e)
+        n_full, n_reg = kinds.count("F"), kinds.count("R")
+        flops_edit = (n_full * f_full + n_reg * f_reg) * (2 if args.true_cfg > 1 else 1)
     per_rank = None
     if world > 1:
         per_rank = [None] * world
@@ -590,19 +600,20 @@ def main():
                                f"thresh=0.88 cache_thresh=0.04, L=L_c={L}, T={T}, " +
                                (f"K_e={K_e} ({100.0 * K_e / L:.1f}% edited by construction)" if per_rank is None else
                                 "K_e per rank: " + "/".join(str(r["K_e"]) for r in per_rank) + " (see per_rank)") +
-                               f", plan {kinds}" + (f", true CFG {args.true_cfg} (two forwards per computed step)"
-                                                                  if args.true_cfg > 1 else ""),
+                               (f", plan {kinds}" if kinds else "") + (f", true CFG {args.true_cfg} (two forwards per computed step)"
+                                                                       if args.true_cfg > 1 else ""),
                    "images_per_gpu": 1, "parallelism": f"image-sharded x{world}",
                    "params_billion": round(sum(int(torch.tensor(s).prod()) for s in synth.flux_param_shapes(cfg).values()) / 1e9, 2)},
         "edit_wall_clock_s": edit_s,
         "native_library": {"path": os.path.relpath(ops._lib.LIB_PATH, ROOT), "abi_version": int(ops._lib.lib().rgn_version()),
                            "kernel_sources_sha16": csrc_hash(), "built_from_sha16": _built_from()},
-        "algorithmic_tflop_per_edit": flops_edit / 1e12,
-        "loop_mfma_frac": flops_edit / edit_s / 1e12 / PEAK_BF16_TFLOPS,
         "model_build_s": t_build,
-        # F = full-token step (incl. the partition at step warmup-1), R = region step (T + K_e query rows), C = cache-served
-        "step_ms_by_kind": step_ms,
     }
+    if args.full:
+        result["algorithmic_tflop_per_edit"] = flops_edit / 1e12
+        result["loop_mfma_frac"] = flops_edit / edit_s / 1e12 / PEAK_BF16_TFLOPS
+        # F = full-token step (incl. the partition at step warmup-1), R = region step (T + K_e query rows), C = cache-served
+        result["step_ms_by_kind"] = step_ms
     if per_rank is not None:
         result["per_rank"] = per_rank          # K_e imbalance between images = the path's only scaling loss
     if dist is not None:
@@ -647,7 +658,11 @@ def main():
     kv = timer.region_kv_read()
     if kv is not None:
         result["region_attention_kv_read"] = kv
-    if rank == 0 and world == 1 and not args.toy and not args.no_5pct:
+    # --full: the untimed legs of a one-GPU run
+    solo_full = args.full and rank == 0 and world == 1
+    if solo_full:
+        from oracle import regione_oracle as O        # checker / cpu_baseline leg only
+    if solo_full and not args.toy and not args.no_5pct:
         # untimed extra leg: the same edit with K_e = 5 % of the tokens - the case where the region-step attention launch is
         # bound by the K / V^T cache read rather than by MFMA ("KV-read HBM GB/s in region attention")
         side5 = int(round((0.05 * L) ** 0.5))
@@ -667,7 +682,7 @@ def main():
                                  "gemm_tflops": s5.get("gemm_bf16_kernel", {}).get("achieved_tflops"),
                                  "attention_tflops": s5.get("attention_kernel", {}).get("achieved_tflops")}
         pipe._bench_target = keep
-    if rank == 0 and world == 1 and not args.no_vanilla:
+    if solo_full and not args.no_vanilla:
         # full-token denoising on the same engine: the speed-up the reference headlines (README.md:23)
         helper.disable()
         van = pipe(image=img, prompt_embeds=prompt, pooled_prompt_embeds=pooled, height=args.size, width=args.size,
@@ -687,7 +702,7 @@ def main():
         result["latent_psnr_vs_full_token_random_weights_db"] = {
             "value": O.psnr(out.cpu(), van.cpu()),
             "note": "random weights: not the quality metric (needs a real checkpoint; unmeasurable in this image)"}
-    if rank == 0 and world == 1 and not args.toy and not args.no_vanilla:
+    if solo_full and not args.toy and not args.no_vanilla:
         # SURVEY.md section 8 row f4 / BASELINE.json "end-to-end edit wall-clock": the reference's timing protocol wraps the whole pipe(...) call
         # (src/FluxKontext/main.py:62-73), whose last stage is `vae.decode` (FluxKontext/inplace.py:396-402).  Untimed leg: the final latents
         # of the edit above through the HIP decoder (regione_amd/vae.py: [EXT] AutoencoderKL layout, synthetic weights - timing does not
@@ -721,7 +736,7 @@ def main():
         del enc, mom
         del dec, img
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1:
+    if solo_full:
         # parity with the oracle (torch-CPU bf16 = the reference's dtype path), committed tool reports (tools/parity_full_depth.py; the
         # -m gpu suite re-runs the 16 x 16-grid cases with assertions): round 5 = the HEADLINE shape itself (L = 4096, T = 512, K_e = 1024,
         # 57 blocks, d = 3072: one FULL step with store + one REGION step) and the 28-step loops at full width AND depth; round 4 = the
@@ -750,7 +765,7 @@ def main():
                 par[name].update(label)
         if len(par) > 2:
             result["parity_full_depth_db"] = par
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if solo_full and not args.no_cpu_baseline:
         plan = "".join(O.derive_schedule(L, "flux", 6, 2, "16", 0.04))
         result["cpu_baseline"] = cpu_baseline(cfg, T, N, K_e, plan)
     if rank == 0:

@@ -218,11 +218,11 @@ def test_bench_one_rank_executes_rccl_init_all_gather_and_max_reduce():
 
 
 def test_bench_json_contract_single_gpu():
-    """`python bench.py` prints exactly one JSON line with the fields the driver and SURVEY.md section 8(d) ask for (toy trunk
-    so that the CPU-baseline leg takes seconds; the field set does not depend on the size)."""
+    """`python bench.py --full` prints exactly one JSON line with the fields the driver and SURVEY.md section 8(d) ask for (toy
+    trunk so that the CPU-baseline leg takes seconds; the field set does not depend on the size)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "1", "--warmup", "1", "--toy"], cwd=root,
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "1", "--warmup", "1", "--toy", "--full"], cwd=root,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -246,6 +246,30 @@ def test_bench_json_contract_single_gpu():
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "steps/s" and cb["value"] > 0 and cb["cores"] >= 1 and cb["sample"]
     assert abs(d["value"] - 28 * d["steps"] / (d["ms_per_step"] * 1e-3 * d["steps"])) < 1e-6 * d["value"]
+    # the untimed legs of --full: the plan and per-kind step times of two instrumented edits, full-token denoising
+    assert sum(v["n"] for v in d["step_ms_by_kind"].values()) == 28 and ", plan " in d["config"]["workload"]
+    assert d["full_token"]["edit_wall_clock_s"] > 0 and d["speedup_vs_full_token"] > 0
+
+
+def test_bench_plain_run_leaves_the_untimed_legs_to_full():
+    """`python bench.py` without `--full` prints the headline fields and the roofline of its last timed edit, and runs none of
+    the untimed legs: no per-kind step times, plan, full-token leg, parity reports or CPU baseline on its line."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "1", "--warmup", "1", "--toy"], cwd=root,
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["unit"] == "steps/s" and d["steps"] == 1 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["metric"].startswith("denoising steps/sec") and d["ms_per_step"] > 0
+    assert abs(d["value"] - 28 * d["steps"] / (d["ms_per_step"] * 1e-3 * d["steps"])) < 1e-6 * d["value"]
+    assert d["roofline"]["launches"] > 0 and d["roofline_attention"]["launches"] > 0
+    for k in ("step_ms_by_kind", "loop_mfma_frac", "region_5pct", "full_token", "speedup_vs_full_token", "end_to_end",
+              "parity_full_depth_db", "cpu_baseline"):
+        assert k not in d, k
+    assert "K_e=" in d["config"]["workload"] and "plan" not in d["config"]["workload"]
 
 
 def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):

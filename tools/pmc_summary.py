@@ -4,7 +4,7 @@
     cd /tmp && export TMPDIR=/tmp
     rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_BUSY_CYCLES SQ_WAVE_CYCLES \
               SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE -d out/mfma -o m -- \
-              python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-vanilla
+              python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-vanilla --no-5pct
     python tools/pmc_summary.py out/mfma/m_results.db > profiles/rNN_pmc_mfma.json
 
 Derived (gfx94x formula, ROCm 7.2 ships no gfx950 section): MfmaUtil = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE * 256 CUs * 4 SIMDs);
@@ -51,7 +51,7 @@ def main():
         if p.get("SQ_LDS_IDX_ACTIVE"):
             row["lds_bank_conflict_share"] = p.get("SQ_LDS_BANK_CONFLICT", 0.0) / p["SQ_LDS_IDX_ACTIVE"]
         out[k] = row
-    out["note"] = ("one rocprofv3 --kernel-trace --pmc pass over `bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-vanilla`; "
+    out["note"] = ("one rocprofv3 --kernel-trace --pmc pass over `bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-vanilla --no-5pct`; "
                    "mfma_util = sum over instances of SQ_VALU_MFMA_BUSY_CYCLES / (mean GRBM_GUI_ACTIVE * 256 CUs * 4 SIMDs) (gfx94x derived-metric formula); kernels are "
                    "slowed by the counter collection, ratios are what to read")
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

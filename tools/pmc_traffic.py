@@ -2,8 +2,8 @@
 """Per-launch HBM-side traffic of the MFMA kernels from two rocprofv3 PMC passes (rocpd sqlite output).
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --kernel-trace --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum -d out/rd -o rd -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-vanilla
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE                            -d out/wr -o wr -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-vanilla
+    rocprofv3 --kernel-trace --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum -d out/rd -o rd -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-vanilla --no-5pct
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE                            -d out/wr -o wr -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-vanilla --no-5pct
     python tools/pmc_traffic.py out/rd/rd_results.db out/wr/wr_results.db > profiles/rNN_pmc_traffic.json
 
 FETCH_SIZE itself segfaults rocprofv3 on this image, so the read side is rebuilt from its expression
@@ -77,8 +77,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("rd_db")
     ap.add_argument("wr_db")
-    ap.add_argument("--edits", type=int, default=2, help="RegionE edits the profiled command ran (`bench.py --steps 1 --warmup 0 --no-5pct "
-                                                         "--no-vanilla` = 1 timed + 1 characterising = 2)")
+    ap.add_argument("--edits", type=int, default=3, help="RegionE edits the profiled command ran (`bench.py --full --steps 1 --warmup 0 "
+                                                         "--no-cpu-baseline --no-vanilla --no-5pct` = 1 timed + 2 characterising = 3)")
     ap.add_argument("--lat-db", default=None, help="optional third pass: --pmc TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_sum")
     args = ap.parse_args()
     rd, wr = per_kernel(args.rd_db), per_kernel(args.wr_db)

@@ -33,7 +33,7 @@ cat $O/gemm_store_ab_epilogues.txt | head -40
 for rep in 1 2; do
   for v in old fast pers; do
     case $v in old) E="RGN_LIB=$OLD RGN_PLAN_OVERRIDE=gemm_persistent=0";; fast) E="RGN_PLAN_OVERRIDE=gemm_persistent=0";; pers) E="RGN_PLAN_OVERRIDE=";; esac
-    env $E python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-5pct --no-vanilla 2>/dev/null > $O/gemm_store_ab_bench_${v}_$rep.json
+    env $E python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-5pct --no-vanilla 2>/dev/null > $O/gemm_store_ab_bench_${v}_$rep.json
     python - <<PY
 import json
 d=json.load(open("$O/gemm_store_ab_bench_${v}_$rep.json"))
