@@ -415,6 +415,35 @@ int rgn_padded_to_nchw_cvt(const void* X, int ld, void* O, int Co, int H, int W,
  * bf16 rounding of the output; border rows and channels >= C_valid of Y are written as zeros.  gamma: [C_pad] bf16, 16-byte aligned. */
 int rgn_rms_norm_silu(const void* X, void* Y, int Hp, int Wp, int C_valid, int C_pad, const void* gamma, int silu, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * f4  text encoders of FLUX.1 Kontext: `encode_prompt` (FluxKontext/inplace.py:185-211) runs [EXT] transformers CLIPTextModel
+ * (pooler_output) and T5EncoderModel (last_hidden_state).  Projections are rgn_gemm_bf16; these are the pieces around it.
+ *
+ * Self-attention with head dim 64, read straight from the fused QKV GEMM output: QKV [L, 3 H 64] bf16 (columns q | k | v, head-major
+ * inside each), O [L, H 64] bf16; both 16-byte aligned.  Per head and query i:
+ *   O[i] = softmax_j(scale * q_i . k_j + bias[h][j - i + Lmax - 1]) v_j     over j < L (j <= i when causal != 0)
+ * bias: NULL or a bf16 table [H][2 Lmax - 1] (T5's relative-position bias for every offset), L <= Lmax <= 4096.  Scores and the online
+ * softmax in fp32, P rounded to bf16 for the P V MFMA, O rounded once; fixed reduction order: a repeated call is bit-identical.
+ * 1 <= L <= 4096, 1 <= H <= 1024, 0 < scale < inf (T5: 1; CLIP: 1/8). */
+int rgn_text_attention_bf16(const void* QKV, void* O, int L, int H, float scale, int causal, const void* bias, int Lmax, void* stream);
+/* out[i, :] = tok[ids[i], :] (+ pos[i, :], one bf16 rounding: CLIP's `token_embedding + position_embedding`); an id outside
+ * [0, vocab) gives a zero row (the table is never read out of bounds).  ids int64 [L]; tok [vocab, d], pos [npos, d] (NULL: T5's
+ * plain gather; else L <= npos), out [L, d]: bf16, 16-byte aligned, d % 8 == 0. */
+int rgn_text_embed(const int64_t* ids, int L, const void* tok, int vocab, const void* pos, int npos, void* out, int d, void* stream);
+/* T5 v1.1 gated-GELU product: y[m, f] = bf16(x[m, F + f] * x[m, f]) - x is the output of ONE rgn_gemm_bf16 over [wi_1 ; wi_0] with
+ * RGN_EPI_GELU from column F (linear half, then GELU-tanh half); `hidden_gelu * hidden_linear` of T5DenseGatedActDense.
+ * F % 8 == 0, ldx >= 2 F, ldy >= F (strides multiples of 8), x and y 16-byte aligned. */
+int rgn_geglu_bf16(const void* x, int ldx, void* y, int ldy, int M, int F, void* stream);
+/* CLIP's quick_gelu on bf16 with the eager op sequence's roundings: t = bf16(1.702 x), s = bf16(sigmoid(t)), y = bf16(x s).  y may be x. */
+int rgn_quick_gelu_bf16(const void* x, void* y, size_t n, void* stream);
+/* Affine LayerNorm over rows of width d (nn.LayerNorm on bf16): fp32 mean, fp32 variance about it, both in a fixed order,
+ * out = bf16(gamma * (rstd * (x - mean)) + beta).  gamma, beta: [d] bf16. */
+int rgn_layer_norm_rows(const void* x, int ldx, const void* gamma, const void* beta, void* out, int ldo, int M, int d, float eps,
+                        void* stream);
+/* CLIPTextModel's pooled row, chosen on the device (no host sync): index = argmax(int32(ids)) when eos_token_id == 2, else the first
+ * position with int32(ids) == eos_token_id (0 when there is none); out[:d] = x[index, :d].  ids int64 [L]; x, out bf16. */
+int rgn_text_pool_row(const int64_t* ids, int L, int eos_token_id, const void* x, int ldx, int d, void* out, void* stream);
+
 /* Device properties the host side needs for roofline reporting (no torch types). */
 int rgn_device_info(int* cu_count, int* clock_khz, size_t* hbm_bytes);
 

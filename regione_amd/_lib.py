@@ -122,6 +122,13 @@ SIGNATURES = {
     "rgn_padded_to_nchw": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
     "rgn_padded_to_nchw_cvt": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p],
     "rgn_rms_norm_silu": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p],
+    # f4: text encoders of FLUX.1 Kontext (CLIP-L, T5-XXL; csrc/text.hip)
+    "rgn_text_attention_bf16": [_c_void_p, _c_void_p, _c_int, _c_int, _c_float, _c_int, _c_void_p, _c_int, _c_void_p],
+    "rgn_text_embed": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p],
+    "rgn_geglu_bf16": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
+    "rgn_quick_gelu_bf16": [_c_void_p, _c_void_p, C.c_size_t, _c_void_p],
+    "rgn_layer_norm_rows": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p],
+    "rgn_text_pool_row": [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p],
 }
 _RESTYPE = {"rgn_last_error": C.c_char_p, "rgn_abi_struct_bytes": C.c_size_t, "rgn_attention_workspace_bytes": C.c_size_t,
             "rgn_gemm_workspace_bytes": C.c_size_t, "rgn_groupnorm_workspace_bytes": C.c_size_t,

@@ -313,6 +313,76 @@ def hip_vae_encoder_for(host, dev):
     return host._regione_hip_vae_encoder
 
 
+_TEXT_ENCODERS = (("text_encoder", "clip"), ("text_encoder_2", "t5"))
+
+
+def _adopt_text_encoder(mod, kind: str, dev):
+    """(HIP encoder, None) or (None, the reason the host module keeps running)."""
+    from . import text_encoders as TE
+    cfg = getattr(mod, "config", None)
+    if cfg is None or not hasattr(mod, "state_dict"):
+        return None, f"{type(mod).__name__} is not a transformers module"
+    why = TE.clip_refusal(cfg) if kind == "clip" else TE.t5_refusal(cfg)
+    if why is None and type(mod).__name__ != ("CLIPTextModel" if kind == "clip" else "T5EncoderModel"):
+        why = f"{type(mod).__name__} (another layout: the kernels restate CLIPTextModel / T5EncoderModel)"
+    if why is None and any("lora" in n.lower() for n, _ in mod.named_modules()):
+        why = "PEFT / LoRA layers in the module"
+    if why is not None:
+        return None, why
+    try:
+        return (TE.HipClipTextModel(mod, dev) if kind == "clip" else TE.HipT5EncoderModel(mod, dev)), None
+    except _lib.RegionEHipError as e:
+        return None, str(e)
+
+
+def hip_text_encoders_for(host, dev):
+    """(CLIP, T5) of a FLUX.1 Kontext host adopted onto the HIP kernels (regione_amd/text_encoders.py), once
+    per host pipeline and kept on it as `_regione_hip_text`.  A module the kernels do not cover (another layout, head dim != 64, non-bf16
+    weights, PEFT / LoRA layers) stays the host's, with one warning naming the reason: None in its place.  A host without the modules
+    gets (None, None) silently; `pipe._regione_hip_text = False` before the first call keeps the host modules on purpose."""
+    cached = host.__dict__.get("_regione_hip_text", _NO_HIP_VAE)
+    if cached is False or cached is None:
+        return None, None
+    if cached is not _NO_HIP_VAE:
+        return cached
+    got = []
+    for attr, kind in _TEXT_ENCODERS:
+        mod = getattr(host, attr, None)
+        enc, why = (None, None) if mod is None else _adopt_text_encoder(mod, kind, dev)
+        if why is not None:
+            warnings.warn(f"{attr} kept on the host module: {why}", RuntimeWarning, stacklevel=3)
+        got.append(enc)
+    host._regione_hip_text = tuple(got)
+    return host._regione_hip_text
+
+
+class _hip_text_encoders:
+    """`with _hip_text_encoders(host, dev): host.encode_prompt(...)` - the host's own `encode_prompt` (tokenizers, `_get_clip_prompt_embeds`,
+    `_get_t5_prompt_embeds`: its code, untouched) runs with `text_encoder` / `text_encoder_2` bound to the adopted HIP encoders; the
+    bindings are undone on exit, an exception included."""
+
+    def __init__(self, host, dev):
+        self.host, self.dev, self.saved = host, dev, []
+
+    def __enter__(self):
+        d = self.host.__dict__
+        for (attr, _), enc in zip(_TEXT_ENCODERS, hip_text_encoders_for(self.host, self.dev)):
+            if enc is not None:
+                self.saved.append((attr, d.get(attr, _NO_HIP_VAE)))
+                d[attr] = enc                  # the instance dict: no pipeline __setattr__ (diffusers would re-register the component)
+        return self
+
+    def __exit__(self, *a):
+        d = self.host.__dict__
+        for attr, orig in reversed(self.saved):
+            if orig is _NO_HIP_VAE:
+                del d[attr]
+            else:
+                d[attr] = orig
+        self.saved = []
+        return False
+
+
 class _hip_vae_encode:
     """`with _hip_vae_encode(host, dev): host.prepare_latents(...)` - the host's own `prepare_latents` (resize, `_encode_vae_image`,
     `retrieve_latents`, shift / scale, packing: its code, untouched) runs with `vae.encode` answered by the HIP encoder for single 4-D
@@ -427,14 +497,15 @@ def _hosted_flux(host, eng, image=None, prompt=None, prompt_2=None, negative_pro
     exec_dev = getattr(host, "_execution_device", dev)
     has_neg = negative_prompt is not None or (negative_prompt_embeds is not None and negative_pooled_prompt_embeds is not None)
     do_true_cfg = true_cfg_scale > 1 and has_neg
-    prompt_embeds, pooled_prompt_embeds, _ = host.encode_prompt(
-        prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
-        device=exec_dev, num_images_per_prompt=1, max_sequence_length=max_sequence_length, lora_scale=None)
-    if do_true_cfg:
-        negative_prompt_embeds, negative_pooled_prompt_embeds, _ = host.encode_prompt(
-            prompt=negative_prompt, prompt_2=negative_prompt_2, prompt_embeds=negative_prompt_embeds,
-            pooled_prompt_embeds=negative_pooled_prompt_embeds, device=exec_dev, num_images_per_prompt=1,
-            max_sequence_length=max_sequence_length, lora_scale=None)
+    with _hip_text_encoders(host, dev):
+        prompt_embeds, pooled_prompt_embeds, _ = host.encode_prompt(
+            prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
+            device=exec_dev, num_images_per_prompt=1, max_sequence_length=max_sequence_length, lora_scale=None)
+        if do_true_cfg:
+            negative_prompt_embeds, negative_pooled_prompt_embeds, _ = host.encode_prompt(
+                prompt=negative_prompt, prompt_2=negative_prompt_2, prompt_embeds=negative_prompt_embeds,
+                pooled_prompt_embeds=negative_pooled_prompt_embeds, device=exec_dev, num_images_per_prompt=1,
+                max_sequence_length=max_sequence_length, lora_scale=None)
     # 4. latents: the host packs noise and the VAE-encoded condition image (inplace.py:210-226)
     with _hip_vae_encode(host, dev):
         latents, image_latents, _, _ = host.prepare_latents(image, 1, eng.transformer.cfg_model.in_channels // 4, height, width,
@@ -725,6 +796,8 @@ def attach(pipe, device="cuda"):
             dev = eng.transformer.device
             hip_vae_for(pipe, dev)
             hip_vae_encoder_for(pipe, dev)
+        if _host_name(pipe) == "FluxKontextPipeline":         # the text encoders of encode_prompt likewise (CLIP-L, T5-XXL)
+            hip_text_encoders_for(pipe, eng.transformer.device)
     return eng
 
 
