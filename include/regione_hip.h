@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 107
+#define RGN_ABI_VERSION 108
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -443,6 +443,30 @@ int rgn_layer_norm_rows(const void* x, int ldx, const void* gamma, const void* b
 /* CLIPTextModel's pooled row, chosen on the device (no host sync): index = argmax(int32(ids)) when eos_token_id == 2, else the first
  * position with int32(ids) == eos_token_id (0 when there is none); out[:d] = x[index, :d].  ids int64 [L]; x, out bf16. */
 int rgn_text_pool_row(const int64_t* ids, int L, int eos_token_id, const void* x, int ldx, int d, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * f4  language model of the Qwen2.5-VL prompt encoder: `encode_prompt` of QwenImageEditPipeline / QwenImageEditPlusPipeline
+ * (QwenImageEdit/inplace.py, QwenImageEditPlus/inplace.py) runs [EXT] transformers Qwen2_5_VLForConditionalGeneration.  Projections are
+ * rgn_gemm_bf16, the norms rgn_rms_norm_rows, the embedding rgn_text_embed; these are the pieces around them.
+ *
+ * Causal grouped-query self-attention with head dim 128, read straight from the fused QKV GEMM output: QKV [L, (Hq + 2 Hkv) 128] bf16
+ * (columns q | k | v, head-major inside each), O [L, Hq 128] bf16; both 16-byte aligned.  Query head h uses KV head h / (Hq / Hkv):
+ *   O[i, h] = softmax_{j <= i}(scale * q_{i,h} . k_{j,kv(h)}) v_{j,kv(h)}
+ * Replaces the attention interface call of Qwen2_5_VLAttention.forward (repeat_kv + softmax(QK^T * scaling + causal mask) V).  Key tiles
+ * wholly above the diagonal are skipped.  Scores and the online softmax in fp32, P rounded to bf16 for the P V MFMA, O accumulated in
+ * fp32 and rounded once; fixed reduction order: a repeated call is bit-identical.
+ * 1 <= L <= 4096, 1 <= Hkv <= Hq <= 1024, Hq % Hkv == 0, 0 < scale < inf (Qwen2.5-VL-7B: Hq 28, Hkv 4, scale 1/sqrt(128)). */
+int rgn_lm_attention_bf16(const void* QKV, void* O, int L, int Hq, int Hkv, float scale, void* stream);
+/* Multimodal RoPE on the q and k columns (the first (Hq + Hkv) 128 of each row) of that QKV buffer, in place; the v columns are not
+ * touched.  cos, sin: bf16 [L, 128], the tables AFTER the mrope_section selection (one row per token, shared by every head).  Replaces
+ * `apply_multimodal_rotary_pos_emb(q, k, cos, sin, mrope_section)` with its eager bf16 op sequence, three roundings:
+ *   x <- bf16(bf16(x * cos) + bf16(rotate_half(x) * sin)),   rotate_half(x) = [-x[64:], x[:64]] per head.
+ * ld = row stride of QKV in elements (>= (Hq + 2 Hkv) 128, a multiple of 8); QKV, cos, sin 16-byte aligned. */
+int rgn_mrope_bf16(void* QKV, int ld, const void* cos, const void* sin, int L, int Hq, int Hkv, void* stream);
+/* SwiGLU product: y[m, f] = bf16(bf16(silu(x[m, f])) * x[m, F + f]) - x is the output of ONE rgn_gemm_bf16 over [gate_proj ; up_proj];
+ * `self.act_fn(self.gate_proj(x)) * self.up_proj(x)` of Qwen2MLP.forward with its two roundings.
+ * F % 8 == 0, ldx >= 2 F, ldy >= F (strides multiples of 8), x and y 16-byte aligned. */
+int rgn_swiglu_bf16(const void* x, int ldx, void* y, int ldy, int M, int F, void* stream);
 
 /* Device properties the host side needs for roofline reporting (no torch types). */
 int rgn_device_info(int* cu_count, int* clock_khz, size_t* hbm_bytes);

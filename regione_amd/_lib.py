@@ -129,6 +129,10 @@ SIGNATURES = {
     "rgn_quick_gelu_bf16": [_c_void_p, _c_void_p, C.c_size_t, _c_void_p],
     "rgn_layer_norm_rows": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p],
     "rgn_text_pool_row": [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p],
+    # f4: language model of the Qwen2.5-VL prompt encoder (csrc/text.hip)
+    "rgn_lm_attention_bf16": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p],
+    "rgn_mrope_bf16": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
+    "rgn_swiglu_bf16": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
 }
 _RESTYPE = {"rgn_last_error": C.c_char_p, "rgn_abi_struct_bytes": C.c_size_t, "rgn_attention_workspace_bytes": C.c_size_t,
             "rgn_gemm_workspace_bytes": C.c_size_t, "rgn_groupnorm_workspace_bytes": C.c_size_t,

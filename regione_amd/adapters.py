@@ -383,6 +383,65 @@ class _hip_text_encoders:
         return False
 
 
+_QWEN_TEXT_HOSTS = ("QwenImageEditPipeline", "QwenImageEditPlusPipeline")
+
+
+def hip_qwen_text_encoder_for(host, dev):
+    """The host's Qwen2.5-VL prompt encoder with its language model adopted onto the HIP kernels (regione_amd/qwen_text_encoder.py;
+    SURVEY.md section 8 row f4), once per host pipeline and kept on it as `_regione_hip_qwen_text`.  A module the kernels do not cover
+    (`qwen25vl_refusal`: sliding-window layers, another head dim, ...; non-bf16 weights; PEFT / LoRA layers) stays the host's, with one
+    warning naming the reason.  A `text_encoder` that is not a `Qwen2_5_VLForConditionalGeneration` is left alone silently;
+    `pipe._regione_hip_text = False` before the first call keeps the host module on purpose."""
+    if host.__dict__.get("_regione_hip_text", _NO_HIP_VAE) is False:
+        return None
+    cached = host.__dict__.get("_regione_hip_qwen_text", _NO_HIP_VAE)
+    if cached is not _NO_HIP_VAE:
+        return cached
+    mod = getattr(host, "text_encoder", None)
+    enc = None
+    if type(mod).__name__ == "Qwen2_5_VLForConditionalGeneration" and getattr(mod, "config", None) is not None:
+        from . import qwen_text_encoder as QT
+        why = QT.qwen25vl_refusal(mod.config)
+        if why is None and any("lora" in n.lower() for n, _ in mod.named_modules()):
+            why = "PEFT / LoRA layers in the module"
+        if why is None:
+            try:
+                enc = QT.HipQwen25VLTextEncoder(mod, dev)
+            except _lib.RegionEHipError as e:
+                why = str(e)
+        if why is not None:
+            warnings.warn(f"text_encoder kept on the host module: {why}", RuntimeWarning, stacklevel=3)
+    host._regione_hip_qwen_text = enc
+    return enc
+
+
+class _hip_qwen_text_encoder:
+    """`with _hip_qwen_text_encoder(host, dev): host.encode_prompt(...)` - the host's own `encode_prompt` (the template, the processor,
+    `_get_qwen_prompt_embeds`, `_extract_masked_hidden`: its code, untouched) runs with `text_encoder` bound to the adopted HIP encoder,
+    which answers what that code touches (the call, `.dtype`, `.device`, `.config`); the binding is undone on exit, an exception included."""
+
+    def __init__(self, host, dev):
+        self.host, self.dev, self.saved = host, dev, None
+
+    def __enter__(self):
+        enc = hip_qwen_text_encoder_for(self.host, self.dev)
+        if enc is not None:
+            d = self.host.__dict__
+            self.saved = (d.get("text_encoder", _NO_HIP_VAE),)
+            d["text_encoder"] = enc                # the instance dict: no pipeline __setattr__ (diffusers would re-register the component)
+        return self
+
+    def __exit__(self, *a):
+        if self.saved is not None:
+            d = self.host.__dict__
+            if self.saved[0] is _NO_HIP_VAE:
+                del d["text_encoder"]
+            else:
+                d["text_encoder"] = self.saved[0]
+            self.saved = None
+        return False
+
+
 class _hip_vae_encode:
     """`with _hip_vae_encode(host, dev): host.prepare_latents(...)` - the host's own `prepare_latents` (resize, `_encode_vae_image`,
     `retrieve_latents`, shift / scale, packing: its code, untouched) runs with `vae.encode` answered by the HIP encoder for single 4-D
@@ -711,9 +770,10 @@ def _hosted_qwen(host, eng, image=None, prompt=None, negative_prompt=None, true_
     do_true_cfg = true_cfg_scale > 1 and has_neg
     enc = lambda p, e, m: host.encode_prompt(image=prompt_image, prompt=p, prompt_embeds=e, prompt_embeds_mask=m, device=exec_dev,
                                              num_images_per_prompt=1, max_sequence_length=max_sequence_length)
-    prompt_embeds, prompt_embeds_mask = enc(prompt, prompt_embeds, prompt_embeds_mask)
-    if do_true_cfg:
-        negative_prompt_embeds, negative_prompt_embeds_mask = enc(negative_prompt, negative_prompt_embeds, negative_prompt_embeds_mask)
+    with _hip_qwen_text_encoder(host, dev):                # the Qwen2.5-VL language model of encode_prompt on the HIP kernels
+        prompt_embeds, prompt_embeds_mask = enc(prompt, prompt_embeds, prompt_embeds_mask)
+        if do_true_cfg:
+            negative_prompt_embeds, negative_prompt_embeds_mask = enc(negative_prompt, negative_prompt_embeds, negative_prompt_embeds_mask)
     with _hip_vae_encode(host, dev):                       # vae.encode of the condition images on the HIP encoder (Qwen VAE: one frame each)
         latents, image_latents = host.prepare_latents(image, 1, eng.transformer.cfg_model.in_channels // 4, height, width,
                                                       prompt_embeds.dtype, exec_dev, generator, latents)
@@ -798,6 +858,8 @@ def attach(pipe, device="cuda"):
             hip_vae_encoder_for(pipe, dev)
         if _host_name(pipe) == "FluxKontextPipeline":         # the text encoders of encode_prompt likewise (CLIP-L, T5-XXL)
             hip_text_encoders_for(pipe, eng.transformer.device)
+        if _host_name(pipe) in _QWEN_TEXT_HOSTS:              # Qwen-Image-Edit's prompt encoder: the Qwen2.5-VL language model
+            hip_qwen_text_encoder_for(pipe, eng.transformer.device)
     return eng
 
 

@@ -1,0 +1,325 @@
+"""The language model of the Qwen2.5-VL prompt encoder on the HIP kernels (`encode_prompt` of Qwen-Image-Edit).
+
+`encode_prompt` of QwenImageEditPipeline / QwenImageEditPlusPipeline runs diffusers' `_get_qwen_prompt_embeds`: the [EXT] transformers
+`Qwen2_5_VLForConditionalGeneration` over the prompt template, the condition images' tokens and the instruction, reading
+`hidden_states[-1]`.  The decoder stack is restated here on the library's kernels, rounding where the eager bf16 module rounds:
+
+  layer   n = rms_norm_rows(h)                       Qwen2_5_VLRMSNorm (fp32 variance, w * bf16(x * rsqrt))
+          qkv = n @ [q; k; v]^T + [bq; bk; bv]       one rgn_gemm_bf16 over the concatenated weight: [L, (Hq + 2 Hkv) 128]
+          mrope(qkv, cos, sin)                       apply_multimodal_rotary_pos_emb on the q and k columns, in place
+          a = lm_attention(qkv)                      causal, grouped-query (query head h reads KV head h / (Hq / Hkv)), scale 1/sqrt(128)
+          h = h + a @ o^T                            RGN_EPI_GATE_RESID with a gate of ones = torch's bf16 `h + linear(a)`
+          ff = n2 @ [gate; up]^T                     one GEMM, then swiglu: bf16(bf16(silu(gate)) * up)
+          h = h + swiglu(ff) @ down^T                the gated residual again
+  final   rms_norm_rows(h)                           `model.language_model.norm`
+
+Positions are the adopted module's own: `module.model.compute_3d_position_ids(...)` with the caller's arguments (None -> the plain arange
+of Qwen2_5_VLTextModel.forward); the cos / sin tables are built on the CPU with the module's `rotary_emb` arithmetic and `inv_freq`
+buffer, the `mrope_section` selection applied once, cast to bf16 and copied in one host-to-device copy per call.  The vision tower stays the
+host's eager module (`get_image_features`); its embeddings are placed at the image-token rows by rgn_scatter_rows.
+
+There is no eager fallback inside: what the kernels do not implement raises RegionEHipError before any launch, and the adapter
+(regione_amd/adapters.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
+only; every call returns freshly allocated outputs.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+
+from . import _lib, ops
+from .text_encoders import _Buffers, _bf16_only, _check_k, _check_names, _refuse, _source
+
+_p, _stream = ops._p, ops._stream
+
+HEAD_DIM = 128
+LM = "model.language_model."
+NOT_ADOPTED = ("lm_head.", "model.visual.")
+
+
+class QwenTextEncoderOutput:
+    """What diffusers reads of the Qwen2.5-VL output: `.hidden_states[-1]` (and `.last_hidden_state`, the same tensor: the final hidden
+    state AFTER the final norm, which is what transformers returns as the last entry).  The EARLIER entries of `hidden_states` (the
+    embeddings and the per-layer states) are ABSENT: the tuple has that one element."""
+
+    def __init__(self, last_hidden_state: torch.Tensor, with_hidden_states: bool):
+        self.last_hidden_state = last_hidden_state
+        self.hidden_states = (last_hidden_state,) if with_hidden_states else None
+
+    def to_tuple(self):
+        return tuple(t for t in (self.last_hidden_state, self.hidden_states) if t is not None)
+
+    def __getitem__(self, i):
+        if isinstance(i, str):
+            return getattr(self, i)
+        return self.to_tuple()[i]
+
+
+def _text_config(cfg):
+    return getattr(cfg, "text_config", None) or cfg
+
+
+def qwen25vl_refusal(cfg) -> Optional[str]:
+    """Why a Qwen2.5-VL config (the composite one or its text_config) is not one the kernels implement (None: it is)."""
+    tc = _text_config(cfg)
+    if getattr(tc, "model_type", None) not in ("qwen2_5_vl", "qwen2_5_vl_text"):
+        return f"model_type {getattr(tc, 'model_type', None)!r} (the Qwen2.5-VL language model is covered)"
+    d, hq, hkv = tc.hidden_size, tc.num_attention_heads, tc.num_key_value_heads
+    if d % hq or d // hq != HEAD_DIM:
+        return f"head dim {d / hq:g} (the attention kernel is head-dim {HEAD_DIM})"
+    if hkv < 1 or hq % hkv:
+        return f"{hq} query heads over {hkv} KV heads (Hq % Hkv != 0)"
+    rope = getattr(tc, "rope_parameters", None) or {}
+    if rope.get("rope_type", "default") != "default":
+        return f"rope_type {rope.get('rope_type')!r} (the default RoPE is implemented)"
+    sec = list(rope.get("mrope_section") or [])
+    if len(sec) != 3 or 2 * sum(sec) != HEAD_DIM:
+        return f"mrope_section {sec} (three sections summing to {HEAD_DIM // 2})"
+    if "sliding_attention" in (getattr(tc, "layer_types", None) or []):
+        return "sliding-window layers (full causal attention is implemented)"
+    if getattr(tc, "hidden_act", None) != "silu":
+        return f"hidden_act {getattr(tc, 'hidden_act', None)!r} (silu is implemented)"
+    bad = {k: v for k, v in dict(hidden_size=d, intermediate_size=tc.intermediate_size).items() if v % 64}
+    if bad:
+        return f"widths {bad} are not multiples of 64"
+    return None
+
+
+def qwen25vl_param_shapes(cfg) -> Dict[str, tuple]:
+    tc = _text_config(cfg)
+    d, F, hq, hkv = tc.hidden_size, tc.intermediate_size, tc.num_attention_heads, tc.num_key_value_heads
+    s = {LM + "embed_tokens.weight": (tc.vocab_size, d), LM + "norm.weight": (d,)}
+    for i in range(tc.num_hidden_layers):
+        b = f"{LM}layers.{i}."
+        for n, rows in (("q", hq * HEAD_DIM), ("k", hkv * HEAD_DIM), ("v", hkv * HEAD_DIM)):
+            s[f"{b}self_attn.{n}_proj.weight"], s[f"{b}self_attn.{n}_proj.bias"] = (rows, d), (rows,)
+        s[f"{b}self_attn.o_proj.weight"] = (d, hq * HEAD_DIM)
+        s[f"{b}mlp.gate_proj.weight"], s[f"{b}mlp.up_proj.weight"], s[f"{b}mlp.down_proj.weight"] = (F, d), (F, d), (d, F)
+        s[f"{b}input_layernorm.weight"], s[f"{b}post_attention_layernorm.weight"] = (d,), (d,)
+    return s
+
+
+def default_inv_freq(cfg) -> torch.Tensor:
+    """Qwen2_5_VLRotaryEmbedding.compute_default_rope_parameters on the CPU (used when no module is at hand)."""
+    base = _text_config(cfg).rope_parameters["rope_theta"]
+    return 1.0 / (base ** (torch.arange(0, HEAD_DIM, 2, dtype=torch.float) / HEAD_DIM))
+
+
+def mrope_tables(inv_freq: torch.Tensor, position_ids: torch.Tensor, mrope_section) -> torch.Tensor:
+    """[2, B, L, 128] bf16 on the CPU: (cos, sin) of Qwen2_5_VLRotaryEmbedding.forward for `position_ids` [3, B, L] in fp32, then the
+    `mrope_section` selection of apply_multimodal_rotary_pos_emb (chunk i of the channel axis from position axis i % 3), then the cast."""
+    inv = inv_freq.detach().float().cpu()
+    pos = position_ids.detach().cpu()
+    inv_e = inv[None, None, :, None].expand(3, pos.shape[1], -1, 1)
+    pos_e = pos[:, :, None, :].float()
+    freqs = (inv_e @ pos_e).transpose(2, 3)
+    emb = torch.cat((freqs, freqs), dim=-1)
+    sec = list(mrope_section) * 2
+    pick = lambda t: torch.cat([m[i % 3] for i, m in enumerate(t.split(sec, dim=-1))], dim=-1)
+    return torch.stack([pick(emb.cos()), pick(emb.sin())]).to(torch.bfloat16).contiguous()
+
+
+def valid_lengths(attention_mask: Optional[torch.Tensor], B: int, L: int, what: str = "HipQwen25VLTextEncoder"):
+    """Valid length per row of a [B, L] mask that is a run of ones followed by zeros (right padding); anything else is refused."""
+    if attention_mask is None:
+        return [L] * B
+    m = attention_mask.detach().cpu()
+    if tuple(m.shape) != (B, L):
+        _refuse(what, f"attention_mask of shape {tuple(m.shape)} for input_ids [{B}, {L}]")
+    m = m != 0
+    n = m.sum(dim=1)
+    want = torch.arange(L)[None, :] < n[:, None]
+    if not torch.equal(m, want):
+        _refuse(what, "attention_mask is not a run of ones followed by zeros (left padding and holes are not implemented: rows are "
+                      "processed over their valid prefix)")
+    if int(n.min()) < 1:
+        _refuse(what, "attention_mask with an empty row")
+    return [int(v) for v in n]
+
+
+def image_rows(input_ids: torch.Tensor, lengths, image_token_id: int, n_embeds: int, what: str = "HipQwen25VLTextEncoder"):
+    """Per batch row, the positions of `image_token_id` (CPU); the placeholder count over the batch must equal the embedding rows, as
+    transformers' get_placeholder_mask requires."""
+    ids = input_ids.detach().cpu()
+    hit = ids == image_token_id
+    total = int(hit.sum())
+    if total != n_embeds:
+        raise ValueError(f"Image features and image tokens do not match, tokens: {total}, features: {n_embeds}")
+    rows = []
+    for b, n in enumerate(lengths):
+        if bool(hit[b, n:].any()):
+            _refuse(what, "image tokens in the padded part of a row")
+        rows.append(torch.nonzero(hit[b, :n]).flatten())
+    return rows
+
+
+class HipQwen25VLTextEncoder:
+    """`Qwen2_5_VLForConditionalGeneration(input_ids, attention_mask, pixel_values, image_grid_thw, output_hidden_states=True)` with the
+    language model on the HIP kernels.  Returns an object with `.last_hidden_state` [B, L, d] bf16 and `.hidden_states`, a ONE-element
+    tuple whose `[-1]` is that final hidden state after the final norm - the earlier entries transformers returns (embeddings, per-layer
+    states) are absent.  Padded positions are zero rows."""
+    what = "HipQwen25VLTextEncoder"
+
+    def __init__(self, module_or_state_dict, device=None, config=None, max_length: int = 4096):
+        sd, cfg, dev, mod = _source(module_or_state_dict, config, device, self.what)
+        why = qwen25vl_refusal(cfg)
+        if why:
+            _refuse(self.what, why)
+        if not 1 <= max_length <= 4096:
+            _refuse(self.what, f"max_length {max_length} outside [1, 4096]")
+        tc = _text_config(cfg)
+        self.config, self.device, self.max_length, self.module = cfg, dev, int(max_length), mod
+        self.d, self.F, self.Hq, self.Hkv, self.eps = tc.hidden_size, tc.intermediate_size, tc.num_attention_heads, tc.num_key_value_heads, \
+            float(tc.rms_norm_eps)
+        self.qkv_cols = (self.Hq + 2 * self.Hkv) * HEAD_DIM
+        self.scale = HEAD_DIM ** -0.5
+        self.mrope_section = list(tc.rope_parameters["mrope_section"])
+        self.image_token_id, self.video_token_id = getattr(cfg, "image_token_id", None), getattr(cfg, "video_token_id", None)
+        _check_k(self.what, hidden_size=self.d, intermediate_size=self.F, attention_width=self.Hq * HEAD_DIM)
+        lm = {k: v for k, v in sd.items() if not k.startswith(NOT_ADOPTED)}           # lm_head.* / model.visual.*: known, not adopted
+        _check_names(self.what, lm, qwen25vl_param_shapes(cfg))
+        _bf16_only(self.what, lm)
+
+        def w(k):
+            return lm[LM + k].to(dev, torch.bfloat16).contiguous()
+
+        def cat(b, names, kind):
+            return torch.cat([lm[f"{LM}{b}{n}.{kind}"].to(dev, torch.bfloat16) for n in names]).contiguous()
+        self.tok = w("embed_tokens.weight")                                            # in place: no copy when it is already there
+        self.layers = []
+        for i in range(tc.num_hidden_layers):
+            b = f"layers.{i}."
+            qkv = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")
+            self.layers.append(dict(
+                ln1=w(b + "input_layernorm.weight"), wqkv=cat(b, qkv, "weight"), bqkv=cat(b, qkv, "bias"),
+                wo=w(b + "self_attn.o_proj.weight"), ln2=w(b + "post_attention_layernorm.weight"),
+                wgu=cat(b, ("mlp.gate_proj", "mlp.up_proj"), "weight"), wdown=w(b + "mlp.down_proj.weight")))
+        self.final_ln = w("norm.weight")
+        # the module's own inv_freq buffer (a `.to(bfloat16)` of the module rounds it; the eager forward then uses the rounded one)
+        rot = getattr(getattr(getattr(mod, "model", None), "language_model", None), "rotary_emb", None) if mod is not None else None
+        self.inv_freq = rot.inv_freq.detach().float().cpu() if rot is not None else default_inv_freq(cfg)
+        self.ones = torch.ones(self.d, dtype=torch.bfloat16, device=dev)
+        self.buf = _Buffers(dev)
+
+    @property
+    def dtype(self):
+        return torch.bfloat16
+
+    # ---- host-side preparation (no kernel) -----------------------------------------------------------------------------------------
+    def position_ids_for(self, input_ids, attention_mask=None, image_grid_thw=None, position_ids=None, mm_token_type_ids=None):
+        """[3, B, L] int64: the caller's `position_ids`, else what the adopted module computes (`model.compute_3d_position_ids`), else
+        the arange of Qwen2_5_VLTextModel.forward."""
+        B, L = input_ids.shape
+        if position_ids is None:
+            if self.module is None:
+                _refuse(self.what, "adopted from a state dict (no module to ask for the 3-D positions): pass position_ids")
+            position_ids = self.module.model.compute_3d_position_ids(
+                input_ids=input_ids, image_grid_thw=image_grid_thw, video_grid_thw=None, inputs_embeds=None, attention_mask=attention_mask,
+                past_key_values=None, mm_token_type_ids=mm_token_type_ids)
+            if position_ids is None:
+                position_ids = torch.arange(L).view(1, 1, -1).expand(3, B, -1)
+        if position_ids.ndim == 2:
+            position_ids = position_ids[None, ...].expand(3, position_ids.shape[0], -1)
+        elif position_ids.ndim == 3 and position_ids.shape[0] == 4:
+            position_ids = position_ids[1:]
+        if tuple(position_ids.shape) != (3, B, L):
+            _refuse(self.what, f"position_ids of shape {tuple(position_ids.shape)} for input_ids [{B}, {L}]")
+        return position_ids
+
+    def _prepare(self, input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids, image_embeds, kw):
+        for k in ("pixel_values_videos", "video_grid_thw", "second_per_grid_ts"):
+            if kw.get(k) is not None:
+                _refuse(self.what, f"{k}: videos are not implemented")
+        for k in ("past_key_values", "inputs_embeds", "labels"):
+            if kw.get(k) is not None:
+                _refuse(self.what, f"{k} is not implemented (one prefill pass over input_ids)")
+        for k in ("use_cache", "output_attentions"):
+            if kw.get(k):
+                _refuse(self.what, f"{k}=True is not implemented")
+        known = ("pixel_values_videos", "video_grid_thw", "second_per_grid_ts", "past_key_values", "inputs_embeds", "labels", "use_cache",
+                 "output_attentions")
+        extra = sorted(k for k in kw if k not in known)
+        if extra:
+            _refuse(self.what, f"arguments {extra} are not implemented")
+        if not isinstance(input_ids, torch.Tensor) or input_ids.dim() != 2:
+            _refuse(self.what, "input_ids must be a [B, L] tensor")
+        B, L = input_ids.shape
+        if not 1 <= L <= self.max_length:
+            _refuse(self.what, f"sequence length {L} outside [1, {self.max_length}] (max_length of this adoption)")
+        ids_cpu = input_ids.detach().cpu()
+        if self.video_token_id is not None and bool((ids_cpu == self.video_token_id).any()):
+            _refuse(self.what, "video tokens in input_ids: videos are not implemented")
+        lengths = valid_lengths(attention_mask, B, L, self.what)
+        if pixel_values is not None and image_embeds is not None:
+            _refuse(self.what, "pass pixel_values or image_embeds, not both")
+        if pixel_values is not None and self.module is None:
+            _refuse(self.what, "adopted from a state dict (no vision tower at hand): pass image_embeds instead of pixel_values")
+        pos = self.position_ids_for(input_ids, attention_mask, image_grid_thw, position_ids, mm_token_type_ids)
+        tables = mrope_tables(self.inv_freq, pos, self.mrope_section)
+        return ids_cpu, lengths, tables
+
+    def _image_embeds(self, pixel_values, image_grid_thw, image_embeds):
+        if pixel_values is not None:                       # the vision tower: the host's eager module, as in Qwen2_5_VLModel.forward
+            image_embeds = self.module.get_image_features(pixel_values, image_grid_thw).pooler_output
+        if image_embeds is None:
+            return None
+        if isinstance(image_embeds, (tuple, list)):
+            image_embeds = torch.cat(list(image_embeds), dim=0)
+        if image_embeds.dim() != 2 or image_embeds.shape[1] != self.d:
+            _refuse(self.what, f"image embeddings of shape {tuple(image_embeds.shape)} (rows of width {self.d})")
+        return image_embeds.to(self.device, torch.bfloat16).contiguous()
+
+    # ---- the call --------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def __call__(self, input_ids, attention_mask=None, pixel_values=None, image_grid_thw=None, position_ids=None, mm_token_type_ids=None,
+                 output_hidden_states=False, return_dict=True, image_embeds=None, **kw):
+        ids_cpu, lengths, tables = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids,
+                                                 image_embeds, kw)
+        B, L = ids_cpu.shape
+        emb = self._image_embeds(pixel_values, image_grid_thw, image_embeds)
+        rows = None
+        if emb is not None:
+            if self.image_token_id is None:
+                _refuse(self.what, "the config has no image_token_id")
+            rows = image_rows(ids_cpu, lengths, int(self.image_token_id), emb.shape[0], self.what)
+            idx = torch.cat(rows).to(self.device)
+        ids = input_ids.to(self.device, torch.int64).contiguous()
+        tab = tables.to(self.device)                                              # the one host-to-device copy of the tables
+        Lb = max(lengths)
+        t = self.buf.get(Lb, dict(h=(Lb, self.d), n=(Lb, self.d), qkv=(Lb, self.qkv_cols), a=(Lb, self.Hq * HEAD_DIM), ff=(Lb, 2 * self.F),
+                                  g=(Lb, self.F)))
+        out = torch.empty(B, L, self.d, dtype=torch.bfloat16, device=self.device)
+        lib = _lib.lib()
+        if min(lengths) < L:                                                      # padded positions are zero rows
+            _lib.check(lib.rgn_fill_zero(_p(out), out.numel() * 2, _stream()), "rgn_fill_zero")
+        at = 0
+        for bi, n in enumerate(lengths):
+            h, nn, qkv, a, ff, g = (t[k][:n] for k in ("h", "n", "qkv", "a", "ff", "g"))
+            cos, sin = tab[0, bi], tab[1, bi]
+            rc = lib.rgn_text_embed(_p(ids[bi]), n, _p(self.tok), self.tok.shape[0], None, 0, _p(h), self.d, _stream())
+            _lib.check(rc, "rgn_text_embed")
+            if rows is not None and rows[bi].numel():
+                k = rows[bi].numel()
+                rc = lib.rgn_scatter_rows(_p(emb[at:at + k]), _p(idx[at:at + k]), _p(h), k, self.d * 2, _stream())
+                _lib.check(rc, "rgn_scatter_rows")
+                at += k
+            for p in self.layers:
+                self._rms(h, p["ln1"], nn)
+                ops.gemm(nn, p["wqkv"], p["bqkv"], qkv)
+                rc = lib.rgn_mrope_bf16(_p(qkv), qkv.stride(0), _p(cos), _p(sin), n, self.Hq, self.Hkv, _stream())
+                _lib.check(rc, "rgn_mrope_bf16")
+                rc = lib.rgn_lm_attention_bf16(_p(qkv), _p(a), n, self.Hq, self.Hkv, float(self.scale), _stream())
+                _lib.check(rc, "rgn_lm_attention_bf16")
+                ops.gemm(a, p["wo"], None, h, epilogue=ops.EPI_GATE_RESID, gate=self.ones, resid=h)
+                self._rms(h, p["ln2"], nn)
+                ops.gemm(nn, p["wgu"], None, ff)
+                _lib.check(lib.rgn_swiglu_bf16(_p(ff), ff.stride(0), _p(g), g.stride(0), n, self.F, _stream()), "rgn_swiglu_bf16")
+                ops.gemm(g, p["wdown"], None, h, epilogue=ops.EPI_GATE_RESID, gate=self.ones, resid=h)
+            self._rms(h, self.final_ln, out[bi, :n])
+        res = QwenTextEncoderOutput(out, bool(output_hidden_states))
+        return res if return_dict else res.to_tuple()
+
+    def _rms(self, x, w, out):
+        rc = _lib.lib().rgn_rms_norm_rows(_p(x), x.stride(0), _p(w), _p(out), out.stride(0), x.shape[0], self.d, self.eps, _stream())
+        _lib.check(rc, "rgn_rms_norm_rows")
