@@ -10,10 +10,11 @@
 //   gn_apply_kernel                         y = (x - mean) * rstd * gamma + beta, optional SiLU, border rows -> 0
 //   upsample2x_kernel                       nearest-neighbour 2 x upsample into the next level's padded image
 //   softmax_rows_kernel                     mid-block attention: P = softmax(scale * S) per row over the valid (non-border) key columns
-//   vae_attention_kernel                    mid-block attention fused (flash-style, no S in memory): O = softmax(scale Q K^T) V + b_v
+//   vae_attention_kernel                    mid-block attention fused (flash-style, no S in memory, the tile core of attn_tile.h):
+//                                           O = softmax(scale Q K^T) V + b_v
 //   rms_norm_kernel                         channel RMS-norm (+ SiLU) per pixel: the Qwen-Image (Wan-2.1) VAE's RMS_norm
 //   nchw_to_padded_kernel / padded_to_nchw_kernel   the host tensor layouts on either side of the decoder
-#include "common.h"
+#include "attn_tile.h"
 
 namespace rgn {
 
@@ -195,130 +196,64 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(uint16_t* __restrict_
 
 // ---- fused mid-block attention: one head of width C over the valid pixels, no score matrix in memory ---------------------------------
 // Queries and keys are enumerated over the H x W VALID pixels (i -> padded row (i / W + 1) * Wp + i % W + 1): border pixels are never keys,
-// and border query rows are not written.  Block = 4 waves x 16 queries; key tiles of 32 keys are staged in LDS (K pixel-major with a
-// padded row stride, V transposed to [C][keys]) and shared by the four waves.  Per wave and tile (v_mfma_f32_16x16x32_bf16):
-//   S^T [32 keys x 16 queries] = K Q^T   C / 32 k-steps x 2 key blocks, Q^T held in registers for the whole key loop
-//   online softmax in fp32 (exp2, scale * log2 e folded in), P rounded to bf16 in the registers the next MFMA reads as its B operand
-//   O^T [C x 16 queries] += V^T P^T      C / 16 channel blocks, one MFMA each: key slot 8 g + e of lane group g = key 4 g + e (e < 4),
-//                                        16 + 4 g + e - 4 (e >= 4) - the S^T output layout, so P needs no shuffle
-// The running max / sum and every reduction have a fixed order: a repeated call is bit-identical.
-constexpr int VA_BQ = 64, VA_BK = 32;
+// and border query rows are not written.  Block = 4 waves x 16 queries on the tile core of attn_tile.h (D = C), whose staging reads each
+// key's padded row from a table in LDS, written one tile ahead.  The scores stay raw (scale * log2 e is folded into the exp2 multiplier);
+// only the last tile masks (keys past the last pixel).  The epilogue adds b_v.
 template <int C> struct VaShape {
-    static constexpr int KLD = C + 8;                  // K row stride in LDS (u16): 16-byte aligned rows, 4 banks apart
-    static constexpr int VLD = VA_BK + 4;              // V^T row stride in LDS (u16): 8-byte aligned
-    static constexpr size_t lds = (size_t)VA_BK * KLD * 2 + (size_t)C * VLD * 2 + 2 * VA_BK * sizeof(long long);
+    static constexpr size_t lds = (size_t)(AttnTile<C>::K_LDS + AttnTile<C>::V_LDS) * 2 + 2 * ATTN_BK * sizeof(long long);
 };
 
 template <int C>
 __global__ __launch_bounds__(256, 2) void vae_attention_kernel(const uint16_t* Q, const uint16_t* __restrict__ K, const uint16_t* __restrict__ V,
                                                                  const uint16_t* __restrict__ bv, uint16_t* O, int H, int W, float sl2e) {
-    constexpr int KLD = VaShape<C>::KLD, VLD = VaShape<C>::VLD, KS = C / 32, CT = C / 16, VPR = C / 8;
+    using T = AttnTile<C>;
+    constexpr int BK = T::BK;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint16_t* kl = (uint16_t*)smem;
-    uint16_t* vl = kl + VA_BK * KLD;
-    long long* krow = (long long*)(vl + C * VLD);      // [2][VA_BK] padded row of each key of a tile (-1: past the last key)
+    uint16_t* vl = kl + T::K_LDS;
+    long long* krow = (long long*)(vl + T::V_LDS);     // [2][BK] padded row of each key of a tile (-1: past the last key)
     const int n = H * W, Wp = W + 2, tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
-    const int qi = blockIdx.x * VA_BQ + (tid >> 6) * 16 + li;
+    const int qi = blockIdx.x * T::BQ + (tid >> 6) * 16 + li;
     const bool qok = qi < n;
     const int qc = qok ? qi : n - 1;
     const size_t qrow = (size_t)(qc / W + 1) * Wp + qc % W + 1;
-    bf16x8 qf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const bf16x8*)(Q + qrow * C + ks * 32 + g * 8);
-    f32x4 o[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) o[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run = -INFINITY, l_run = 0.f;
-    const int ntiles = (n + VA_BK - 1) / VA_BK;
-    if (tid < VA_BK) krow[tid] = tid < n ? (long long)(tid / W + 1) * Wp + tid % W + 1 : -1;
+    T tile;
+    tile.init(Q + qrow * C, g);
+    const int ntiles = (n + BK - 1) / BK;
+    if (tid < BK) krow[tid] = tid < n ? (long long)(tid / W + 1) * Wp + tid % W + 1 : -1;
     for (int t = 0; t < ntiles; ++t) {
-        const int k0 = t * VA_BK;
-        const long long* kr = krow + (t & 1) * VA_BK;
+        const int k0 = t * BK;
+        const long long* kr = krow + (t & 1) * BK;
         __syncthreads();                               // the previous tile is consumed; this tile's key rows are visible
-        for (int i = tid; i < VA_BK * VPR; i += 256) {
-            const int kk = i / VPR, v = i - kk * VPR;
-            const long long r = kr[kk];
-            uint4 w = make_uint4(0u, 0u, 0u, 0u);
-            if (r >= 0) w = *(const uint4*)(K + (size_t)r * C + v * 8);
-            *(uint4*)(kl + kk * KLD + v * 8) = w;
-        }
-        for (int i = tid; i < (VA_BK / 2) * VPR; i += 256) {
-            const int kp = i / VPR, v = i - kp * VPR;
-            const long long r0 = kr[2 * kp], r1 = kr[2 * kp + 1];
-            uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;   // keys past the last one: V = 0 (P = 0 there; 0 x garbage could be NaN)
-            if (r0 >= 0) a = *(const uint4*)(V + (size_t)r0 * C + v * 8);
-            if (r1 >= 0) b = *(const uint4*)(V + (size_t)r1 * C + v * 8);
-            const uint32_t as[4] = {a.x, a.y, a.z, a.w}, bs[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const uint32_t lo = (e & 1) ? as[e >> 1] >> 16 : as[e >> 1] & 0xffffu;
-                const uint32_t hi = (e & 1) ? bs[e >> 1] & 0xffff0000u : bs[e >> 1] << 16;
-                *(uint32_t*)(vl + (v * 8 + e) * VLD + 2 * kp) = lo | hi;
-            }
-        }
-        if (tid < VA_BK) {                             // the next tile's key rows (the other half of the table)
-            const int j = k0 + VA_BK + tid;
-            krow[((t + 1) & 1) * VA_BK + tid] = j < n ? (long long)(j / W + 1) * Wp + j % W + 1 : -1;
+        T::stage(kl, vl, K, V, (size_t)C, tid, [&](int kk) { return kr[kk]; });
+        if (tid < BK) {                                // the next tile's key rows (the other half of the table)
+            const int j = k0 + BK + tid;
+            krow[((t + 1) & 1) * BK + tid] = j < n ? (long long)(j / W + 1) * Wp + j % W + 1 : -1;
         }
         __syncthreads();
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
+        tile.step(kl, vl, li, g, sl2e, [&](const float (&s)[8], float (&sc)[8]) {     // every tile holds at least one key
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const bf16x8 k0f = *(const bf16x8*)(kl + li * KLD + ks * 32 + g * 8);
-            const bf16x8 k1f = *(const bf16x8*)(kl + (16 + li) * KLD + ks * 32 + g * 8);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0f, qf[ks], s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1f, qf[ks], s1, 0, 0, 0);
-        }
-        if (k0 + VA_BK > n) {                          // last tile only
+            for (int e = 0; e < 8; ++e) sc[e] = s[e];
+            if (k0 + BK > n) {                         // last tile only
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (k0 + 4 * g + r >= n) s0[r] = -INFINITY;
-                if (k0 + 16 + 4 * g + r >= n) s1[r] = -INFINITY;
+                for (int e = 0; e < 8; ++e)
+                    if (k0 + T::key_of_slot(g, e) >= n) sc[e] = -INFINITY;
             }
-        }
-        float mx = fmaxf(fmaxf(fmaxf(s0[0], s0[1]), fmaxf(s0[2], s0[3])), fmaxf(fmaxf(s1[0], s1[1]), fmaxf(s1[2], s1[3])));
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);          // finite: every tile holds at least one key
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * sl2e);
-        const float nb = -m_new * sl2e;
-        uint32_t pw[4];
-        pw[0] = f2bf_pk(__builtin_amdgcn_exp2f(__builtin_fmaf(s0[0], sl2e, nb)), __builtin_amdgcn_exp2f(__builtin_fmaf(s0[1], sl2e, nb)));
-        pw[1] = f2bf_pk(__builtin_amdgcn_exp2f(__builtin_fmaf(s0[2], sl2e, nb)), __builtin_amdgcn_exp2f(__builtin_fmaf(s0[3], sl2e, nb)));
-        pw[2] = f2bf_pk(__builtin_amdgcn_exp2f(__builtin_fmaf(s1[0], sl2e, nb)), __builtin_amdgcn_exp2f(__builtin_fmaf(s1[1], sl2e, nb)));
-        pw[3] = f2bf_pk(__builtin_amdgcn_exp2f(__builtin_fmaf(s1[2], sl2e, nb)), __builtin_amdgcn_exp2f(__builtin_fmaf(s1[3], sl2e, nb)));
-        // the row sum is taken over the bf16 P the MFMA multiplies, so the weights the output is divided by are the ones it used
-        const float ps = ((lo_bf(pw[0]) + hi_bf(pw[0])) + (lo_bf(pw[1]) + hi_bf(pw[1]))) + ((lo_bf(pw[2]) + hi_bf(pw[2])) + (lo_bf(pw[3]) + hi_bf(pw[3])));
-        l_run = __builtin_fmaf(l_run, alpha, ps);
-        m_run = m_new;
-        if (__any(alpha != 1.0f)) {                    // the max moved for some query of the wave (x 1 is exact: skipping it changes nothing)
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) o[ct] *= alpha;
-        }
-        const bf16x8 pf = __builtin_bit_cast(bf16x8, make_uint4(pw[0], pw[1], pw[2], pw[3]));
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            const uint16_t* vr = vl + (ct * 16 + li) * VLD + 4 * g;
-            const uint2 va = *(const uint2*)vr, vb = *(const uint2*)(vr + 16);
-            const bf16x8 vf = __builtin_bit_cast(bf16x8, make_uint4(va.x, va.y, vb.x, vb.y));
-            o[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[ct], 0, 0, 0);
-        }
+        });
     }
-    float l = l_run;
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
+    const float l = tile.row_sum();
     if (!qok) return;
     const float inv = 1.0f / l;
     uint16_t* orow = O + qrow * C + 4 * g;
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
+    for (int ct = 0; ct < T::CT; ++ct) {
         float b[4] = {0.f, 0.f, 0.f, 0.f};
         if (bv) {
             const uint2 bw = *(const uint2*)(bv + ct * 16 + 4 * g);
             b[0] = lo_bf(bw.x); b[1] = hi_bf(bw.x); b[2] = lo_bf(bw.y); b[3] = hi_bf(bw.y);
         }
-        *(uint2*)(orow + ct * 16) = make_uint2(f2bf_pk(__builtin_fmaf(o[ct][0], inv, b[0]), __builtin_fmaf(o[ct][1], inv, b[1])),
-                                               f2bf_pk(__builtin_fmaf(o[ct][2], inv, b[2]), __builtin_fmaf(o[ct][3], inv, b[3])));
+        *(uint2*)(orow + ct * 16) = make_uint2(f2bf_pk(__builtin_fmaf(tile.o[ct][0], inv, b[0]), __builtin_fmaf(tile.o[ct][1], inv, b[1])),
+                                               f2bf_pk(__builtin_fmaf(tile.o[ct][2], inv, b[2]), __builtin_fmaf(tile.o[ct][3], inv, b[3])));
     }
 }
 
@@ -412,7 +347,7 @@ int launch_vae_attention(const void* Q, const void* K, const void* V, const void
         (void)hipFuncSetAttribute((const void*)vae_attention_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)VaShape<C>::lds);
         attr = true;
     }
-    const int blocks = (int)(((long long)H * W + VA_BQ - 1) / VA_BQ);
+    const int blocks = (int)(((long long)H * W + ATTN_BQ - 1) / ATTN_BQ);
     hipLaunchKernelGGL(vae_attention_kernel<C>, dim3(blocks), dim3(256), VaShape<C>::lds, st, (const uint16_t*)Q, (const uint16_t*)K,
                        (const uint16_t*)V, (const uint16_t*)b_v, (uint16_t*)O, H, W, scale * 1.4426950408889634f);
     return check_launch("vae_attention_kernel");
@@ -480,7 +415,7 @@ int rgn_vae_attention_bf16(const void* Q, const void* K, const void* V, const vo
     if (C != 384 && C != 512) return fail(RGN_E_UNSUPPORTED, "vae_attention: C must be 384 or 512");
     if ((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O) & 15) != 0 || ((uintptr_t)b_v & 7) != 0)
         return fail(RGN_E_UNSUPPORTED, "vae_attention: Q, K, V, O must be 16-byte aligned, b_v 8-byte aligned");
-    if ((long long)(Hp - 2) * (Wp - 2) >= (1ll << 31) - VA_BQ) return fail(RGN_E_UNSUPPORTED, "vae_attention: image too large");
+    if ((long long)(Hp - 2) * (Wp - 2) >= (1ll << 31) - ATTN_BQ) return fail(RGN_E_UNSUPPORTED, "vae_attention: image too large");
     hipStream_t st = (hipStream_t)stream;
     return C == 512 ? launch_vae_attention<512>(Q, K, V, b_v, O, Hp - 2, Wp - 2, scale, st)
                     : launch_vae_attention<384>(Q, K, V, b_v, O, Hp - 2, Wp - 2, scale, st);

@@ -29,7 +29,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib, ops
-from .text_encoders import _Buffers, _bf16_only, _check_k, _check_names, _refuse, _source
+from .text_encoders import _Buffers, _HipTextEncoder, _bf16_only, _check_k, _check_names, _refuse, _source
 
 _p, _stream = ops._p, ops._stream
 
@@ -154,7 +154,7 @@ def image_rows(input_ids: torch.Tensor, lengths, image_token_id: int, n_embeds: 
     return rows
 
 
-class HipQwen25VLTextEncoder:
+class HipQwen25VLTextEncoder(_HipTextEncoder):
     """`Qwen2_5_VLForConditionalGeneration(input_ids, attention_mask, pixel_values, image_grid_thw, output_hidden_states=True)` with the
     language model on the HIP kernels.  Returns an object with `.last_hidden_state` [B, L, d] bf16 and `.hidden_states`, a ONE-element
     tuple whose `[-1]` is that final hidden state after the final norm - the earlier entries transformers returns (embeddings, per-layer
@@ -201,10 +201,6 @@ class HipQwen25VLTextEncoder:
         self.inv_freq = rot.inv_freq.detach().float().cpu() if rot is not None else default_inv_freq(cfg)
         self.ones = torch.ones(self.d, dtype=torch.bfloat16, device=dev)
         self.buf = _Buffers(dev)
-
-    @property
-    def dtype(self):
-        return torch.bfloat16
 
     # ---- host-side preparation (no kernel) -----------------------------------------------------------------------------------------
     def position_ids_for(self, input_ids, attention_mask=None, image_grid_thw=None, position_ids=None, mm_token_type_ids=None):
@@ -297,8 +293,7 @@ class HipQwen25VLTextEncoder:
         for bi, n in enumerate(lengths):
             h, nn, qkv, a, ff, g = (t[k][:n] for k in ("h", "n", "qkv", "a", "ff", "g"))
             cos, sin = tab[0, bi], tab[1, bi]
-            rc = lib.rgn_text_embed(_p(ids[bi]), n, _p(self.tok), self.tok.shape[0], None, 0, _p(h), self.d, _stream())
-            _lib.check(rc, "rgn_text_embed")
+            self._embed(ids[bi, :n], h)
             if rows is not None and rows[bi].numel():
                 k = rows[bi].numel()
                 rc = lib.rgn_scatter_rows(_p(emb[at:at + k]), _p(idx[at:at + k]), _p(h), k, self.d * 2, _stream())
@@ -319,7 +314,3 @@ class HipQwen25VLTextEncoder:
             self._rms(h, self.final_ln, out[bi, :n])
         res = QwenTextEncoderOutput(out, bool(output_hidden_states))
         return res if return_dict else res.to_tuple()
-
-    def _rms(self, x, w, out):
-        rc = _lib.lib().rgn_rms_norm_rows(_p(x), x.stride(0), _p(w), _p(out), out.stride(0), x.shape[0], self.d, self.eps, _stream())
-        _lib.check(rc, "rgn_rms_norm_rows")

@@ -136,6 +136,10 @@ class _HipTextEncoder:
                                        _p(out), self.d, _stream())
         _lib.check(rc, "rgn_text_embed")
 
+    def _rms(self, x, w, out):
+        rc = _lib.lib().rgn_rms_norm_rows(_p(x), x.stride(0), _p(w), _p(out), out.stride(0), x.shape[0], self.d, self.eps, _stream())
+        _lib.check(rc, "rgn_rms_norm_rows")
+
     def _attention(self, qkv, out, L, scale, causal, bias=None):
         rc = _lib.lib().rgn_text_attention_bf16(_p(qkv), _p(out), L, self.H, float(scale), int(causal), _p(bias), self.max_length, _stream())
         _lib.check(rc, "rgn_text_attention_bf16")
@@ -240,10 +244,6 @@ class HipT5EncoderModel(_HipTextEncoder):
                                         attention=attn0).to(dev, torch.bfloat16).contiguous()
         self.ones = torch.ones(self.d, dtype=torch.bfloat16, device=dev)
         self.buf = _Buffers(dev)
-
-    def _rms(self, x, w, out):
-        rc = _lib.lib().rgn_rms_norm_rows(_p(x), x.stride(0), _p(w), _p(out), out.stride(0), x.shape[0], self.d, self.eps, _stream())
-        _lib.check(rc, "rgn_rms_norm_rows")
 
     @torch.no_grad()
     def __call__(self, input_ids, attention_mask=None, output_hidden_states=False, return_dict=True, **kw):

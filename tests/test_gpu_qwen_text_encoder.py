@@ -248,7 +248,7 @@ def test_a_warm_text_only_call_dispatches_only_libregione_hip_kernels():
     names = [e.name for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")]
     foreign = sorted({n[:120] for n in names if not (("rgn::" in n) or n.startswith("__amd_rocclr_") or n.lower().startswith(("memcpy", "memset")))})
     assert foreign == [], foreign
-    assert any("lm_attention_kernel" in n for n in names) and any("gemm" in n for n in names)
+    assert any("text_attention_kernel" in n for n in names) and any("gemm" in n for n in names)
     assert any("mrope_kernel" in n for n in names) and any("swiglu_kernel" in n for n in names)
     assert torch.isfinite(a.hidden_states[-1].float()).all()
 
