@@ -511,6 +511,105 @@ __global__ __launch_bounds__(512, 1) void attention_asm_kernel(const AttnArgs g)
   }
 }
 
+// One wave per SIMD: 4 waves x 64 query rows (two 32-row q-blocks per wave) around RGN_ATTN_LOOP_W64_ASM.  Same item (256 rows of one head),
+// item map, AttnArgs, LDS images and epilogue as attention_asm_kernel<0, true>, and per output row the same arithmetic in the same order:
+// the two kernels write the same bits.  Every K / V^T fragment read feeds the MFMAs of both q-blocks.  Unsplit static-shift launches only.
+__global__ __launch_bounds__(256, 1) void attention_asm64_kernel(const AttnArgs g) {
+    constexpr int QB = 256;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nQ = (g.Sq + QB - 1) / QB;
+    const int ntiles = g.Skv / KV_T;
+    int unit;
+    {
+        const int nb = g.nitems_launch;
+        const int bid = blockIdx.x, xcd = bid & 7, loc = bid >> 3;
+        const int q = nb >> 3, r = nb & 7;
+        unit = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    }
+    const uint32_t HD2 = (uint32_t)g.H * 256u;                 // bytes of one K row (H * 128 bf16)
+    const int lane = tid & 63;
+    const int ql = lane & 31, half = lane >> 5;
+    const int item = g.item_offset + unit;
+    const int h = item / nQ, qb = item - h * nQ;
+    const int q0 = qb * QB + wave * 64;
+    float m_run = g.static_m, l_run0 = 0.f, l_run1 = 0.f;
+    {
+        uint32_t krel[8], vrel[4];
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) krel[ks] = ql * 256 + (((ks * 2 + half) ^ (ql & 15)) << 4);
+#pragma unroll
+        for (int kb4 = 0; kb4 < 4; ++kb4) vrel[kb4] = ql * 128 + (((kb4 * 2 + half) ^ ((ql >> 1) & 7)) << 4);
+        // per-lane source offsets of this wave's 4 + 4 DMA pieces (bytes from the slab bases): pieces 4 wave .. 4 wave + 3 of the 16
+        uint32_t dk[4], dv[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int piece = wave * 4 + p;
+            const int krow = piece * 4 + (lane >> 4);
+            dk[p] = (uint32_t)krow * HD2 + h * 256 + (((lane & 15) ^ (krow & 15)) << 4);
+            const int vrow = piece * 8 + (lane >> 3);
+            dv[p] = (uint32_t)(h * 128 + vrow) * (uint32_t)(g.skv_pad * 2) + (((lane & 7) ^ ((vrow >> 1) & 7)) << 4);
+        }
+        const uint16_t* qptr0 = g.Q + (size_t)min(q0 + ql, g.Sq - 1) * g.ldq + h * 128 + half * 8;
+        const uint16_t* qptr1 = g.Q + (size_t)min(q0 + 32 + ql, g.Sq - 1) * g.ldq + h * 128 + half * 8;
+        auto rsrc = [](const void* p) {
+            const uint64_t a = (uint64_t)p;
+            u32x4_s r;
+            r[0] = __builtin_amdgcn_readfirstlane((uint32_t)a);
+            r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32) & 0xffffu);
+            r[2] = 0xffffffffu;
+            r[3] = 0x00020000u;
+            return r;
+        };
+        const u32x4_s rk = rsrc(g.K), rv = rsrc(g.Vt);
+        const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)smem;    // 0: no static LDS
+        const uint32_t kadv = __builtin_amdgcn_readfirstlane((uint32_t)KV_T * HD2);
+        uint32_t tk = __builtin_amdgcn_readfirstlane(0u), tv = __builtin_amdgcn_readfirstlane(0u);
+        const uint32_t tk_last = __builtin_amdgcn_readfirstlane((uint32_t)(ntiles - 1) * kadv);
+        const uint32_t tv_last = __builtin_amdgcn_readfirstlane((uint32_t)(ntiles - 1) * 128u);
+        uint32_t stg_k = __builtin_amdgcn_readfirstlane(lds0 + 32768u), stg_v = __builtin_amdgcn_readfirstlane(lds0), stg_d = stg_v;
+        const uint32_t wdst = __builtin_amdgcn_readfirstlane((uint32_t)wave * 4096u);
+        uint32_t cnt = __builtin_amdgcn_readfirstlane((uint32_t)(ntiles - 1) >> 1), rem = __builtin_amdgcn_readfirstlane((uint32_t)(ntiles - 1) & 1u);
+        const float sl2e = g.scale_log2e;
+        uint32_t stmp, stmp2, sdst;
+        asm volatile(RGN_ATTN_LOOP_W64_ASM
+                     : [l_run0] "+&v"(l_run0), [l_run1] "+&v"(l_run1), [tk] "+&s"(tk), [tv] "+&s"(tv), [stg_k] "+&s"(stg_k),
+                       [stg_v] "+&s"(stg_v), [stg_d] "+&s"(stg_d), [cnt] "+&s"(cnt), [stmp] "=&s"(stmp), [stmp2] "=&s"(stmp2),
+                       [sdst] "=&s"(sdst)
+                     : [krel0] "v"(krel[0]), [krel1] "v"(krel[1]), [krel2] "v"(krel[2]), [krel3] "v"(krel[3]), [krel4] "v"(krel[4]),
+                       [krel5] "v"(krel[5]), [krel6] "v"(krel[6]), [krel7] "v"(krel[7]), [vrel0] "v"(vrel[0]), [vrel1] "v"(vrel[1]),
+                       [vrel2] "v"(vrel[2]), [vrel3] "v"(vrel[3]), [dk0] "v"(dk[0]), [dk1] "v"(dk[1]), [dk2] "v"(dk[2]), [dk3] "v"(dk[3]),
+                       [dv0] "v"(dv[0]), [dv1] "v"(dv[1]), [dv2] "v"(dv[2]), [dv3] "v"(dv[3]), [qptr0] "v"(qptr0), [qptr1] "v"(qptr1),
+                       [m_run] "v"(m_run), [rk] "s"(rk), [rv] "s"(rv), [kadv] "s"(kadv), [tk_last] "s"(tk_last), [tv_last] "s"(tv_last),
+                       [wdst] "s"(wdst), [rem] "s"(rem), [sl2e] "s"(sl2e)
+                     : RGN_ATTN_LOOP_W64_CLOBBERS);
+    }
+    // O^T accumulators: q-block j in a[64 j + db * 16 + r]
+    const float inv0 = 1.0f / (l_run0 + __shfl_xor(l_run0, 32, 64));
+    const float inv1 = 1.0f / (l_run1 + __shfl_xor(l_run1, 32, 64));
+    constexpr int OT_LD = 136;
+    uint16_t* ot = (uint16_t*)smem;                      // 256 rows x 136 bf16 = 68 KiB: fits, one pass
+    static_for<32>([&](auto Ic) {
+        constexpr int I = decltype(Ic)::value;           // I = j * 16 + db * 4 + r4
+        constexpr int j = I / 16, db = (I / 4) % 4, r4 = I % 4, A = j * 64 + db * 16 + r4 * 4;
+        const float inv = j ? inv1 : inv0;
+        uint16_t* orow = ot + ((wave * 2 + j) * 32 + ql) * OT_LD;
+        const int d = db * 32 + 8 * r4 + 4 * half;
+        const uint32_t w0 = cvt_pk_bf16(agpr_read1<A + 0>() * inv, agpr_read1<A + 1>() * inv);
+        const uint32_t w1 = cvt_pk_bf16(agpr_read1<A + 2>() * inv, agpr_read1<A + 3>() * inv);
+        *(uint2*)(orow + d) = make_uint2(w0, w1);
+    });
+    __syncthreads();
+    constexpr int RPP = 256 / 16;
+#pragma unroll
+    for (int it = 0; it < QB / RPP; ++it) {
+        const int row = (tid >> 4) + it * RPP, c = (tid & 15) * 8;
+        const int qr2 = qb * QB + row;
+        if (qr2 < g.Sq) *(uint4*)(g.O + (size_t)qr2 * g.ldo + h * 128 + c) = *(const uint4*)(ot + row * OT_LD + c);
+    }
+}
+
 // Merge the nsplit partial results of each split item: O = sum_s O_s 2^(m_s - m*) / sum_s l_s 2^(m_s - m*).
 template <int QB>
 __global__ __launch_bounds__(256) void attention_combine_kernel(const AttnArgs g) {
@@ -596,10 +695,13 @@ static int launch_attention_asm(const AttnArgs& g, int nblocks, hipStream_t st) 
     if (dev < 0 || dev >= 64 || !attr[dev]) {
         (void)hipFuncSetAttribute((const void*)attention_asm_kernel<SPLIT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         (void)hipFuncSetAttribute((const void*)attention_asm_kernel<SPLIT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        if (SPLIT == 0) (void)hipFuncSetAttribute((const void*)attention_asm64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         if (dev >= 0 && dev < 64) attr[dev] = true;
     }
     if (nblocks == 0) return 0;
-    if (g.static_on) hipLaunchKernelGGL((attention_asm_kernel<SPLIT, true>), dim3(nblocks), dim3(512), LDS, st, g);
+    // unsplit static-shift launches (whole rounds and unsplit remainders): one wave per SIMD, 64 query rows per wave - the same bits
+    if (SPLIT == 0 && g.static_on) hipLaunchKernelGGL(attention_asm64_kernel, dim3(nblocks), dim3(256), LDS, st, g);
+    else if (g.static_on) hipLaunchKernelGGL((attention_asm_kernel<SPLIT, true>), dim3(nblocks), dim3(512), LDS, st, g);
     else hipLaunchKernelGGL((attention_asm_kernel<SPLIT, false>), dim3(nblocks), dim3(512), LDS, st, g);
     return check_launch("attention_asm_kernel");
 }

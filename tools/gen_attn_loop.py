@@ -29,6 +29,7 @@ Registers (per wave; 2 waves per SIMD -> 256 in total):
 Named operands: see attn.hip (attention_asm_kernel).
 """
 import os
+import re
 
 S_BASE = (32, 64)
 PF, FR, TMP = 96, 112, 144
@@ -487,6 +488,395 @@ def emit():
     return st.ins
 
 
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Second loop (RGN_ATTN_LOOP_W64_ASM): 4 waves, ONE per SIMD, each owning 64 query rows as two 32-row q-blocks j = 0, 1 of the same
+# 256-row item.  Static-shift softmax only.  Same MFMA, same swapped products, same 64-key tile, same five-stage ring, same swizzles as
+# the loop above - and per output row the same arithmetic in the same order (MFMA k order, fma / exp2 / RNE packing of P, the four-chain
+# row sum, tile order), so the results are bit-identical.  What changes: every K / V^T fragment is read from LDS ONCE and feeds the MFMAs
+# of both q-blocks (32 ds_read_b128 per tile for 64 MFMAs instead of 32 for 32), and the one wave of a SIMD has the VALU to itself.
+#
+#     X(t):  32 MFMA  S(t+1)[j] = K(t+1) Q[j]^T       ||  E2(t): exp2 of the s1 halves of S(t), all 32 bf16 packings of P(t); 8 DMA pieces
+#     Y(t):  32 MFMA  O[j] += V^T(t) P(t)[j]^T        ||  R(t): row sums of P(t);  E1(t+1): exp2 of the s0 halves of S(t+1)
+#
+# so every MFMA gap carries about one v_exp_f32 and two or three plain VALU instructions (weights 5/3 and 1 when spacing), one ds_read
+# every second gap, and no phase opens with a VALU block.  Registers (512 per wave):
+#     a[0:127]    O^T, q-block j at 64 j (4 d-blocks x 16)      a[128:191]  Q fragments, q-block j at 128 + 32 j (8 k-steps x 4)
+#     v[32:95]    S set 0 (q-block j at 32 + 32 j)               v[96:159]   S set 1
+#     v[160:191]  pf: P packed to bf16, q-block j at 160 + 16 j  v[192:223]  fragment window, 8 slots x 4
+#     v[224:239]  temporaries                                    v[0:31]     operands (compiler-allocated)
+# ------------------------------------------------------------------------------------------------------------------------------------
+W_S = ((32, 64), (96, 128))                        # [set][q-block]
+W_PF = (160, 176)
+W_FR, W_NEGM, W_KA, W_VA = 192, 224, 225, 226
+W_ACC = ((228, 229, 230, 231), (232, 233, 234, 235))
+W_O, W_Q = (0, 64), (128, 160)
+W_NV, W_NA = 240, 192                              # registers the statement owns: v32..v239, a0..a191
+W_D = 4                                            # fragment prefetch distance (fragments; two MFMAs each)
+W_DMA_AT = (1, 5, 9, 13, 17, 21, 25, 29)           # MFMA index of X behind which each of the wave's 8 LDS-DMA pieces is issued
+W_MFMA_TO_VALU = 3                                 # a VALU instruction touches an MFMA result only behind this many later MFMAs
+
+
+def wslot(i):
+    return v(W_FR + 4 * (i % 8), 4)
+
+
+def w_k_read(st, f):
+    ks, b = divmod(f, 2)
+    if b == 0:
+        st.emit(f"v_add_u32 {v(W_KA)}, %[stg_k], %[krel{ks}]")
+    st.read(("K", f), wslot(f), v(W_KA), b * 8192)
+
+
+def w_v_read(st, g):
+    kb4, db = divmod(g, 4)
+    if db == 0:
+        st.emit(f"v_add_u32 {v(W_VA)}, %[stg_v], %[vrel{kb4}]")
+    st.read(("V", g), wslot(g), v(W_VA), K_TILE + db * 4096)
+
+
+def w_qk_mfma(st, f, q, j):
+    ks, b = divmod(f, 2)
+    d = v(W_S[q][j] + 16 * b, 16)
+    st.need(("K", f))
+    st.emit(f"v_mfma_f32_32x32x16_bf16 {d}, {wslot(f)}, {a(W_Q[j] + 4 * ks, 4)}, {'0' if ks == 0 else d}")
+
+
+def w_pv_mfma(st, g, j):
+    kb4, db = divmod(g, 4)
+    st.need(("V", g))
+    st.emit(f"v_mfma_f32_32x32x16_bf16 {a(W_O[j] + 16 * db, 16)}, {wslot(g)}, {v(W_PF[j] + 4 * kb4, 4)}, {a(W_O[j] + 16 * db, 16)}")
+
+
+def w_fma(p, j, i):
+    return f"v_fma_f32 {v(W_S[p][j] + i)}, {v(W_S[p][j] + i)}, %[sl2e], {v(W_NEGM)}"
+
+
+def w_exp(p, j, i):
+    return f"v_exp_f32 {v(W_S[p][j] + i)}, {v(W_S[p][j] + i)}"
+
+
+def w_cvt(p, j, k):
+    return f"v_cvt_pk_bf16_f32 {v(W_PF[j] + k)}, {v(W_S[p][j] + 2 * k)}, {v(W_S[p][j] + 2 * k + 1)}"
+
+
+def w_e1_ops(p):
+    """E1 on S set p: scale-and-shift and exp2 of the s0 halves (registers 0..15: the P operands of PV k-blocks 0, 1) of both q-blocks;
+    a fma runs eight elements ahead of its exp"""
+    el = [(j, i) for i in range(16) for j in range(2)]
+    ops = [w_fma(p, j, i) for j, i in el[:8]]
+    for n, (j, i) in enumerate(el):
+        ops.append(w_exp(p, j, i))
+        if n + 8 < len(el):
+            ops.append(w_fma(p, *el[n + 8]))
+    return ops
+
+
+def w_e2_ops(p):
+    """E2 on S set p: the s1 halves (registers 16..31) of both q-blocks, and every packing: those of the s0 halves (exp'd by E1 in the
+    previous Y) first - PV starts with them - then each s1 pair ten or more exps behind its second element"""
+    el = [(j, i) for i in range(16, 32) for j in range(2)]
+    early = [(j, k) for k in range(8) for j in range(2)]
+    ops = [w_fma(p, j, i) for j, i in el[:8]]
+    for n in range(len(el) + 12):
+        if n < len(el):
+            ops.append(w_exp(p, *el[n]))
+        if n + 8 < len(el):
+            ops.append(w_fma(p, *el[n + 8]))
+        if n % 2 == 1 and early:
+            ops.append(w_cvt(p, *early.pop(0)))
+        m = n - 10
+        if 0 <= m < len(el) and el[m][1] % 2 == 1:
+            ops.append(w_cvt(p, el[m][0], el[m][1] // 2))
+    assert not early and sum(o.startswith("v_cvt") for o in ops) == 32 and sum(o.startswith("v_exp") for o in ops) == 32
+    return ops
+
+
+def w_rowsum_ops(p):
+    """row sums of P (S set p), each q-block with the four chains and the final order of rowsum_ops_scalar; the two q-blocks alternate"""
+    per = []
+    for j in range(2):
+        b, acc = W_S[p][j], W_ACC[j]
+        ops = [f"v_mov_b32 {v(acc[i])}, {v(b + i)}" for i in range(4)]
+        ops += [f"v_add_f32 {v(acc[i % 4])}, {v(acc[i % 4])}, {v(b + i)}" for i in range(4, 32)]
+        ops += [f"v_add_f32 {v(acc[0])}, {v(acc[0])}, {v(acc[1])}", f"v_add_f32 {v(acc[2])}, {v(acc[2])}, {v(acc[3])}",
+                f"v_add_f32 {v(acc[0])}, {v(acc[0])}, {v(acc[2])}", f"v_add_f32 %[l_run{j}], %[l_run{j}], {v(acc[0])}"]
+        per.append(ops)
+    return [o for pair in zip(*per) for o in pair]
+
+
+def w_weight(o):
+    return 5.0 / 3.0 if isinstance(o, str) and o.startswith("v_exp") else 1.0
+
+
+def w_spread(fillers, n_gaps, first=0, pre=None):
+    """fillers per gap so that every gap from `first` on carries about the same WEIGHT (v_exp_f32 5/3, anything else 1; `pre[i]` =
+    weight gap i carries already: its LDS-DMA piece)"""
+    pre = pre or [0.0] * n_gaps
+    total = sum(w_weight(o) for o in fillers) + sum(pre[first:])
+    avg = total / (n_gaps - first)
+    gaps, cum, fi = [0] * n_gaps, 0.0, 0
+    for g in range(first, n_gaps):
+        cum += pre[g]
+        target = avg * (g - first + 1)
+        while fi < len(fillers) and (g == n_gaps - 1 or cum + w_weight(fillers[fi]) / 2 <= target):
+            cum += w_weight(fillers[fi])
+            gaps[g] += 1
+            fi += 1
+    assert fi == len(fillers)
+    return gaps
+
+
+def w_merge(xs, ys):
+    """xs and ys interleaved evenly, each in its own order"""
+    out, i, j = [], 0, 0
+    while i < len(xs) or j < len(ys):
+        if j >= len(ys) or (i < len(xs) and i * len(ys) <= j * len(xs)):
+            out.append(xs[i]); i += 1
+        else:
+            out.append(ys[j]); j += 1
+    return out
+
+
+def w_dma_split():
+    def pro(st):
+        st.emit("s_min_u32 %[stmp], %[tk], %[tk_last]")
+        st.emit("s_min_u32 %[stmp2], %[tv], %[tv_last]")
+        st.emit("s_add_u32 %[sdst], %[stg_d], %[wdst]")
+
+    def piece(kind, p):                    # (set m0, issue): one instruction at least has to sit between the two
+        def m0(st):
+            st.emit(f"s_add_u32 m0, %[sdst], {(K_TILE if kind == 'v' else 0) + p * 1024}")
+
+        def load(st):
+            st.emit(f"buffer_load_dwordx4 %[d{kind}{p}], %[r{kind}], %[{'stmp2' if kind == 'v' else 'stmp'}] offen lds")
+        return m0, load
+
+    def epi(st):
+        st.emit("s_add_u32 %[tk], %[tk], %[kadv]")
+        st.emit("s_add_u32 %[tv], %[tv], 128")
+        advance(st, "stg_d")
+    return pro, [piece("k", p) for p in range(4)] + [piece("v", p) for p in range(4)], epi
+
+
+def w_dma_issue(st):
+    pro, pieces, epi = w_dma_split()
+    pro(st)
+    for m0, load in pieces:
+        m0(st)
+        st.emit("s_nop 0")
+        load(st)
+    epi(st)
+
+
+def w_phase_x(st, p, full, dma=None):
+    """X(t), S(t) in set p.  Entry: K fragments 0..D-1 of tile t+1 requested.  Exit: V^T fragments 0..D-1 of tile t requested.
+    Fragment f lives in slot f % 8 and is requested D fragments (2 D MFMAs) before its first use."""
+    q = 1 - p
+    vops = w_e2_ops(p)
+    if not full:
+        for o in vops:
+            st.emit(o)
+        for g in range(W_D):
+            w_v_read(st, g)
+        return
+    mf = []
+    for n in range(32):
+        def m(st, n=n):
+            f, j = divmod(n, 2)
+            if j == 0 and f + W_D < 16:
+                w_k_read(st, f + W_D)
+            if n in W_DMA_AT:                                # m0 in front of the MFMA: the MFMA is the wait state the DMA needs behind it
+                dma[0][W_DMA_AT.index(n)][0](st)
+            w_qk_mfma(st, f, q, j)
+            if j == 1 and f >= 8 and f - 8 < W_D:            # both users of slot f % 8 have issued: V^T prefetch for Y(t)
+                w_v_read(st, f - 8)
+            if n in W_DMA_AT:
+                dma[0][W_DMA_AT.index(n)][1](st)
+                if n == W_DMA_AT[-1]:
+                    dma[1](st)
+        mf.append(m)
+    pre = [2.0 if n in W_DMA_AT else 0.0 for n in range(32)]
+    interleave(st, mf, vops, w_spread(vops, 32, pre=pre))
+
+
+def w_phase_y(st, p, full):
+    """Y(t): PV MFMAs of tile t; row sums of P(t); with `full` E1 of S(t+1) (set 1-p, written by the last MFMAs of X(t): not before
+    MFMA W_MFMA_TO_VALU of this phase) and the first D K fragments of tile t+2."""
+    rs = w_rowsum_ops(p)
+    mf = []
+    for n in range(32):
+        def m(st, n=n):
+            g, j = divmod(n, 2)
+            if j == 0 and g + W_D < 16:
+                w_v_read(st, g + W_D)
+            w_pv_mfma(st, g, j)
+            if full and j == 1 and g >= 8 and g - 8 < W_D:
+                w_k_read(st, g - 8)
+        mf.append(m)
+    if full:
+        e1 = w_e1_ops(1 - p)
+        n0 = 4 * W_MFMA_TO_VALU + 2
+        fill = rs[:n0] + w_merge(rs[n0:], e1)
+        gaps = w_spread(rs[:n0], W_MFMA_TO_VALU + 1)
+        rest = w_spread(fill[n0:], 32, first=W_MFMA_TO_VALU + 1)
+        gaps = gaps + rest[W_MFMA_TO_VALU + 1:]
+    else:
+        fill, gaps = rs, w_spread(rs, 32)
+    interleave(st, mf, fill, gaps)
+
+
+def w_body(st, p, full):
+    dma = None
+    if full:
+        st.emit("s_waitcnt vmcnt(8)")                      # tile t+2 has landed (the 8 pieces of t+3 may be in flight)
+        st.emit("s_barrier")
+        pro, pieces, epi = w_dma_split()
+        pro(st)                                            # tile t+4 -> the stage of tile t-1, piece by piece inside X
+        dma = (pieces, epi)
+    w_phase_x(st, p, full, dma)
+    if full:
+        advance(st, "stg_k")
+    w_phase_y(st, p, full)
+    advance(st, "stg_v")
+
+
+def w_prologue(st):
+    for j in range(2):                                     # Q fragments -> S set 1 (free until X(0)), then into a[128:191]
+        for ks in range(8):
+            st.emit(f"global_load_dwordx4 {v(W_S[1][j] + 4 * ks, 4)}, %[qptr{j}], off offset:{ks * 32}")
+    for _ in range(4):
+        w_dma_issue(st)
+    for n in range(128):
+        st.emit(f"v_accvgpr_write_b32 {a(n)}, 0")
+    st.emit("s_waitcnt vmcnt(32)")                         # Q landed (the 32 DMA pieces may be in flight)
+    for j in range(2):
+        for k in range(32):
+            st.emit(f"v_accvgpr_write_b32 {a(W_Q[j] + k)}, {v(W_S[1][j] + k)}")
+    st.emit(f"v_sub_f32 {v(W_NEGM)}, 0, %[m_run]")
+    st.emit("s_waitcnt vmcnt(16)")                         # tiles 0, 1 landed
+    st.emit("s_barrier")
+    st.emit("s_mov_b32 %[stmp], %[stg_k]")                 # S(0) = K(0) Q^T into set 0 (stage 0: stg_v), not overlapped
+    st.emit("s_mov_b32 %[stg_k], %[stg_v]")
+    for f in range(W_D):
+        w_k_read(st, f)
+    for f in range(16):
+        if f + W_D < 16:
+            w_k_read(st, f + W_D)
+        for j in range(2):
+            w_qk_mfma(st, f, 0, j)
+    st.emit("s_mov_b32 %[stg_k], %[stmp]")
+    st.emit("s_nop 15")
+    st.emit("s_nop 15")
+    for o in w_e1_ops(0):
+        st.emit(o)
+    for f in range(W_D):                                   # K prefetch of tile 1 for X(0)
+        w_k_read(st, f)
+
+
+def w_entry_check(st, entry):
+    """A body label is reachable from the prologue (cnt == 0) as well as from the body in front of it: the bookkeeping there has to assume
+    at least the prologue's K prefetch in flight, or the first MFMAs would be emitted without their lgkmcnt waits."""
+    assert st.pending[-len(entry):] == list(entry), st.pending
+    st.entry_checks = getattr(st, "entry_checks", 0) + 1
+
+
+def w_emit():
+    st = Stream()
+    w_prologue(st)
+    entry = [("K", f) for f in range(W_D)]
+    assert st.pending == entry
+    L = 30
+    st.emit("s_cmp_eq_u32 %[cnt], 0")
+    st.emit(f"s_cbranch_scc1 {L + 2}f")
+    st.emit(f"{L + 1}:")
+    w_entry_check(st, entry)
+    w_body(st, 0, True)
+    w_body(st, 1, True)
+    assert set(st.pending) <= set(entry)
+    st.emit("s_sub_u32 %[cnt], %[cnt], 1")
+    st.emit("s_cmp_lg_u32 %[cnt], 0")
+    st.emit(f"s_cbranch_scc1 {L + 1}b")
+    st.emit(f"{L + 2}:")
+    st.emit("s_cmp_eq_u32 %[rem], 0")
+    st.emit(f"s_cbranch_scc1 {L + 3}f")
+    st.pending = list(entry)                             # reached from the prologue too (two tiles): its K reads are still in flight
+    w_entry_check(st, entry)
+    w_body(st, 0, True)
+    w_body(st, 1, False)
+    st.emit(f"s_branch {L + 4}f")
+    st.emit(f"{L + 3}:")
+    st.pending = list(entry)
+    w_entry_check(st, entry)
+    w_body(st, 0, False)
+    st.emit(f"{L + 4}:")
+    st.emit("s_waitcnt vmcnt(0)")
+    st.emit("s_waitcnt lgkmcnt(0)")
+    st.emit("s_barrier")
+    st.emit("s_nop 15")
+    st.emit("s_nop 15")
+    assert st.entry_checks == 3                          # every label a body starts at: the loop top, the remainder, the last tile
+    w_selfcheck(st.ins)
+    return st.ins
+
+
+def regs(tok):
+    """('v' | 'a', lo, hi) of a register operand token, else None"""
+    m = re.fullmatch(r"([va])(\d+)", tok) or re.fullmatch(r"([va])\[(\d+):(\d+)\]", tok)
+    if not m:
+        return None
+    return m.group(1), int(m.group(2)), int(m.group(m.lastindex))
+
+
+def mfma_valu_distances(lines):
+    """For every non-MFMA instruction of a straight-line listing that names a register an earlier MFMA wrote: (MFMAs issued in between,
+    wait states in between with s_nop N = N + 1 and anything else 1, the line).  Only the LAST writer of a register counts."""
+    last = {}                                            # (file, n) -> (mfma ordinal, position in wait states)
+    out, n_mfma, pos = [], 0, 0
+    for l in lines:
+        op = l.split()[0] if l.split() else ""
+        toks = [t.strip(",") for t in l.split()[1:]]
+        if op.startswith("v_mfma"):
+            n_mfma += 1
+            pos += 1
+            f, lo, hi = regs(toks[0])
+            for r in range(lo, hi + 1):
+                last[(f, r)] = (n_mfma, pos)
+            continue
+        if op.endswith(":") or not op:
+            continue
+        hit = None
+        for t in toks:
+            r = regs(t)
+            if r:
+                for k in range(r[1], r[2] + 1):
+                    if (r[0], k) in last:
+                        w = last.pop((r[0], k))
+                        hit = w if hit is None or w[1] > hit[1] else hit
+        if hit:
+            out.append((n_mfma - hit[0], pos - hit[1], l))
+        m = re.fullmatch(r"s_nop (\d+)", l)
+        pos += int(m.group(1)) + 1 if m else 1
+    return out
+
+
+def w_selfcheck(lines):
+    n_read = sum(l.startswith("ds_read") for l in lines)
+    n_mfma = sum(l.startswith("v_mfma") for l in lines)
+    for l in lines:
+        assert not l.startswith(("v_pk_", "v_dot2")), l
+        for t in l.split()[1:]:
+            r = regs(t.strip(","))
+            if r:
+                assert r[2] < (W_NV if r[0] == "v" else W_NA) and (r[0] == "a" or r[1] >= 32), l
+    # three full bodies (64 MFMAs, 32 fragment reads), two last-tile bodies (32 PV MFMAs, 16 reads); the prologue's S(0): 32 MFMAs, 16 + D reads
+    assert n_mfma == 3 * 64 + 2 * 32 + 32, n_mfma
+    assert n_read == 3 * 32 + 2 * 16 + 16 + W_D, n_read
+    for x, y in zip(lines, lines[1:]):
+        assert not (x.startswith("s_add_u32 m0") and y.startswith("buffer_load")), (x, y)
+    for between, states, l in mfma_valu_distances(lines):
+        assert between >= W_MFMA_TO_VALU - 1 or states >= 32, (between, states, l)
+
+
 def main():
     here = os.path.dirname(os.path.abspath(__file__))
     out = os.path.join(here, "..", "regione_amd", "csrc", "attn_loop_asm.inc")
@@ -513,6 +903,15 @@ def main():
             for l in lines:
                 f.write(f'    "{l}\\n\\t" \\\n')
             f.write('    ""\n')
+        lines = w_emit()
+        n_mfma = sum(1 for l in lines if l.startswith("v_mfma"))
+        f.write(f"// RGN_ATTN_LOOP_W64_ASM: {len(lines)} instructions, {n_mfma} MFMAs (4 waves x 64 query rows, static shift)\n")
+        f.write("#define RGN_ATTN_LOOP_W64_ASM \\\n")
+        for l in lines:
+            f.write(f'    "{l}\\n\\t" \\\n')
+        f.write('    ""\n')
+        clob = [f'"a{n}"' for n in range(W_NA)] + [f'"v{n}"' for n in range(32, W_NV)] + ['"memory"', '"scc"', '"vcc"']
+        f.write("#define RGN_ATTN_LOOP_W64_CLOBBERS " + ", ".join(clob) + "\n")
         clob = [f'"a{n}"' for n in range(96)] + [f'"v{n}"' for n in range(32, 160)] + ['"memory"', '"scc"', '"vcc"']
         f.write("#define RGN_ATTN_LOOP_CLOBBERS " + ", ".join(clob) + "\n")
     print(f"wrote {os.path.normpath(out)}")

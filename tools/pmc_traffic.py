@@ -32,7 +32,7 @@ def per_kernel(db):
         # attention_asm_kernel (hand-scheduled loop) and attention_kernel (ragged KV lengths) count as one kernel family;
         # the small merge kernels (attention_combine*) are left out
         k = ("gemm_bf16_kernel" if ("gemm_bf16_kernel" in name or "gemm_reduce4w_kernel" in name) else
-             "attention_kernel" if ("attention_kernel" in name or "attention_asm_kernel" in name) else None)
+             "attention_kernel" if ("attention_kernel" in name or "attention_asm_kernel" in name or "attention_asm64_kernel" in name) else None)
         if k:
             d = out.setdefault(k, {}).setdefault(counter, [0, 0.0])
             d[0] += n
@@ -110,7 +110,7 @@ def main():
              f"join {disp} d on e.{key} = d.{dkey} join {sym} s on d.kernel_id = s.id group by s.kernel_name, p.name")
         for name, counter, total in c.execute(q):
             fam = ("gemm_bf16_kernel" if ("gemm_bf16_kernel" in name or "gemm_reduce4w" in name) else
-                   "attention_kernel" if ("attention_kernel" in name or "attention_asm_kernel" in name) else
+                   "attention_kernel" if ("attention_kernel" in name or "attention_asm_kernel" in name or "attention_asm64_kernel" in name) else
                    "gemv_bf16_kernel (HBM-streaming yardstick)" if "gemv_bf16_kernel" in name else
                    "ln_modulate_kernel" if "ln_modulate" in name else None)
             if fam:
