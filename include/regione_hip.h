@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 108
+#define RGN_ABI_VERSION 109
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -467,6 +467,33 @@ int rgn_mrope_bf16(void* QKV, int ld, const void* cos, const void* sin, int L, i
  * `self.act_fn(self.gate_proj(x)) * self.up_proj(x)` of Qwen2MLP.forward with its two roundings.
  * F % 8 == 0, ldx >= 2 F, ldy >= F (strides multiples of 8), x and y 16-byte aligned. */
 int rgn_swiglu_bf16(const void* x, int ldx, void* y, int ldy, int M, int F, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * f4  vision tower of the Qwen2.5-VL prompt encoder ([EXT] transformers Qwen2_5_VisionTransformerPretrainedModel: `get_image_features`
+ * of the encode_prompt above).  Projections (the patch embedding included) are rgn_gemm_bf16, the norms rgn_rms_norm_rows, the MLP
+ * product rgn_swiglu_bf16, the window reorder rgn_gather_rows / the GEMM's out_rows; these are the pieces around them (csrc/vision.hip).
+ *
+ * Non-causal self-attention over packed segments (the windows of a window block, one segment per image of a full-attention block), read
+ * straight from the fused QKV GEMM output: QKV [L, 3 H Dp] bf16 (all q heads | all k heads | all v heads), O [L, H Dp] bf16.  Dp in
+ * {32, 64, 96, 128} is the head width padded with ZERO columns to a multiple of 32 (zero weight rows and bias entries: the dot products
+ * and the real output columns are unchanged, the output's pad columns are exactly 0); `scale` is the caller's (real width ^ -0.5).
+ * items: int32 [n_items, 4] on the device = (q0, n_q, k_lo, k_hi): queries [q0, q0 + n_q), 1 <= n_q <= 64, attend to keys [k_lo, k_hi),
+ * their segment; no item crosses a segment; one workgroup per (item, head).  An item outside [0, L) is skipped; rows no item names are
+ * not written.  Replaces the per-chunk attention interface calls of Qwen2_5_VLVisionAttention.forward.  Arithmetic and determinism as
+ * rgn_lm_attention_bf16 (same tile core).  QKV, O, items 16-byte aligned; 1 <= H <= 1024; 0 < scale < inf. */
+int rgn_vision_attention_bf16(const void* QKV, void* O, int L, int H, int Dp, float scale, const int* items, int n_items, void* stream);
+/* apply_rotary_pos_emb_vision on the q and k columns (the first 2 H Dp of each row) of that QKV buffer, in place:
+ *   x <- bf16(f32(x) * cos + f32(rotate_half(x)) * sin),   rotate_half(x) = [-x[D/2:], x[:D/2]] per head over the REAL width D
+ * both products and the sum rounded to fp32, one rounding to bf16 (bit-equal to the eager op).  cos, sin: fp32 [L, D], one row per token.
+ * Columns D..Dp of each head and the v columns are not written.  D % 8 == 0, Dp >= D with Dp % 32 == 0, ld >= 3 H Dp (a multiple of 8);
+ * QKV, cos, sin 16-byte aligned. */
+int rgn_vision_rope_bf16(void* QKV, int ld, const float* cos, const float* sin, int L, int H, int D, int Dp, void* stream);
+/* nn.GELU() in its exact form on bf16: y = bf16(0.5 x (1 + erf(x / sqrt 2))) in fp32 (the patch merger; RGN_EPI_GELU is the tanh form).
+ * y may be x. */
+int rgn_gelu_erf_bf16(const void* x, void* y, size_t n, void* stream);
+/* y[m, :K] = bf16(x[m, :K]), y[m, K:Kp] = 0: x [M, K] fp32 (RGN_F32) or bf16 (RGN_BF16) with row stride ldx, y [M, Kp] bf16 contiguous,
+ * 16-byte aligned, Kp % 8 == 0.  `pixel_values.to(bfloat16)` padded to a GEMM reduction width (K = 1176 -> Kp = 1216). */
+int rgn_cast_pad_rows(const void* x, int x_dtype, int ldx, void* y, int M, int K, int Kp, void* stream);
 
 /* Device properties the host side needs for roofline reporting (no torch types). */
 int rgn_device_info(int* cu_count, int* clock_khz, size_t* hbm_bytes);

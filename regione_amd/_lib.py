@@ -133,6 +133,11 @@ SIGNATURES = {
     "rgn_lm_attention_bf16": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p],
     "rgn_mrope_bf16": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
     "rgn_swiglu_bf16": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
+    # f4: vision tower of the Qwen2.5-VL prompt encoder (csrc/vision.hip)
+    "rgn_vision_attention_bf16": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p, _c_int, _c_void_p],
+    "rgn_vision_rope_bf16": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p],
+    "rgn_gelu_erf_bf16": [_c_void_p, _c_void_p, C.c_size_t, _c_void_p],
+    "rgn_cast_pad_rows": [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
 }
 _RESTYPE = {"rgn_last_error": C.c_char_p, "rgn_abi_struct_bytes": C.c_size_t, "rgn_attention_workspace_bytes": C.c_size_t,
             "rgn_gemm_workspace_bytes": C.c_size_t, "rgn_groupnorm_workspace_bytes": C.c_size_t,

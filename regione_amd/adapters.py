@@ -390,8 +390,11 @@ def hip_qwen_text_encoder_for(host, dev):
     """The host's Qwen2.5-VL prompt encoder with its language model adopted onto the HIP kernels (regione_amd/qwen_text_encoder.py;
     SURVEY.md section 8 row f4), once per host pipeline and kept on it as `_regione_hip_qwen_text`.  A module the kernels do not cover
     (`qwen25vl_refusal`: sliding-window layers, another head dim, ...; non-bf16 weights; PEFT / LoRA layers) stays the host's, with one
-    warning naming the reason.  A `text_encoder` that is not a `Qwen2_5_VLForConditionalGeneration` is left alone silently;
-    `pipe._regione_hip_text = False` before the first call keeps the host module on purpose."""
+    warning naming the reason.  With the language model the vision tower is adopted (regione_amd/qwen_vision.py) and handed to the encoder
+    as `vision=`; a tower `vision_refusal` names (or one with non-bf16 weights) stays the host's eager module under the adopted language
+    model, with one "vision tower kept on the host module: ..." warning; `pipe._regione_hip_vision = False` keeps it there on purpose,
+    silently.  A `text_encoder` that is not a `Qwen2_5_VLForConditionalGeneration` is left alone silently;
+    `pipe._regione_hip_text = False` before the first call keeps the whole host module on purpose."""
     if host.__dict__.get("_regione_hip_text", _NO_HIP_VAE) is False:
         return None
     cached = host.__dict__.get("_regione_hip_qwen_text", _NO_HIP_VAE)
@@ -411,6 +414,16 @@ def hip_qwen_text_encoder_for(host, dev):
                 why = str(e)
         if why is not None:
             warnings.warn(f"text_encoder kept on the host module: {why}", RuntimeWarning, stacklevel=3)
+        elif host.__dict__.get("_regione_hip_vision", _NO_HIP_VAE) is not False:
+            from . import qwen_vision as QV
+            why = QV.vision_refusal(mod.config)
+            if why is None:
+                try:
+                    enc.vision = QV.HipQwen25VLVisionTower(mod, dev)
+                except _lib.RegionEHipError as e:
+                    why = str(e)
+            if why is not None:
+                warnings.warn(f"vision tower kept on the host module: {why}", RuntimeWarning, stacklevel=3)
     host._regione_hip_qwen_text = enc
     return enc
 

@@ -15,8 +15,9 @@
 
 Positions are the adopted module's own: `module.model.compute_3d_position_ids(...)` with the caller's arguments (None -> the plain arange
 of Qwen2_5_VLTextModel.forward); the cos / sin tables are built on the CPU with the module's `rotary_emb` arithmetic and `inv_freq`
-buffer, the `mrope_section` selection applied once, cast to bf16 and copied in one host-to-device copy per call.  The vision tower stays the
-host's eager module (`get_image_features`); its embeddings are placed at the image-token rows by rgn_scatter_rows.
+buffer, the `mrope_section` selection applied once, cast to bf16 and copied in one host-to-device copy per call.  The vision tower is
+`vision=`, a HipQwen25VLVisionTower (regione_amd/qwen_vision.py: the tower on the same kernels; the adapter passes one), or with
+`vision=None` the host's eager module (`get_image_features`); its embeddings are placed at the image-token rows by rgn_scatter_rows.
 
 There is no eager fallback inside: what the kernels do not implement raises RegionEHipError before any launch, and the adapter
 (regione_amd/adapters.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
@@ -161,8 +162,9 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
     states) are absent.  Padded positions are zero rows."""
     what = "HipQwen25VLTextEncoder"
 
-    def __init__(self, module_or_state_dict, device=None, config=None, max_length: int = 4096):
+    def __init__(self, module_or_state_dict, device=None, config=None, max_length: int = 4096, vision=None):
         sd, cfg, dev, mod = _source(module_or_state_dict, config, device, self.what)
+        self.vision = vision                               # a HipQwen25VLVisionTower, or None: the adopted module's eager tower
         why = qwen25vl_refusal(cfg)
         if why:
             _refuse(self.what, why)
@@ -249,14 +251,16 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         lengths = valid_lengths(attention_mask, B, L, self.what)
         if pixel_values is not None and image_embeds is not None:
             _refuse(self.what, "pass pixel_values or image_embeds, not both")
-        if pixel_values is not None and self.module is None:
+        if pixel_values is not None and self.module is None and self.vision is None:
             _refuse(self.what, "adopted from a state dict (no vision tower at hand): pass image_embeds instead of pixel_values")
         pos = self.position_ids_for(input_ids, attention_mask, image_grid_thw, position_ids, mm_token_type_ids)
         tables = mrope_tables(self.inv_freq, pos, self.mrope_section)
         return ids_cpu, lengths, tables
 
     def _image_embeds(self, pixel_values, image_grid_thw, image_embeds):
-        if pixel_values is not None:                       # the vision tower: the host's eager module, as in Qwen2_5_VLModel.forward
+        if pixel_values is not None and self.vision is not None:       # the vision tower on the HIP kernels
+            image_embeds = self.vision(pixel_values, image_grid_thw).pooler_output
+        elif pixel_values is not None:                     # the host's eager module, as in Qwen2_5_VLModel.forward
             image_embeds = self.module.get_image_features(pixel_values, image_grid_thw).pooler_output
         if image_embeds is None:
             return None
