@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 109
+#define RGN_ABI_VERSION 110
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -51,7 +51,7 @@ int rgn_plan_override(const char* key, int value);
 /* The current value of one knob (-1 = not forced), so that a scoped override can restore what it found instead of resetting
  * (nested scopes, a process preset through RGN_PLAN_OVERRIDE). */
 int rgn_plan_override_get(const char* key, int* value);
-/* The launch plan the GEMM planner chose for the last rgn_gemm_* call on this thread (introspection for tests and traces; the
+/* The launch plan the GEMM planner chose for the last rgn_gemm_group call on this thread (introspection for tests and traces; the
  * reference has no counterpart): bits 0-7 = K pieces of the remainder (1 = none), bit 8 = quarter-tile remainder, bit 10 =
  * 256 x 256 tile geometry. */
 int rgn_gemm_last_plan(void);
@@ -128,52 +128,64 @@ int rgn_cfg_combine(const void* pos, const void* neg, void* out, int dtype, floa
                     int K, int D, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * bf16 MFMA GEMM  C = epilogue(A[M,K] @ W[N,K]^T + bias)  (fp32 accumulate).
- * Replaces torch nn.Linear calls of the block bodies [EXT diffusers] and, with `out_rows`,
- * the Triton index-scatter GEMM _partially_linear (fused_kernels.py:9-101).
+ * MFMA GEMM  C = epilogue(A[M,K] @ W[N,K]^T + bias)  (bf16 activations, bf16 or fp8 weights, fp32 accumulate): ONE entry point,
+ * rgn_gemm_group, one descriptor (rgn_gemm_problem) per problem.  Replaces torch nn.Linear calls of the block bodies [EXT diffusers]
+ * and, with `out_rows`, the Triton index-scatter GEMM _partially_linear (fused_kernels.py:9-101).
  *   epilogue: RGN_EPI_BIAS        C[r] = bf16(acc + bias)
- *             RGN_EPI_GELU        C[r] = bf16(gelu_tanh(bf16(acc + bias)))  for columns >= gelu_from_col
+ *             RGN_EPI_GELU        C[r] = bf16(gelu_tanh(bf16(acc + bias)))  for columns >= gelu_from_col (rounded up to 8)
  *             RGN_EPI_GATE_RESID  C[r] = bf16(f32(resid[r]) + f32(bf16(gate[n] * bf16(acc + bias))))
+ *             RGN_EPI_QKV         the fused Q/K/V epilogue below; gelu_from_col <= 0 means "no GELU columns" (= N)
  *   r = out_rows ? out_rows[m] : m   (row scatter; out_rows int64 or NULL)
- * K % 64 == 0; M, N arbitrary (>0).  resid uses ldc and may alias C.
- */
-#define RGN_EPI_BIAS 0
-#define RGN_EPI_GELU 1
-#define RGN_EPI_GATE_RESID 2
-int rgn_gemm_bf16(const void* A, int lda, const void* W, int ldw, const void* bias, void* C, int ldc,
-                  int M, int N, int K, int epilogue, int gelu_from_col, const void* gate,
-                  const void* resid, const int64_t* out_rows, void* workspace, size_t workspace_bytes,
-                  void* stream);
-/* `workspace` (optional, fp32 scratch, rgn_gemm_workspace_bytes()) enables the round-aware schedule:
- * output tiles that do not fill a whole round of the chip's workgroup slots are cut along K, spread
- * over all CUs and finished by a reduce pass (8 workgroups per tile, epilogue in registers; bit-identical to a reduce by the
- * tile's own workgroup).  NULL = plain single launch.
+ * K % 64 == 0; M, N arbitrary (N > 0; M == 0 problems are skipped, a call of empty problems only returns 0).  resid uses ldc and may
+ * alias C.  A, W, C, resid 16-byte aligned; lda, ldc (and ldw of bf16 weights) multiples of 8.
+ *
+ * Up to FOUR problems with the same N, K, epilogue and weight format go in ONE launch: the text and image streams of a double block
+ * (the small problem's tiles fill the tail of the large one instead of running as an under-occupied launch of their own), for BOTH
+ * classifier-free-guidance branches (reference: the B = 2 batched CFG forward, Step1XEdit/inplace.py:381-399;
+ * Step1XEditV1P2/inplace.py:398,416 and QwenImageEdit/inplace.py:371-405 run the branches in sequence - rows of different
+ * branches never interact in a Linear, so one launch computes both).  Each problem keeps its own activations, output,
+ * gate / residual (per-branch AdaLN gates) and - with RGN_EPI_QKV - its own Q/K/V epilogue descriptor (per-branch K / V^T
+ * cache slabs, rotary tables and cache-row lists); problems may share W (streamed from HBM once for both branches).
+ * Per output element the accumulation order depends only on the tile geometry and the split-K piece count the planner
+ * picks for the launch, never on which other problems share it.
+ * `out_rows` and a strided W (`ldw` other than 0 / K) are accepted only in a launch of exactly one non-empty problem, `out_rows` not
+ * with RGN_EPI_QKV (RGN_E_UNSUPPORTED otherwise).
+ *
+ * fp8 weights (BASELINE.json configs[4]: "fp8 weights on CDNA4"): `wscale` != NULL - then for every problem of the call - says W is
+ * stored as OCP e4m3fn bytes ([N, K], ldw in BYTES, a multiple of 16) with one fp32 scale per output channel (`wscale[N]`, 16-byte
+ * aligned): C = epilogue((A @ dequant(W8)^T) * wscale[n] + bias).  Activations, bias, outputs and every epilogue stay bf16 / fp32
+ * exactly as with bf16 weights; the fp8 -> bf16 conversion is exact (v_cvt_scalef32_pk_bf16_fp8 in registers, after the LDS read),
+ * the scale multiplies the fp32 accumulator.  Replaces nothing in the reference (which ships bf16 weights): storage format of the
+ * [EXT] Linear weights only; quantisation (per-channel absmax / 448) is done by the caller
+ * (regione_amd.harness.flux.FluxTransformer2DModel.quantize_fp8_).  The fp8 tiles are converted in registers inside the
+ * hand-scheduled K loop.  A/B switch RGN_W8_WIDEN_MIN_M=<rows> (default 0 = never): with a workspace and at least that many rows in
+ * total the call first widens W8 to bf16 (exact) into the TAIL of the workspace (N x K x 2 bytes per distinct weight matrix, >= 64 MiB
+ * left for the split remainders) and runs the bf16 K loop on it - same result bit for bit, weights stay fp8 in HBM.
+ *
+ * `workspace` (optional, fp32 scratch, rgn_gemm_workspace_bytes()) enables the round-aware schedule: output tiles that do not fill a
+ * whole round of the chip's workgroup slots are cut along K, spread over all CUs and finished by a reduce pass (8 workgroups per
+ * tile, epilogue in registers; bit-identical to a reduce by the tile's own workgroup).  NULL = plain single launch.
  * Sizing: rgn_gemm_workspace_bytes() is a shape-independent upper bound (256 MiB = 255 remainder tiles x 4 pieces x 256 KiB of
- * fp32 fragments, plus room for the fp8 weight widening of rgn_gemm_w8*); any smaller buffer is valid too - the planner only
- * considers piece counts whose partials fit in `workspace_bytes` (and skips the split / the widening when nothing fits).
- * A workspace belongs to ONE stream at a time: calls on two streams need two buffers. */
-size_t rgn_gemm_workspace_bytes(void);
-
-/* Two independent problems with the same N, K and epilogue in ONE launch (the text and image
- * streams of a double block: different A / W / bias / C / gate / resid).  The small problem's tiles
- * fill the tail of the large one instead of running as an under-occupied launch of their own. */
-int rgn_gemm_bf16_pair(const void* A0, int lda0, const void* W0, const void* bias0, void* C0, int ldc0, int M0,
-                       const void* gate0, const void* resid0, const void* A1, int lda1, const void* W1,
-                       const void* bias1, void* C1, int ldc1, int M1, const void* gate1, const void* resid1,
-                       int N, int K, int epilogue, int gelu_from_col, void* workspace, size_t workspace_bytes,
-                       void* stream);
-
-/* Fused QKV projection (reference: the Linear projections + `attn.norm_q/k` + `apply_rotary_emb` + K/V cache
+ * fp32 fragments, plus room for the fp8 weight widening); any smaller buffer is valid too - the planner only considers piece counts
+ * whose partials fit in `workspace_bytes` (and skips the split / the widening when nothing fits).
+ * A workspace belongs to ONE stream at a time: calls on two streams need two buffers.
+ *
+ * RGN_EPI_QKV, the fused QKV projection (reference: the Linear projections + `attn.norm_q/k` + `apply_rotary_emb` + K/V cache
  * placement of RegoionEFluxAttnProcessor2_0.__call__, FluxKontext/inplace.py:735-794; the K/V partial update
- * `_partially_linear`, fused_kernels.py:81-101).  Same GEMM as rgn_gemm_bf16, but the epilogue of each 256-column
- * block of C does what rgn_qk_norm_rope_store does as a separate pass:
+ * `_partially_linear`, fused_kernels.py:81-101).  The same GEMM, but the epilogue of each 256-column block of C does what
+ * rgn_qk_norm_rope_store does as a separate pass:
  *   columns [k_col, k_col + heads*128): per-head RMSNorm + RoPE (k tables, row kv_rows[r]) -> k_slab row kv_rows[r]
  *   columns [v_col, ...):               transposed into vt_slab (kv index permuted as rgn_attention expects)
  *   columns [q_col, ...):               per-head RMSNorm + RoPE (q tables, row r) -> C in place
  *   columns >= gelu_from_col:           GELU-tanh -> C           (the fused MLP half of a single-stream block)
  * K and V columns are NOT written to C.  r = row_base + local row (row_base: where this problem's rows sit in
  * the joint [text | image] sequence that the tables / kv_rows are indexed by).  Results are bit-identical to
- * rgn_gemm_bf16 followed by rgn_qk_norm_rope_store. */
+ * RGN_EPI_BIAS followed by rgn_qk_norm_rope_store. */
+#define RGN_EPI_BIAS 0
+#define RGN_EPI_GELU 1
+#define RGN_EPI_GATE_RESID 2
+#define RGN_EPI_QKV 3
+#define RGN_EPI_CONV 4            /* rgn_conv_bf16 only */
 typedef struct rgn_qkv_epilogue {
     const void* wq;            /* [128] bf16 RMSNorm weights of this stream (norm_q / norm_added_q) */
     const void* wk;
@@ -189,66 +201,22 @@ typedef struct rgn_qkv_epilogue {
     int fp16_roundtrip;        /* 1: K / V columns round fp32 -> fp16 -> bf16 like the reference's partial-update kernel
                                   (fused_kernels.py:80); 0: one rounding, like F.linear on store / plain steps */
 } rgn_qkv_epilogue;
-#define RGN_EPI_QKV 3
-#define RGN_EPI_CONV 4            /* rgn_conv_bf16 only */
-int rgn_gemm_bf16_qkv(const void* A, int lda, const void* W, int ldw, const void* bias, void* C, int ldc, int M, int N,
-                      int K, int gelu_from_col, const rgn_qkv_epilogue* e, void* workspace, size_t workspace_bytes,
-                      void* stream);
-int rgn_gemm_bf16_qkv_pair(const void* A0, int lda0, const void* W0, const void* bias0, void* C0, int ldc0, int M0,
-                           const rgn_qkv_epilogue* e0, const void* A1, int lda1, const void* W1, const void* bias1,
-                           void* C1, int ldc1, int M1, const rgn_qkv_epilogue* e1, int N, int K, void* workspace,
-                           size_t workspace_bytes, void* stream);
-
-/* Up to FOUR problems with the same N, K, epilogue and weight format in ONE launch: the text and image streams of a double
- * block for BOTH classifier-free-guidance branches (reference: the B = 2 batched CFG forward, Step1XEdit/inplace.py:381-399;
- * Step1XEditV1P2/inplace.py:398,416 and QwenImageEdit/inplace.py:371-405 run the branches in sequence - rows of different
- * branches never interact in a Linear, so one launch computes both).  Each problem keeps its own activations, output,
- * gate / residual (per-branch AdaLN gates) and - with RGN_EPI_QKV - its own Q/K/V epilogue descriptor (per-branch K / V^T
- * cache slabs, rotary tables and cache-row lists); problems may share W (streamed from HBM once for both branches).
- * W is [N, K] contiguous (bf16, or fp8 bytes when `wscale` is set - then for every problem).  M == 0 problems are skipped.
- * Per output element the accumulation order depends only on the tile geometry and the split-K piece count the planner
- * picks for the launch, never on which other problems share it. */
 typedef struct rgn_gemm_problem {
     const void* A;             /* [M, K] bf16, row stride lda */
-    const void* W;             /* [N, K] */
+    const void* W;             /* [N, K], row stride ldw */
     const float* wscale;       /* per-output-channel fp32 scale: W is OCP e4m3fn bytes; NULL: W is bf16 */
     const void* bias;          /* [N] bf16 or NULL */
     void* C;                   /* [M, N] bf16, row stride ldc */
     const void* gate;          /* RGN_EPI_GATE_RESID */
     const void* resid;
     const rgn_qkv_epilogue* qkv;   /* RGN_EPI_QKV */
+    const int64_t* out_rows;   /* row scatter, NULL = identity */
     int lda, ldc, M;
+    int ldw;                   /* 0 = W is dense: K elements (bf16) / K bytes (fp8) */
 } rgn_gemm_problem;
 int rgn_gemm_group(const rgn_gemm_problem* probs, int nprob, int N, int K, int epilogue, int gelu_from_col, void* workspace,
                    size_t workspace_bytes, void* stream);
-
-/* fp8 weights (BASELINE.json configs[4]: "fp8 weights on CDNA4").  The same four GEMM entry points with W stored as OCP
- * e4m3fn bytes ([N, K], ldw in BYTES, a multiple of 16) plus one fp32 scale per output channel (`wscale[N]`, 16-byte
- * aligned): C = epilogue((A @ dequant(W8)^T) * wscale[n] + bias).  Activations, bias, outputs and every epilogue stay
- * bf16 / fp32 exactly as in the bf16 calls; the fp8 -> bf16 conversion is exact (v_cvt_scalef32_pk_bf16_fp8 in registers, after
- * the LDS read), the scale multiplies the fp32 accumulator.  Replaces nothing in the reference (which ships bf16 weights):
- * storage format of the [EXT] Linear weights only; quantisation (per-channel absmax / 448) is done by the caller
- * (regione_amd.harness.flux.FluxTransformer2DModel.quantize_fp8_).
- * Default since round 3: the fp8 tiles are converted in registers inside the hand-scheduled K loop.  A/B switch RGN_W8_WIDEN_MIN_M=<rows>
- * (default 0 = never): with a workspace and at least that many rows in total the call first widens W8 to bf16 (exact) into the TAIL
- * of the workspace (N x K x 2 bytes per distinct weight matrix, >= 64 MiB left for the split remainders) and runs the bf16 K loop on
- * it - same result bit for bit, weights stay fp8 in HBM. */
-int rgn_gemm_w8(const void* A, int lda, const void* W8, int ldw, const float* wscale, const void* bias, void* C, int ldc,
-                int M, int N, int K, int epilogue, int gelu_from_col, const void* gate, const void* resid,
-                const int64_t* out_rows, void* workspace, size_t workspace_bytes, void* stream);
-int rgn_gemm_w8_pair(const void* A0, int lda0, const void* W0, const float* wscale0, const void* bias0, void* C0, int ldc0,
-                     int M0, const void* gate0, const void* resid0, const void* A1, int lda1, const void* W1,
-                     const float* wscale1, const void* bias1, void* C1, int ldc1, int M1, const void* gate1,
-                     const void* resid1, int N, int K, int epilogue, int gelu_from_col, void* workspace,
-                     size_t workspace_bytes, void* stream);
-int rgn_gemm_w8_qkv(const void* A, int lda, const void* W8, int ldw, const float* wscale, const void* bias, void* C, int ldc,
-                    int M, int N, int K, int gelu_from_col, const rgn_qkv_epilogue* e, void* workspace,
-                    size_t workspace_bytes, void* stream);
-int rgn_gemm_w8_qkv_pair(const void* A0, int lda0, const void* W0, const float* wscale0, const void* bias0, void* C0,
-                         int ldc0, int M0, const rgn_qkv_epilogue* e0, const void* A1, int lda1, const void* W1,
-                         const float* wscale1, const void* bias1, void* C1, int ldc1, int M1,
-                         const rgn_qkv_epilogue* e1, int N, int K, void* workspace, size_t workspace_bytes, void* stream);
-
+size_t rgn_gemm_workspace_bytes(void);
 
 /* Skinny GEMV for the AdaLN modulation / timestep embedders:
  *   y[b,n] = bf16( sum_k W[n,k] * act(x[b,k]) + bias[n] ),  act = silu (rounded to bf16) if silu_input.
@@ -390,7 +358,7 @@ int rgn_groupnorm_silu(const void* X, void* Y, int Hp, int Wp, int C, const void
                        void* workspace, int precomputed_blocks, void* stream);
 /* Nearest-neighbour 2 x upsample of a padded image [Hp * Wp, C] into the padded image [(2 Hp - 2) * (2 Wp - 2), C] (border zero). */
 int rgn_upsample2x(const void* X, void* Y, int Hp, int Wp, int C, void* stream);
-/* Mid-block attention = three GEMMs (rgn_gemm_bf16) + this pass: S [Hp * Wp, ld] holds q . k for every (query, key) pixel of the
+/* Mid-block attention = three GEMMs (rgn_gemm_group) + this pass: S [Hp * Wp, ld] holds q . k for every (query, key) pixel of the
  * padded image; in place P = softmax(scale * S) per row over the VALID key columns (border pixels and the padding columns
  * [Hp * Wp, ld) get probability 0).  ld % 8 == 0, ld <= 24576. */
 int rgn_softmax_rows(void* S, int ld, int Hp, int Wp, float scale, void* stream);
@@ -417,7 +385,7 @@ int rgn_rms_norm_silu(const void* X, void* Y, int Hp, int Wp, int C_valid, int C
 
 /* ------------------------------------------------------------------------------------------
  * f4  text encoders of FLUX.1 Kontext: `encode_prompt` (FluxKontext/inplace.py:185-211) runs [EXT] transformers CLIPTextModel
- * (pooler_output) and T5EncoderModel (last_hidden_state).  Projections are rgn_gemm_bf16; these are the pieces around it.
+ * (pooler_output) and T5EncoderModel (last_hidden_state).  Projections are rgn_gemm_group; these are the pieces around it.
  *
  * Self-attention with head dim 64, read straight from the fused QKV GEMM output: QKV [L, 3 H 64] bf16 (columns q | k | v, head-major
  * inside each), O [L, H 64] bf16; both 16-byte aligned.  Per head and query i:
@@ -430,7 +398,7 @@ int rgn_text_attention_bf16(const void* QKV, void* O, int L, int H, float scale,
  * [0, vocab) gives a zero row (the table is never read out of bounds).  ids int64 [L]; tok [vocab, d], pos [npos, d] (NULL: T5's
  * plain gather; else L <= npos), out [L, d]: bf16, 16-byte aligned, d % 8 == 0. */
 int rgn_text_embed(const int64_t* ids, int L, const void* tok, int vocab, const void* pos, int npos, void* out, int d, void* stream);
-/* T5 v1.1 gated-GELU product: y[m, f] = bf16(x[m, F + f] * x[m, f]) - x is the output of ONE rgn_gemm_bf16 over [wi_1 ; wi_0] with
+/* T5 v1.1 gated-GELU product: y[m, f] = bf16(x[m, F + f] * x[m, f]) - x is the output of ONE rgn_gemm_group problem over [wi_1 ; wi_0] with
  * RGN_EPI_GELU from column F (linear half, then GELU-tanh half); `hidden_gelu * hidden_linear` of T5DenseGatedActDense.
  * F % 8 == 0, ldx >= 2 F, ldy >= F (strides multiples of 8), x and y 16-byte aligned. */
 int rgn_geglu_bf16(const void* x, int ldx, void* y, int ldy, int M, int F, void* stream);
@@ -447,7 +415,7 @@ int rgn_text_pool_row(const int64_t* ids, int L, int eos_token_id, const void* x
 /* ------------------------------------------------------------------------------------------
  * f4  language model of the Qwen2.5-VL prompt encoder: `encode_prompt` of QwenImageEditPipeline / QwenImageEditPlusPipeline
  * (QwenImageEdit/inplace.py, QwenImageEditPlus/inplace.py) runs [EXT] transformers Qwen2_5_VLForConditionalGeneration.  Projections are
- * rgn_gemm_bf16, the norms rgn_rms_norm_rows, the embedding rgn_text_embed; these are the pieces around them.
+ * rgn_gemm_group, the norms rgn_rms_norm_rows, the embedding rgn_text_embed; these are the pieces around them.
  *
  * Causal grouped-query self-attention with head dim 128, read straight from the fused QKV GEMM output: QKV [L, (Hq + 2 Hkv) 128] bf16
  * (columns q | k | v, head-major inside each), O [L, Hq 128] bf16; both 16-byte aligned.  Query head h uses KV head h / (Hq / Hkv):
@@ -463,14 +431,14 @@ int rgn_lm_attention_bf16(const void* QKV, void* O, int L, int Hq, int Hkv, floa
  *   x <- bf16(bf16(x * cos) + bf16(rotate_half(x) * sin)),   rotate_half(x) = [-x[64:], x[:64]] per head.
  * ld = row stride of QKV in elements (>= (Hq + 2 Hkv) 128, a multiple of 8); QKV, cos, sin 16-byte aligned. */
 int rgn_mrope_bf16(void* QKV, int ld, const void* cos, const void* sin, int L, int Hq, int Hkv, void* stream);
-/* SwiGLU product: y[m, f] = bf16(bf16(silu(x[m, f])) * x[m, F + f]) - x is the output of ONE rgn_gemm_bf16 over [gate_proj ; up_proj];
+/* SwiGLU product: y[m, f] = bf16(bf16(silu(x[m, f])) * x[m, F + f]) - x is the output of ONE rgn_gemm_group problem over [gate_proj ; up_proj];
  * `self.act_fn(self.gate_proj(x)) * self.up_proj(x)` of Qwen2MLP.forward with its two roundings.
  * F % 8 == 0, ldx >= 2 F, ldy >= F (strides multiples of 8), x and y 16-byte aligned. */
 int rgn_swiglu_bf16(const void* x, int ldx, void* y, int ldy, int M, int F, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * f4  vision tower of the Qwen2.5-VL prompt encoder ([EXT] transformers Qwen2_5_VisionTransformerPretrainedModel: `get_image_features`
- * of the encode_prompt above).  Projections (the patch embedding included) are rgn_gemm_bf16, the norms rgn_rms_norm_rows, the MLP
+ * of the encode_prompt above).  Projections (the patch embedding included) are rgn_gemm_group, the norms rgn_rms_norm_rows, the MLP
  * product rgn_swiglu_bf16, the window reorder rgn_gather_rows / the GEMM's out_rows; these are the pieces around them (csrc/vision.hip).
  *
  * Non-causal self-attention over packed segments (the windows of a window block, one segment per image of a full-attention block), read

@@ -35,9 +35,10 @@ _qkv_p = C.POINTER(QkvEpilogue)
 
 
 class GemmProblem(C.Structure):
-    """struct rgn_gemm_problem (include/regione_hip.h): one problem of rgn_gemm_group."""
+    """struct rgn_gemm_problem (include/regione_hip.h): one problem of rgn_gemm_group, the one GEMM entry point."""
     _fields_ = [("A", _c_void_p), ("W", _c_void_p), ("wscale", _c_void_p), ("bias", _c_void_p), ("C", _c_void_p),
-                ("gate", _c_void_p), ("resid", _c_void_p), ("qkv", _qkv_p), ("lda", _c_int), ("ldc", _c_int), ("M", _c_int)]
+                ("gate", _c_void_p), ("resid", _c_void_p), ("qkv", _qkv_p), ("out_rows", _c_void_p), ("lda", _c_int), ("ldc", _c_int),
+                ("M", _c_int), ("ldw", _c_int)]
 
 
 _prob_p = C.POINTER(GemmProblem)
@@ -64,29 +65,8 @@ SIGNATURES = {
                        _c_int, _c_void_p],
     "rgn_avd_apply": [_c_void_p, _c_int, _c_void_p, _c_float, _c_int, _c_void_p, _c_int, _c_int, _c_void_p],
     "rgn_cfg_combine": [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_float, _c_int, _c_float, _c_int, _c_int, _c_void_p],
-    "rgn_gemm_bf16": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int,
-                      _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, C.c_size_t, _c_void_p],
     "rgn_gemm_workspace_bytes": [],
     "rgn_gemm_group": [_prob_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p, C.c_size_t, _c_void_p],
-    "rgn_gemm_bf16_qkv": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int,
-                          _qkv_p, _c_void_p, C.c_size_t, _c_void_p],
-    "rgn_gemm_bf16_qkv_pair": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _qkv_p,
-                               _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _qkv_p,
-                               _c_int, _c_int, _c_void_p, C.c_size_t, _c_void_p],
-    "rgn_gemm_bf16_pair": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p,
-                           _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p,
-                           _c_int, _c_int, _c_int, _c_int, _c_void_p, C.c_size_t, _c_void_p],
-    # fp8 (e4m3fn) weights + per-output-channel fp32 scales: the bf16 signatures with a scale pointer behind each W
-    "rgn_gemm_w8": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int,
-                    _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, C.c_size_t, _c_void_p],
-    "rgn_gemm_w8_pair": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p,
-                         _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p,
-                         _c_int, _c_int, _c_int, _c_int, _c_void_p, C.c_size_t, _c_void_p],
-    "rgn_gemm_w8_qkv": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int,
-                        _c_int, _qkv_p, _c_void_p, C.c_size_t, _c_void_p],
-    "rgn_gemm_w8_qkv_pair": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _qkv_p,
-                             _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _qkv_p,
-                             _c_int, _c_int, _c_void_p, C.c_size_t, _c_void_p],
     "rgn_gemv_bf16": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int,
                       _c_void_p],
     "rgn_rms_norm_rows": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p],

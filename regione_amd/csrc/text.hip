@@ -1,5 +1,5 @@
 // Text encoders of FLUX.1 Kontext (`encode_prompt`, reference call sites FluxKontext/inplace.py:185-211):
-// [EXT] transformers CLIPTextModel (the pooled vector) and T5EncoderModel (the 512 context tokens).  Every projection is rgn_gemm_bf16;
+// [EXT] transformers CLIPTextModel (the pooled vector) and T5EncoderModel (the 512 context tokens).  Every projection is rgn_gemm_group;
 // this file holds what the two encoders add around it:
 //   text_attention_kernel     self-attention read straight from the fused QKV GEMM output [L, (Hq + 2 Hkv) D] -> O [L, Hq D] on the tile
 //                             core of attn_tile.h.  D = 64, Hq = Hkv: scale, causal mask (CLIP), per-head relative-position bias table (T5)

@@ -23,6 +23,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <cmath>
 #include <list>
 #include <mutex>
@@ -254,6 +255,25 @@ void check_act(const Tensor& x, const Tensor& w, const Tensor& out, const OptTen
                 "fp8 weight without its per-output-channel fp32 scale (w_scale)");
 }
 
+// one problem of the fused projection as rgn_gemm_group takes it (check_act has seen the tensors); `e` must outlive the launch
+rgn_gemm_problem problem(const Tensor& x, const Tensor& w, const OptTensor& w_scale, const OptTensor& bias, const Tensor& out,
+                         const rgn_qkv_epilogue* e) {
+    rgn_gemm_problem p;
+    p.A = ptr(x); p.W = ptr(w); p.wscale = (const float*)ptr(w_scale); p.bias = ptr(bias);
+    p.C = out.data_ptr(); p.gate = nullptr; p.resid = nullptr; p.qkv = e; p.out_rows = nullptr;
+    p.lda = (int)x.stride(0); p.ldc = (int)out.stride(0); p.M = (int)x.size(0); p.ldw = (int)w.stride(0);
+    return p;
+}
+
+// the non-empty problems of `ps` (equal [N, K] weights `w`) in one launch on the current stream of `like`, fused Q/K/V epilogue
+void launch_qkv(std::vector<rgn_gemm_problem> ps, const Tensor& w, int64_t gelu_from_col, const Tensor& like) {
+    ps.erase(std::remove_if(ps.begin(), ps.end(), [](const rgn_gemm_problem& p) { return p.M == 0; }), ps.end());
+    if (ps.empty()) return;
+    Tensor ws = gemm_ws(like);
+    check_rc(rgn_gemm_group(ps.data(), (int)ps.size(), (int)w.size(0), (int)w.size(1), RGN_EPI_QKV, (int)gelu_from_col, ws.data_ptr(),
+                            (size_t)ws.numel() * 4, stream_of(like)), "rgn_gemm_group");
+}
+
 void kv_partial_update_(const Tensor& x, const Tensor& w_kvq, const OptTensor& b_kvq, Tensor q_out, const Tensor& norm_q,
                         const Tensor& norm_k, const Tensor& cos_q, const Tensor& sin_q, const Tensor& cos_k, const Tensor& sin_k,
                         const OptTensor& kv_rows, Tensor k_cache, Tensor vt_cache, int64_t heads, int64_t row_base, double eps,
@@ -261,17 +281,7 @@ void kv_partial_update_(const Tensor& x, const Tensor& w_kvq, const OptTensor& b
     RGN_DEVICE_GUARD(x);
     check_act(x, w_kvq, q_out, w_scale, b_kvq);
     rgn_qkv_epilogue e = epi(x, norm_q, norm_k, cos_q, sin_q, cos_k, sin_k, kv_rows, k_cache, vt_cache, heads, row_base, eps, fp16_roundtrip);
-    const int gelu = (int)(gelu_from_col < 0 ? 3 * heads * 128 : gelu_from_col);
-    Tensor ws = gemm_ws(x);
-    const int M = (int)x.size(0), N = (int)w_kvq.size(0), K = (int)x.size(1);
-    if (is_fp8(w_kvq))
-        check_rc(rgn_gemm_w8_qkv(ptr(x), (int)x.stride(0), ptr(w_kvq), (int)w_kvq.stride(0), (const float*)ptr(w_scale), ptr(b_kvq),
-                                 q_out.data_ptr(), (int)q_out.stride(0), M, N, K, gelu, &e, ws.data_ptr(), (size_t)ws.numel() * 4,
-                                 stream_of(x)), "rgn_gemm_w8_qkv");
-    else
-        check_rc(rgn_gemm_bf16_qkv(ptr(x), (int)x.stride(0), ptr(w_kvq), (int)w_kvq.stride(0), ptr(b_kvq), q_out.data_ptr(),
-                                   (int)q_out.stride(0), M, N, K, gelu, &e, ws.data_ptr(), (size_t)ws.numel() * 4, stream_of(x)),
-                 "rgn_gemm_bf16_qkv");
+    launch_qkv({problem(x, w_kvq, w_scale, b_kvq, q_out, &e)}, w_kvq, gelu_from_col < 0 ? 3 * heads * 128 : gelu_from_col, x);
 }
 
 // both streams of a double-stream block in one launch: image rows sit behind the `txt_len` text rows of the shared [text ; image]
@@ -289,19 +299,7 @@ void kv_partial_update_pair_(const Tensor& x_img, const Tensor& w_img, const Opt
                 "pair: equal [N, K], contiguous weights of one format");
     rgn_qkv_epilogue e0 = epi(x_img, norm_q_img, norm_k_img, cos_q, sin_q, cos_k, sin_k, kv_rows, k_cache, vt_cache, heads, txt_len, eps, fp16_roundtrip);
     rgn_qkv_epilogue e1 = epi(x_txt, norm_q_txt, norm_k_txt, cos_q, sin_q, cos_k, sin_k, kv_rows, k_cache, vt_cache, heads, 0, eps, false);
-    Tensor ws = gemm_ws(x_img);
-    const int N = (int)w_img.size(0), K = (int)w_img.size(1);
-    if (is_fp8(w_img))
-        check_rc(rgn_gemm_w8_qkv_pair(ptr(x_img), (int)x_img.stride(0), ptr(w_img), (const float*)ptr(w_scale_img), ptr(b_img),
-                                      out_img.data_ptr(), (int)out_img.stride(0), (int)x_img.size(0), &e0, ptr(x_txt), (int)x_txt.stride(0),
-                                      ptr(w_txt), (const float*)ptr(w_scale_txt), ptr(b_txt), out_txt.data_ptr(), (int)out_txt.stride(0),
-                                      (int)x_txt.size(0), &e1, N, K, ws.data_ptr(), (size_t)ws.numel() * 4, stream_of(x_img)),
-                 "rgn_gemm_w8_qkv_pair");
-    else
-        check_rc(rgn_gemm_bf16_qkv_pair(ptr(x_img), (int)x_img.stride(0), ptr(w_img), ptr(b_img), out_img.data_ptr(), (int)out_img.stride(0),
-                                        (int)x_img.size(0), &e0, ptr(x_txt), (int)x_txt.stride(0), ptr(w_txt), ptr(b_txt), out_txt.data_ptr(),
-                                        (int)out_txt.stride(0), (int)x_txt.size(0), &e1, N, K, ws.data_ptr(), (size_t)ws.numel() * 4,
-                                        stream_of(x_img)), "rgn_gemm_bf16_qkv_pair");
+    launch_qkv({problem(x_img, w_img, w_scale_img, b_img, out_img, &e0), problem(x_txt, w_txt, w_scale_txt, b_txt, out_txt, &e1)}, w_img, 0, x_img);
 }
 
 // the projections of up to four (stream, CFG branch) problems in ONE launch: per problem its activations, weights (shared between
@@ -328,18 +326,9 @@ void kv_partial_update_group_(at::TensorList x, at::TensorList w_kvq, const c10:
                     "group: equal [N, K], contiguous weights of one format");
         es[i] = epi(x[i], norm_q[i], norm_k[i], cos_q[i], sin_q[i], cos_k[i], sin_k[i], kv_rows.get(i), k_cache[i], vt_cache[i], heads, row_base[i],
                     eps, !fp16_roundtrip.empty() && fp16_roundtrip[i] != 0);
-        if (x[i].size(0) == 0) continue;
-        rgn_gemm_problem p;
-        p.A = ptr(x[i]); p.W = ptr(w_kvq[i]); p.wscale = (const float*)ptr(sc); p.bias = ptr(OptTensor(b_kvq.get(i)));
-        p.C = q_out[i].data_ptr(); p.gate = nullptr; p.resid = nullptr; p.qkv = &es[i];
-        p.lda = (int)x[i].stride(0); p.ldc = (int)q_out[i].stride(0); p.M = (int)x[i].size(0);
-        ps.push_back(p);
+        ps.push_back(problem(x[i], w_kvq[i], sc, OptTensor(b_kvq.get(i)), q_out[i], &es[i]));
     }
-    if (ps.empty()) return;
-    Tensor ws = gemm_ws(x[0]);
-    check_rc(rgn_gemm_group(ps.data(), (int)ps.size(), (int)w_kvq[0].size(0), (int)w_kvq[0].size(1), RGN_EPI_QKV,
-                            (int)(gelu_from_col < 0 ? 0 : gelu_from_col), ws.data_ptr(), (size_t)ws.numel() * 4, stream_of(x[0])),
-             "rgn_gemm_group");
+    launch_qkv(std::move(ps), w_kvq[0], gelu_from_col < 0 ? 0 : gelu_from_col, x[0]);
 }
 
 void region_attention(const Tensor& q, const Tensor& k_cache, const Tensor& vt_cache, Tensor out, int64_t skv, int64_t heads, double scale,

@@ -1,5 +1,5 @@
 // Vision tower of the Qwen2.5-VL prompt encoder ([EXT] transformers Qwen2_5_VisionTransformerPretrainedModel; SURVEY.md section 8 row f4:
-// `encode_prompt` of Qwen-Image-Edit runs it over the condition images).  Every projection, the patch embedding included, is rgn_gemm_bf16,
+// `encode_prompt` of Qwen-Image-Edit runs it over the condition images).  Every projection, the patch embedding included, is rgn_gemm_group,
 // the norms are rgn_rms_norm_rows, the MLP product is rgn_swiglu_bf16; this file holds what the tower adds around them:
 //   vision_attention_kernel   non-causal self-attention over packed segments (windows, or one segment per image), read straight from the
 //                             fused QKV GEMM output [L, 3 H Dp] -> O [L, H Dp] on the tile core of attn_tile.h.  Dp = the head width

@@ -773,7 +773,7 @@ class FluxTransformer2DModel:
         """Store the trunk's block GEMM weights (QKV(+MLP), out, FeedForward, proj_out of every block: > 99 % of the
         parameters) as OCP e4m3fn with one fp32 scale per output channel (ops.quantize_w8).  Activations, biases, norms,
         embedders and the AdaLN table stay bf16.  The GEMMs then read half the weight bytes; arithmetic is bf16 MFMA on the
-        exactly converted values, the scale multiplies the fp32 accumulator (rgn_gemm_w8*).  Row slices of a quantised
+        exactly converted values, the scale multiplies the fp32 accumulator (rgn_gemm_group with wscale).  Row slices of a quantised
         weight (the last block's row skipping) go through ops.wrows, which slices the scales with it."""
         def q(obj, name):
             w = getattr(obj, name, None)

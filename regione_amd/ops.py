@@ -6,6 +6,7 @@ synchronise except where a host-visible count is explicitly requested.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Optional, Tuple
 
@@ -14,7 +15,7 @@ import torch
 from . import _lib
 
 F32, BF16 = 0, 1
-EPI_BIAS, EPI_GELU, EPI_GATE_RESID = 0, 1, 2
+EPI_BIAS, EPI_GELU, EPI_GATE_RESID, EPI_QKV = 0, 1, 2, 3
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -233,52 +234,62 @@ def _wscale(W: torch.Tensor) -> Optional[torch.Tensor]:
     return s
 
 
+class Problem:
+    """One problem of a GEMM launch: out[r] = epilogue(A @ W^T + bias) with its own gate / residual, Q/K/V epilogue or row scatter."""
+    __slots__ = ("A", "W", "bias", "out", "gate", "resid", "epi", "out_rows")
+
+    def __init__(self, A, W, bias, out, gate=None, resid=None, epi=None, out_rows=None):
+        self.A, self.W, self.bias, self.out, self.gate, self.resid, self.epi, self.out_rows = A, W, bias, out, gate, resid, epi, out_rows
+
+
+def _launch(problems, epilogue: int, gelu_from_col: int):
+    """The one way from here to the GEMM kernel (rgn_gemm_group): drops the empty problems, fills one descriptor per problem - the W row
+    stride from the tensor, the fp8 scale from the weight - borrows the stream's workspace and launches."""
+    probs = [p for p in problems if p.A.shape[0] > 0]
+    if not probs:
+        return
+    assert len(probs) <= 4
+    N, K = probs[0].W.shape
+    arr = (_lib.GemmProblem * len(probs))(*[
+        _lib.GemmProblem(_p(p.A), _p(p.W), _p(_wscale(p.W)), _p(p.bias), _p(p.out), _p(p.gate), _p(p.resid),
+                         ctypes.pointer(p.epi) if p.epi is not None else None, _p(p.out_rows), p.A.stride(0), p.out.stride(0),
+                         p.A.shape[0], p.W.stride(0)) for p in probs])
+    ws = gemm_workspace(probs[0].A.device)
+    rc = _lib.lib().rgn_gemm_group(arr, len(probs), N, K, epilogue, gelu_from_col, _p(ws), ws.numel() * 4, _stream())
+    _lib.check(rc, "rgn_gemm_group")
+
+
+def _check_single(A, W, out):
+    assert A.dtype == out.dtype == torch.bfloat16 and W.dtype in (torch.bfloat16, FP8)
+    K, N = A.shape[1], W.shape[0]
+    assert A.stride(1) == 1 and W.stride(1) == 1 and out.stride(1) == 1 and W.shape[1] == K and out.shape[1] == N
+
+
+def _check_pair(A0, W0, out0, A1, W1, out1):
+    N, K = W0.shape
+    assert W1.shape == (N, K) and W0.is_contiguous() and W1.is_contiguous()
+    assert A0.shape[1] == K and A1.shape[1] == K and out0.shape[1] == N and out1.shape[1] == N
+    for t in (A0, A1, out0, out1):
+        assert t.stride(1) == 1 and t.dtype == torch.bfloat16
+
+
 def gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, *, epilogue: int = EPI_BIAS,
          gelu_from_col: int = 0, gate: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
          out_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out[r] = epilogue(A @ W^T + bias).  A [M,K] (row stride may exceed K), W [N,K] (bf16, or fp8 from quantize_w8), out [*,N] view."""
-    assert A.dtype == out.dtype == torch.bfloat16 and W.dtype in (torch.bfloat16, FP8)
-    M, K = A.shape
-    N = W.shape[0]
-    assert A.stride(1) == 1 and W.stride(1) == 1 and out.stride(1) == 1 and W.shape[1] == K and out.shape[1] == N
+    """out[r] = epilogue(A @ W^T + bias).  A [M,K] (row stride may exceed K), W [N,K] (bf16, or fp8 from quantize_w8; row stride may
+    exceed K), out [*,N] view; r = out_rows[m] (int64) or m."""
+    _check_single(A, W, out)
     if resid is not None:
         assert resid.stride(0) == out.stride(0) and resid.stride(1) == 1
-    ws = gemm_workspace(A.device)
-    sc = _wscale(W)
-    if sc is not None:
-        rc = _lib.lib().rgn_gemm_w8(_p(A), A.stride(0), _p(W), W.stride(0), _p(sc), _p(bias), _p(out), out.stride(0), M, N, K,
-                                    epilogue, gelu_from_col, _p(gate), _p(resid), _p(out_rows), _p(ws), ws.numel() * 4, _stream())
-        _lib.check(rc, "rgn_gemm_w8")
-        return out
-    rc = _lib.lib().rgn_gemm_bf16(_p(A), A.stride(0), _p(W), W.stride(0), _p(bias), _p(out), out.stride(0), M, N, K,
-                                  epilogue, gelu_from_col, _p(gate), _p(resid), _p(out_rows), _p(ws), ws.numel() * 4,
-                                  _stream())
-    _lib.check(rc, "rgn_gemm_bf16")
+    _launch((Problem(A, W, bias, out, gate, resid, None, out_rows),), epilogue, gelu_from_col)
     return out
 
 
 def gemm_pair(A0, W0, b0, out0, A1, W1, b1, out1, *, epilogue: int = EPI_BIAS, gelu_from_col: int = 0,
               gate0=None, resid0=None, gate1=None, resid1=None):
     """Two GEMMs with equal (N, K) and epilogue in one launch: outI = epilogue(AI @ WI^T + bI)."""
-    N, K = W0.shape
-    assert W1.shape == (N, K) and W0.is_contiguous() and W1.is_contiguous()
-    assert A0.shape[1] == K and A1.shape[1] == K and out0.shape[1] == N and out1.shape[1] == N
-    for t in (A0, A1, out0, out1):
-        assert t.stride(1) == 1 and t.dtype == torch.bfloat16
-    ws = gemm_workspace(A0.device)
-    s0, s1 = _wscale(W0), _wscale(W1)
-    if s0 is not None or s1 is not None:
-        rc = _lib.lib().rgn_gemm_w8_pair(_p(A0), A0.stride(0), _p(W0), _p(s0), _p(b0), _p(out0), out0.stride(0), A0.shape[0],
-                                         _p(gate0), _p(resid0), _p(A1), A1.stride(0), _p(W1), _p(s1), _p(b1), _p(out1),
-                                         out1.stride(0), A1.shape[0], _p(gate1), _p(resid1), N, K, epilogue, gelu_from_col,
-                                         _p(ws), ws.numel() * 4, _stream())
-        _lib.check(rc, "rgn_gemm_w8_pair")
-        return
-    rc = _lib.lib().rgn_gemm_bf16_pair(_p(A0), A0.stride(0), _p(W0), _p(b0), _p(out0), out0.stride(0), A0.shape[0],
-                                       _p(gate0), _p(resid0), _p(A1), A1.stride(0), _p(W1), _p(b1), _p(out1),
-                                       out1.stride(0), A1.shape[0], _p(gate1), _p(resid1), N, K, epilogue,
-                                       gelu_from_col, _p(ws), ws.numel() * 4, _stream())
-    _lib.check(rc, "rgn_gemm_bf16_pair")
+    _check_pair(A0, W0, out0, A1, W1, out1)
+    _launch((Problem(A0, W0, b0, out0, gate0, resid0), Problem(A1, W1, b1, out1, gate1, resid1)), epilogue, gelu_from_col)
 
 
 def _check_bias(bias, N: int, dev, what: str):
@@ -329,81 +340,36 @@ def qkv_epilogue(*, wq, wk, rope_q, rope_k, k_slab, vt_slab, H: int, k_col: int,
 def gemm_qkv(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, epi, *,
              gelu_from_col: Optional[int] = None) -> torch.Tensor:
     """QKV (+ fused MLP half) projection whose epilogue normalises / rotates Q and K, places K and V^T in the
-    cache slabs and leaves Q (and GELU(mlp)) in `out`: rgn_gemm_bf16 + rgn_qk_norm_rope_store in one launch."""
-    assert A.dtype == out.dtype == torch.bfloat16 and W.dtype in (torch.bfloat16, FP8)
-    M, K = A.shape
-    N = W.shape[0]
-    assert A.stride(1) == 1 and W.stride(1) == 1 and out.stride(1) == 1 and W.shape[1] == K and out.shape[1] == N
-    _check_bias(bias, N, A.device, "gemm_qkv")
-    ws = gemm_workspace(A.device)
-    sc = _wscale(W)
-    if sc is not None:
-        rc = _lib.lib().rgn_gemm_w8_qkv(_p(A), A.stride(0), _p(W), W.stride(0), _p(sc), _p(bias), _p(out), out.stride(0), M, N, K,
-                                        N if gelu_from_col is None else gelu_from_col, epi, _p(ws), ws.numel() * 4, _stream())
-        _lib.check(rc, "rgn_gemm_w8_qkv")
-        return out
-    rc = _lib.lib().rgn_gemm_bf16_qkv(_p(A), A.stride(0), _p(W), W.stride(0), _p(bias), _p(out), out.stride(0), M, N, K,
-                                      N if gelu_from_col is None else gelu_from_col, epi, _p(ws), ws.numel() * 4, _stream())
-    _lib.check(rc, "rgn_gemm_bf16_qkv")
+    cache slabs and leaves Q (and GELU(mlp)) in `out`: the plain projection + rgn_qk_norm_rope_store in one launch."""
+    _check_single(A, W, out)
+    _check_bias(bias, W.shape[0], A.device, "gemm_qkv")
+    _launch((Problem(A, W, bias, out, epi=epi),), EPI_QKV, W.shape[0] if gelu_from_col is None else gelu_from_col)
     return out
 
 
 def gemm_qkv_pair(A0, W0, b0, out0, epi0, A1, W1, b1, out1, epi1):
     """Both streams of a double block (image + text QKV projections) in one launch, fused Q/K/V epilogue."""
-    N, K = W0.shape
-    assert W1.shape == (N, K) and W0.is_contiguous() and W1.is_contiguous()
-    assert A0.shape[1] == K and A1.shape[1] == K and out0.shape[1] == N and out1.shape[1] == N
-    for t in (A0, A1, out0, out1):
-        assert t.stride(1) == 1 and t.dtype == torch.bfloat16
-    _check_bias(b0, N, A0.device, "gemm_qkv_pair")
-    _check_bias(b1, N, A0.device, "gemm_qkv_pair")
-    ws = gemm_workspace(A0.device)
-    s0, s1 = _wscale(W0), _wscale(W1)
-    if s0 is not None or s1 is not None:
-        rc = _lib.lib().rgn_gemm_w8_qkv_pair(_p(A0), A0.stride(0), _p(W0), _p(s0), _p(b0), _p(out0), out0.stride(0), A0.shape[0],
-                                             epi0, _p(A1), A1.stride(0), _p(W1), _p(s1), _p(b1), _p(out1), out1.stride(0),
-                                             A1.shape[0], epi1, N, K, _p(ws), ws.numel() * 4, _stream())
-        _lib.check(rc, "rgn_gemm_w8_qkv_pair")
-        return
-    rc = _lib.lib().rgn_gemm_bf16_qkv_pair(_p(A0), A0.stride(0), _p(W0), _p(b0), _p(out0), out0.stride(0), A0.shape[0], epi0,
-                                           _p(A1), A1.stride(0), _p(W1), _p(b1), _p(out1), out1.stride(0), A1.shape[0], epi1,
-                                           N, K, _p(ws), ws.numel() * 4, _stream())
-    _lib.check(rc, "rgn_gemm_bf16_qkv_pair")
-
-
-class Problem:
-    """One problem of `gemm_group`: out = epilogue(A @ W^T + bias) with its own gate / residual or Q/K/V epilogue."""
-    __slots__ = ("A", "W", "bias", "out", "gate", "resid", "epi")
-
-    def __init__(self, A, W, bias, out, gate=None, resid=None, epi=None):
-        self.A, self.W, self.bias, self.out, self.gate, self.resid, self.epi = A, W, bias, out, gate, resid, epi
+    _check_pair(A0, W0, out0, A1, W1, out1)
+    _check_bias(b0, W0.shape[0], A0.device, "gemm_qkv_pair")
+    _check_bias(b1, W0.shape[0], A0.device, "gemm_qkv_pair")
+    _launch((Problem(A0, W0, b0, out0, epi=epi0), Problem(A1, W1, b1, out1, epi=epi1)), EPI_QKV, W0.shape[0])
 
 
 def gemm_group(problems, *, epilogue: int = EPI_BIAS, gelu_from_col: int = 0):
-    """Up to four GEMMs with equal (N, K), epilogue and weight format in ONE launch (rgn_gemm_group): the text / image
-    streams of a double block x the cond / uncond CFG branches.  Problems may share W."""
-    import ctypes as C
+    """Up to four GEMMs with equal (N, K), epilogue and weight format in ONE launch: the text / image streams of a double
+    block x the cond / uncond CFG branches.  Problems may share W."""
     probs = [p for p in problems if p.A.shape[0] > 0]
     if not probs:
         return
-    assert len(probs) <= 4
     N, K = probs[0].W.shape
-    arr = (_lib.GemmProblem * len(probs))()
-    for i, p in enumerate(probs):
+    for p in probs:
         assert p.W.shape == (N, K) and p.W.is_contiguous() and p.A.shape[1] == K and p.out.shape == (p.A.shape[0], N)
         for t in (p.A, p.out):
             assert t.stride(1) == 1 and t.dtype == torch.bfloat16
         if p.resid is not None:
             assert p.resid.stride(0) == p.out.stride(0) and p.resid.stride(1) == 1
         _check_bias(p.bias, N, p.A.device, "gemm_group")
-        g = arr[i]
-        g.A, g.W, g.wscale, g.bias, g.C = _p(p.A), _p(p.W), _p(_wscale(p.W)), _p(p.bias), _p(p.out)
-        g.gate, g.resid = _p(p.gate), _p(p.resid)
-        g.qkv = C.pointer(p.epi) if p.epi is not None else None
-        g.lda, g.ldc, g.M = p.A.stride(0), p.out.stride(0), p.A.shape[0]
-    ws = gemm_workspace(probs[0].A.device)
-    rc = _lib.lib().rgn_gemm_group(arr, len(probs), N, K, epilogue, gelu_from_col, _p(ws), ws.numel() * 4, _stream())
-    _lib.check(rc, "rgn_gemm_group")
+    _launch(probs, epilogue, gelu_from_col)
 
 
 def gemv(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], silu_input: bool = False,

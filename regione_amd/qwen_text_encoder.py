@@ -5,7 +5,7 @@
 `hidden_states[-1]`.  The decoder stack is restated here on the library's kernels, rounding where the eager bf16 module rounds:
 
   layer   n = rms_norm_rows(h)                       Qwen2_5_VLRMSNorm (fp32 variance, w * bf16(x * rsqrt))
-          qkv = n @ [q; k; v]^T + [bq; bk; bv]       one rgn_gemm_bf16 over the concatenated weight: [L, (Hq + 2 Hkv) 128]
+          qkv = n @ [q; k; v]^T + [bq; bk; bv]       one rgn_gemm_group over the concatenated weight: [L, (Hq + 2 Hkv) 128]
           mrope(qkv, cos, sin)                       apply_multimodal_rotary_pos_emb on the q and k columns, in place
           a = lm_attention(qkv)                      causal, grouped-query (query head h reads KV head h / (Hq / Hkv)), scale 1/sqrt(128)
           h = h + a @ o^T                            RGN_EPI_GATE_RESID with a gate of ones = torch's bf16 `h + linear(a)`

@@ -4,7 +4,7 @@
 the condition images' patches.  The tower is restated here on the library's kernels, rounding where the eager bf16 module rounds:
 
   patches x = cast_pad_rows(pixel_values)            `.to(bfloat16)`, K = C * 2 * p * p padded with zero columns to a multiple of 64
-          h = x @ patch^T                            the Conv3d with stride = kernel as ONE rgn_gemm_bf16; `out_rows` writes each patch at its
+          h = x @ patch^T                            the Conv3d with stride = kernel as ONE rgn_gemm_group; `out_rows` writes each patch at its
                                                      place in the window order (the module's `hidden_states[window_index]`)
   block   n = rms_norm_rows(h)                       Qwen2_5_VLRMSNorm
           qkv = n @ qkv^T + b                        one GEMM: [L, 3 H Dp], all q heads | all k heads | all v heads, head width padded to Dp

@@ -5,7 +5,7 @@
 Both are restated here on the library's kernels, rounding where the eager bf16 modules round:
 
   T5 layer   n = rms_norm_rows(h)                   T5LayerNorm (fp32 variance, bf16(x * rsqrt) * w)
-             qkv = n @ [q; k; v]^T                  one rgn_gemm_bf16 over the concatenated weight
+             qkv = n @ [q; k; v]^T                  one rgn_gemm_group over the concatenated weight
              a = text_attention(qkv, bias table)    scale 1, the relative-position bias of block 0 shared by every layer
              h = h + a @ o^T                        RGN_EPI_GATE_RESID with a gate of ones = torch's bf16 `h + linear(a)`
              ff = n2 @ [wi_1; wi_0]^T               RGN_EPI_GELU from column d_ff: the linear half, then gelu_new(wi_0 n2)

@@ -20,7 +20,7 @@ def declared_symbols():
 def test_header_declares_expected_surface():
     syms = declared_symbols()
     for s in ("rgn_arp_partition", "rgn_gather_rows", "rgn_scatter_rows", "rgn_euler_step", "rgn_avd_apply",
-              "rgn_gemm_bf16", "rgn_attention", "rgn_qk_norm_rope_store", "rgn_ln_modulate"):
+              "rgn_gemm_group", "rgn_attention", "rgn_qk_norm_rope_store", "rgn_ln_modulate"):
         assert s in syms
 
 
@@ -56,17 +56,35 @@ def test_argument_validation_returns_codes_and_messages_without_touching_the_gpu
 
     def msg():
         return h.rgn_last_error().decode()
-    # GEMM: K must be a multiple of 64, strides multiples of 8, pointers 16-byte aligned, gate/resid for epilogue 2
-    assert h.rgn_gemm_bf16(P, 96, P, 96, None, P, 64, 8, 64, 96, 0, 0, None, None, None, None, 0, None) < 0 and "multiple of 64" in msg()
-    assert h.rgn_gemm_bf16(P, 68, P, 64, None, P, 64, 8, 64, 64, 0, 0, None, None, None, None, 0, None) < 0 and "strides" in msg()
-    assert h.rgn_gemm_bf16(P + 2, 64, P, 64, None, P, 64, 8, 64, 64, 0, 0, None, None, None, None, 0, None) < 0 and "aligned" in msg()
-    assert h.rgn_gemm_bf16(P, 64, P, 64, None, P, 64, 8, 64, 64, 2, 0, None, None, None, None, 0, None) < 0 and "gate" in msg()
-    assert h.rgn_gemm_bf16(None, 64, P, 64, None, P, 64, 8, 64, 64, 0, 0, None, None, None, None, 0, None) < 0
-    assert h.rgn_gemm_bf16(P, 64, P, 64, None, P, 64, 0, 64, 64, 0, 0, None, None, None, None, 0, None) == 0      # M = 0: nothing to do
+    # GEMM (one descriptor per problem): K must be a multiple of 64, strides multiples of 8, pointers 16-byte aligned, gate/resid for
+    # epilogue 2
+    def prob(A=P, W=P, C=P, lda=64, ldc=64, M=8, ldw=0, wscale=None, qkv=None, out_rows=None):
+        return _lib.GemmProblem(A, W, wscale, None, C, None, None, ctypes.pointer(qkv) if qkv is not None else None, out_rows, lda, ldc, M, ldw)
+
+    def group(probs, N=64, K=64, epilogue=0, gelu_from_col=0, nprob=None):
+        arr = (_lib.GemmProblem * max(len(probs), 1))(*probs)
+        return h.rgn_gemm_group(arr, len(probs) if nprob is None else nprob, N, K, epilogue, gelu_from_col, None, 0, None)
+    assert group([prob(lda=96, ldw=96)], K=96) < 0 and "multiple of 64" in msg()
+    assert group([prob(lda=68, ldw=64)]) < 0 and "strides" in msg()
+    assert group([prob(ldw=68)]) < 0 and "strides" in msg()
+    assert group([prob(A=P + 2)]) < 0 and "aligned" in msg()
+    assert group([prob()], epilogue=2) < 0 and "gate" in msg()
+    assert group([prob(A=None)]) < 0
+    assert group([prob(M=0)]) == 0                                                                     # M = 0: nothing to do
+    assert group([prob(A=None, M=0), prob(M=0)]) == 0                                                   # every problem empty
     # fused QKV epilogue: descriptor required, column blocks 256-aligned
-    assert h.rgn_gemm_bf16_qkv(P, 64, P, 64, None, P, 768, 8, 768, 64, 768, None, None, 0, None) < 0 and "rgn_qkv_epilogue" in msg()
+    assert group([prob(ldc=768)], N=768, epilogue=3, gelu_from_col=768) < 0 and "rgn_qkv_epilogue" in msg()
     e = _lib.QkvEpilogue(P, P, P, P, P, P, None, P, P, 0, 64, 0, 128, 512, 2, 1e-6)      # v_col = 128: not 256-aligned
-    assert h.rgn_gemm_bf16_qkv(P, 64, P, 64, None, P, 768, 8, 768, 64, 768, e, None, 0, None) < 0 and "256-aligned" in msg()
+    assert group([prob(ldc=768, qkv=e)], N=768, epilogue=3, gelu_from_col=768) < 0 and "256-aligned" in msg()
+    # a row scatter or a strided W only in a launch of exactly one non-empty problem; one weight format per call; 1..4 problems
+    assert group([prob(out_rows=P), prob(out_rows=P)]) == -2 and "out_rows" in msg()
+    assert group([prob(out_rows=P), prob()]) == -2 and "out_rows" in msg()
+    assert group([prob(ldw=128), prob(ldw=128)]) == -2 and "ldw" in msg()
+    assert group([prob(wscale=P), prob()]) == -2 and "same format" in msg()
+    assert group([prob(wscale=P, ldw=72)]) < 0 and "16-byte aligned" in msg()                           # fp8: ldw in bytes, a multiple of 16
+    assert group([prob()], nprob=0) < 0 and "1..4" in msg()
+    assert group([prob()] * 5) < 0 and "1..4" in msg()
+    assert h.rgn_gemm_group(None, 1, 64, 64, 0, 0, None, 0, None) < 0
     # attention / row kernels
     assert h.rgn_attention(None, 0, P, P, 64, P, 0, 8, 8, 2, 0.1, None, 0, None) < 0
     assert h.rgn_qk_norm_rope_store(P, 12, 0, 0, 0, 8, 2, 0, None, None, P, P, 1e-6, P, P, P, P, None, P, P, 64, None) < 0

@@ -337,7 +337,7 @@ def _qkv_case(M, H, K, mlp, gen, kv_rows=None, skv=None, row_base=0):
 @pytest.mark.parametrize("M,H,K,mlp,gather,row_base", [(600, 2, 256, 1024, False, 0), (333, 2, 256, 0, True, 0),
                                                        (512, 4, 512, 2048, False, 16), (200, 2, 256, 0, True, 24)])
 def test_gemm_qkv_fused_epilogue_bit_identical_to_separate_kernels(M, H, K, mlp, gather, row_base, variant):
-    """rgn_gemm_bf16_qkv == rgn_gemm_bf16 followed by rgn_qk_norm_rope_store, bit for bit: Q (in place), the
+    """RGN_EPI_QKV == RGN_EPI_BIAS followed by rgn_qk_norm_rope_store, bit for bit: Q (in place), the
     GELU(mlp) columns, the K slab and the V^T slab - identity rows, gathered cache rows (region step) and a
     problem that starts at a joint-sequence offset that is / is not a multiple of 16."""
     from regione_amd import ops
@@ -513,7 +513,7 @@ def test_gemm_hand_scheduled_loop_bit_identical_to_compiler_scheduled(M, N, K, e
 @pytest.mark.parametrize("M,N,K,epi,variant", [(8704, 3072, 3072, "bias", "256c"), (1536, 21504, 3072, "gelu", "256c"), (700, 3072, 15360, "gate", "256c"),
                                                (513, 520, 128, "bias", "128"), (300, 704, 256, "gate", "128"), (2000, 1000, 320, "bias", "256c")])
 def test_gemm_fp8_weights_per_channel_scale(M, N, K, epi, variant):
-    """rgn_gemm_w8: W stored as OCP e4m3fn + one fp32 scale per output channel.  Reference = the same GEMM on the
+    """fp8 weights: W stored as OCP e4m3fn + one fp32 scale per output channel.  Reference = the same GEMM on the
     DEQUANTISED weights in fp32 (the conversion fp8 -> bf16 in the kernel is exact; the scale multiplies the fp32
     accumulator): the result must agree to bf16 output rounding - tolerance 2^-8 relative + accumulation noise, like the
     bf16 kernel against its fp32 reference."""

@@ -190,7 +190,7 @@ def test_attention_random_shapes(seed):
 
 @pytest.mark.parametrize("seed", range(8))
 def test_gemm_fused_qkv_epilogue_random_shapes_bit_identical_to_separate_kernels(seed):
-    """rgn_gemm_bf16_qkv == rgn_gemm_bf16 + rgn_qk_norm_rope_store bit for bit at random row counts, head counts, K, MLP widths,
+    """RGN_EPI_QKV == RGN_EPI_BIAS + rgn_qk_norm_rope_store bit for bit at random row counts, head counts, K, MLP widths,
     identity / gathered cache rows and joint-sequence offsets (any residue mod 16: the V^T store has an aligned fast path)."""
     import numpy as np
     from regione_amd import ops
