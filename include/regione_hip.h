@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 110
+#define RGN_ABI_VERSION 111
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -435,6 +435,36 @@ int rgn_mrope_bf16(void* QKV, int ld, const void* cos, const void* sin, int L, i
  * `self.act_fn(self.gate_proj(x)) * self.up_proj(x)` of Qwen2MLP.forward with its two roundings.
  * F % 8 == 0, ldx >= 2 F, ldy >= F (strides multiples of 8), x and y 16-byte aligned. */
 int rgn_swiglu_bf16(const void* x, int ldx, void* y, int ldy, int M, int F, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * f4  greedy decode of that language model (`generate`, one new token per step against a KV cache; csrc/decode.hip).  The row kernels
+ * above run at M = 1 (rgn_rms_norm_rows, rgn_mrope_bf16 with a one-row table, rgn_swiglu_bf16, rgn_text_embed reading the id from device
+ * memory); these are the pieces a one-row step needs besides.  No atomics, fixed reduction orders: a repeated call is bit-identical.
+ *
+ * One-row linear layer: y[n] = bf16(sum_k W[n,k] x[k] + bias[n]); with resid != NULL y[n] = bf16(bf16(sum + bias) + resid[n]), the two
+ * roundings of torch's `h + linear(a)` (what RGN_EPI_GATE_RESID with a gate of ones gives the prefill); y may be resid.  bf16 in, fp32
+ * accumulation in a fixed order; W [N, K] row-major and dense, W and x 16-byte aligned, K % 64 == 0; bias may be NULL.  Weights go from
+ * global memory straight to registers (8 16-byte loads per lane in flight); HBM-bound on W. */
+int rgn_lm_gemv_bf16(const void* W, const void* x, const void* bias, const void* resid, void* y, int N, int K, void* stream);
+/* cache[row0 + i, :] = QKV[i, Hq 128 : (Hq + 2 Hkv) 128] for i < L: the k | v columns of packed QKV rows (after rgn_mrope_bf16) into a
+ * cache [cap, 2 Hkv 128] bf16, bit for bit.  ld = row stride of QKV in elements; 0 <= row0, row0 + L <= cap <= 4096; QKV and cache 16-byte
+ * aligned.  The prefill appends its L rows, a decode step one. */
+int rgn_lm_kv_append_bf16(const void* QKV, int ld, void* cache, int cap, int row0, int L, int Hq, int Hkv, void* stream);
+/* One query token against the first n rows of that cache: O[h] = softmax_{j < n}(scale * q_h . k_{j,kv(h)}) v_{j,kv(h)}, kv(h) = h / (Hq / Hkv).
+ * q: bf16 [Hq 128] (the q columns of the token's QKV row), O: bf16 [Hq 128].  One wave takes one KV head and 64 keys for all Hq / Hkv
+ * query heads of the group; scores, softmax and O in fp32; partials (m, l, o[128]) per (head, slice) go to `workspace` and a second
+ * kernel folds them in slice order.  Cache rows >= n are never read.  1 <= n <= 4096, Hq % Hkv == 0, Hq / Hkv <= 8, 0 < scale < inf;
+ * q, cache, O, workspace 16-byte aligned; workspace_bytes >= rgn_lm_decode_attention_workspace_bytes(Hq, n). */
+int rgn_lm_decode_attention_bf16(const void* q, const void* cache, void* O, int n, int Hq, int Hkv, float scale, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+size_t rgn_lm_decode_attention_workspace_bytes(int Hq, int n);
+/* Greedy pick over the vocabulary: z[v] = sum_k W[v,k] x[k] in fp32 (never rounded to bf16: rounding first turns near-ties into ties),
+ * token_out[0] = argmax_v z[v] as int64 in device memory, the LOWEST index among equal values.  Per-block (value, index) pairs in
+ * `workspace`, then one finalize block.  logits_out != NULL also receives all of z (fp32 [V]).  W [V, K] bf16 dense, W and x 16-byte
+ * aligned, K % 64 == 0, token_out 8-byte aligned; workspace_bytes >= rgn_lm_head_workspace_bytes(V). */
+int rgn_lm_head_argmax(const void* W, const void* x, int V, int K, void* token_out, float* logits_out, void* workspace,
+                       size_t workspace_bytes, void* stream);
+size_t rgn_lm_head_workspace_bytes(int V);
 
 /* ------------------------------------------------------------------------------------------
  * f4  vision tower of the Qwen2.5-VL prompt encoder ([EXT] transformers Qwen2_5_VisionTransformerPretrainedModel: `get_image_features`

@@ -113,6 +113,13 @@ SIGNATURES = {
     "rgn_lm_attention_bf16": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p],
     "rgn_mrope_bf16": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
     "rgn_swiglu_bf16": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
+    # f4: greedy decode of that language model (csrc/decode.hip)
+    "rgn_lm_gemv_bf16": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p],
+    "rgn_lm_kv_append_bf16": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p],
+    "rgn_lm_decode_attention_bf16": [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p, C.c_size_t, _c_void_p],
+    "rgn_lm_decode_attention_workspace_bytes": [_c_int, _c_int],
+    "rgn_lm_head_argmax": [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, C.c_size_t, _c_void_p],
+    "rgn_lm_head_workspace_bytes": [_c_int],
     # f4: vision tower of the Qwen2.5-VL prompt encoder (csrc/vision.hip)
     "rgn_vision_attention_bf16": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p, _c_int, _c_void_p],
     "rgn_vision_rope_bf16": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p],
@@ -121,7 +128,8 @@ SIGNATURES = {
 }
 _RESTYPE = {"rgn_last_error": C.c_char_p, "rgn_abi_struct_bytes": C.c_size_t, "rgn_attention_workspace_bytes": C.c_size_t,
             "rgn_gemm_workspace_bytes": C.c_size_t, "rgn_groupnorm_workspace_bytes": C.c_size_t,
-            "rgn_groupnorm_partial_bytes": C.c_size_t}
+            "rgn_groupnorm_partial_bytes": C.c_size_t, "rgn_lm_decode_attention_workspace_bytes": C.c_size_t,
+            "rgn_lm_head_workspace_bytes": C.c_size_t}
 
 _lib = None
 

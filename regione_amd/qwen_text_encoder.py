@@ -19,6 +19,14 @@ buffer, the `mrope_section` selection applied once, cast to bf16 and copied in o
 `vision=`, a HipQwen25VLVisionTower (regione_amd/qwen_vision.py: the tower on the same kernels; the adapter passes one), or with
 `vision=None` the host's eager module (`get_image_features`); its embeddings are placed at the image-token rows by rgn_scatter_rows.
 
+`generate` is transformers' greedy search for one sequence on the same weights (csrc/decode.hip): the prefill above with the k | v columns of
+every layer appended to a KV cache [layers][cap, 2 Hkv 128] after mRoPE (rgn_lm_kv_append_bf16) and the final norm on the last row only, then
+per new token ONE row through the stack - rgn_lm_gemv_bf16 for the four projections (bias for q|k|v, the two roundings of `h + linear(a)` for
+the residual adds), rgn_lm_decode_attention_bf16 against the cache, the row kernels at M = 1 - and rgn_lm_head_argmax over `lm_head` (fp32
+logits, the lowest index on a tie), which writes the token into the device id buffer the next rgn_text_embed reads.  New token k sits at
+max(prompt positions) + 1 + k on all three axes (`decode_position_ids`).  The loop is a `for` over `max_new_tokens`; the host reads the ids
+every `sync_every` tokens to look for EOS.
+
 There is no eager fallback inside: what the kernels do not implement raises RegionEHipError before any launch, and the adapter
 (regione_amd/adapters.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
 only; every call returns freshly allocated outputs.
@@ -36,7 +44,7 @@ _p, _stream = ops._p, ops._stream
 
 HEAD_DIM = 128
 LM = "model.language_model."
-NOT_ADOPTED = ("lm_head.", "model.visual.")
+NOT_ADOPTED = ("lm_head.", "model.visual.")                  # lm_head.weight: adopted by the first generate()
 
 
 class QwenTextEncoderOutput:
@@ -121,6 +129,35 @@ def mrope_tables(inv_freq: torch.Tensor, position_ids: torch.Tensor, mrope_secti
     return torch.stack([pick(emb.cos()), pick(emb.sin())]).to(torch.bfloat16).contiguous()
 
 
+def decode_position_ids(prompt_position_ids: torch.Tensor, n_new: int) -> torch.Tensor:
+    """[3, B, n_new] int64 on the CPU: the positions transformers gives the tokens `generate` appends.  Qwen2_5_VLModel keeps
+    `rope_deltas = max(prompt position_ids over the three axes) + 1 - L` from the prefill and uses `cache_position + rope_deltas` on every
+    axis afterwards: new token k sits at max + 1 + k."""
+    pos = prompt_position_ids.detach().cpu()
+    top = pos.amax(dim=(0, 2))                                                   # [B]
+    new = top[:, None] + 1 + torch.arange(int(n_new), dtype=pos.dtype)[None, :]
+    return new[None].expand(3, -1, -1).contiguous()
+
+
+class QwenGenerateOutput:
+    """`generate(..., return_dict_in_generate=True)`: `.sequences` [1, L + n_new] int64 and, with `output_logits=True`, `.logits`, a tuple
+    of n_new fp32 [1, V] tensors (the raw lm_head outputs the tokens were picked from); None otherwise."""
+
+    def __init__(self, sequences, logits=None):
+        self.sequences, self.logits = sequences, logits
+
+    def __getitem__(self, k):
+        return getattr(self, k)
+
+
+# arguments of transformers' generate that change WHICH token is picked: refused by name (greedy search is what the kernels implement)
+SAMPLING_ARGS = ("temperature", "top_k", "top_p", "min_p", "typical_p", "epsilon_cutoff", "eta_cutoff", "repetition_penalty",
+                 "encoder_repetition_penalty", "no_repeat_ngram_size", "length_penalty", "diversity_penalty", "penalty_alpha",
+                 "num_beam_groups", "num_return_sequences", "bad_words_ids", "force_words_ids", "suppress_tokens", "begin_suppress_tokens",
+                 "sequence_bias", "logits_processor", "stopping_criteria", "min_new_tokens", "min_length", "guidance_scale",
+                 "exponential_decay_length_penalty", "renormalize_logits", "constraints", "prefix_allowed_tokens_fn", "assistant_model")
+
+
 def valid_lengths(attention_mask: Optional[torch.Tensor], B: int, L: int, what: str = "HipQwen25VLTextEncoder"):
     """Valid length per row of a [B, L] mask that is a run of ones followed by zeros (right padding); anything else is refused."""
     if attention_mask is None:
@@ -179,7 +216,7 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         self.mrope_section = list(tc.rope_parameters["mrope_section"])
         self.image_token_id, self.video_token_id = getattr(cfg, "image_token_id", None), getattr(cfg, "video_token_id", None)
         _check_k(self.what, hidden_size=self.d, intermediate_size=self.F, attention_width=self.Hq * HEAD_DIM)
-        lm = {k: v for k, v in sd.items() if not k.startswith(NOT_ADOPTED)}           # lm_head.* / model.visual.*: known, not adopted
+        lm = {k: v for k, v in sd.items() if not k.startswith(NOT_ADOPTED)}           # lm_head.* / model.visual.*: known, not adopted here
         _check_names(self.what, lm, qwen25vl_param_shapes(cfg))
         _bf16_only(self.what, lm)
 
@@ -203,6 +240,11 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         self.inv_freq = rot.inv_freq.detach().float().cpu() if rot is not None else default_inv_freq(cfg)
         self.ones = torch.ones(self.d, dtype=torch.bfloat16, device=dev)
         self.buf = _Buffers(dev)
+        # generate(): lm_head is adopted at the first call (encode-only users do not pay for it); the KV cache is kept like the buffers
+        self._tied = bool(getattr(cfg, "tie_word_embeddings", False) or getattr(tc, "tie_word_embeddings", False))
+        self._lm_head_src = None if self._tied else sd.get("lm_head.weight")      # a reference, not a copy
+        self.lm_head = None
+        self.kv = _Buffers(dev)
 
     # ---- host-side preparation (no kernel) -----------------------------------------------------------------------------------------
     def position_ids_for(self, input_ids, attention_mask=None, image_grid_thw=None, position_ids=None, mm_token_type_ids=None):
@@ -255,7 +297,7 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             _refuse(self.what, "adopted from a state dict (no vision tower at hand): pass image_embeds instead of pixel_values")
         pos = self.position_ids_for(input_ids, attention_mask, image_grid_thw, position_ids, mm_token_type_ids)
         tables = mrope_tables(self.inv_freq, pos, self.mrope_section)
-        return ids_cpu, lengths, tables
+        return ids_cpu, lengths, tables, pos
 
     def _image_embeds(self, pixel_values, image_grid_thw, image_embeds):
         if pixel_values is not None and self.vision is not None:       # the vision tower on the HIP kernels
@@ -270,12 +312,38 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             _refuse(self.what, f"image embeddings of shape {tuple(image_embeds.shape)} (rows of width {self.d})")
         return image_embeds.to(self.device, torch.bfloat16).contiguous()
 
+    def _prefill_row(self, t, ids_row, n, cos, sin, emb=None, idx=None, cache=None):
+        """The decoder stack over one row of n valid tokens in the buffers `t`; returns (h, n-scratch) BEFORE the final norm.  With `cache`
+        ([layers, cap, 2 Hkv 128]) the k | v columns of every layer are appended as rows [0, n) after mRoPE (generate's prefill)."""
+        lib = _lib.lib()
+        h, nn, qkv, a, ff, g = (t[k][:n] for k in ("h", "n", "qkv", "a", "ff", "g"))
+        self._embed(ids_row, h)
+        if emb is not None:
+            rc = lib.rgn_scatter_rows(_p(emb), _p(idx), _p(h), emb.shape[0], self.d * 2, _stream())
+            _lib.check(rc, "rgn_scatter_rows")
+        for li, p in enumerate(self.layers):
+            self._rms(h, p["ln1"], nn)
+            ops.gemm(nn, p["wqkv"], p["bqkv"], qkv)
+            rc = lib.rgn_mrope_bf16(_p(qkv), qkv.stride(0), _p(cos), _p(sin), n, self.Hq, self.Hkv, _stream())
+            _lib.check(rc, "rgn_mrope_bf16")
+            if cache is not None:
+                rc = lib.rgn_lm_kv_append_bf16(_p(qkv), qkv.stride(0), _p(cache[li]), cache.shape[1], 0, n, self.Hq, self.Hkv, _stream())
+                _lib.check(rc, "rgn_lm_kv_append_bf16")
+            rc = lib.rgn_lm_attention_bf16(_p(qkv), _p(a), n, self.Hq, self.Hkv, float(self.scale), _stream())
+            _lib.check(rc, "rgn_lm_attention_bf16")
+            ops.gemm(a, p["wo"], None, h, epilogue=ops.EPI_GATE_RESID, gate=self.ones, resid=h)
+            self._rms(h, p["ln2"], nn)
+            ops.gemm(nn, p["wgu"], None, ff)
+            _lib.check(lib.rgn_swiglu_bf16(_p(ff), ff.stride(0), _p(g), g.stride(0), n, self.F, _stream()), "rgn_swiglu_bf16")
+            ops.gemm(g, p["wdown"], None, h, epilogue=ops.EPI_GATE_RESID, gate=self.ones, resid=h)
+        return h, nn
+
     # ---- the call --------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def __call__(self, input_ids, attention_mask=None, pixel_values=None, image_grid_thw=None, position_ids=None, mm_token_type_ids=None,
                  output_hidden_states=False, return_dict=True, image_embeds=None, **kw):
-        ids_cpu, lengths, tables = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids,
-                                                 image_embeds, kw)
+        ids_cpu, lengths, tables, _ = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids,
+                                                    image_embeds, kw)
         B, L = ids_cpu.shape
         emb = self._image_embeds(pixel_values, image_grid_thw, image_embeds)
         rows = None
@@ -295,26 +363,155 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             _lib.check(lib.rgn_fill_zero(_p(out), out.numel() * 2, _stream()), "rgn_fill_zero")
         at = 0
         for bi, n in enumerate(lengths):
-            h, nn, qkv, a, ff, g = (t[k][:n] for k in ("h", "n", "qkv", "a", "ff", "g"))
-            cos, sin = tab[0, bi], tab[1, bi]
-            self._embed(ids[bi, :n], h)
-            if rows is not None and rows[bi].numel():
-                k = rows[bi].numel()
-                rc = lib.rgn_scatter_rows(_p(emb[at:at + k]), _p(idx[at:at + k]), _p(h), k, self.d * 2, _stream())
-                _lib.check(rc, "rgn_scatter_rows")
-                at += k
-            for p in self.layers:
-                self._rms(h, p["ln1"], nn)
-                ops.gemm(nn, p["wqkv"], p["bqkv"], qkv)
-                rc = lib.rgn_mrope_bf16(_p(qkv), qkv.stride(0), _p(cos), _p(sin), n, self.Hq, self.Hkv, _stream())
-                _lib.check(rc, "rgn_mrope_bf16")
-                rc = lib.rgn_lm_attention_bf16(_p(qkv), _p(a), n, self.Hq, self.Hkv, float(self.scale), _stream())
-                _lib.check(rc, "rgn_lm_attention_bf16")
-                ops.gemm(a, p["wo"], None, h, epilogue=ops.EPI_GATE_RESID, gate=self.ones, resid=h)
-                self._rms(h, p["ln2"], nn)
-                ops.gemm(nn, p["wgu"], None, ff)
-                _lib.check(lib.rgn_swiglu_bf16(_p(ff), ff.stride(0), _p(g), g.stride(0), n, self.F, _stream()), "rgn_swiglu_bf16")
-                ops.gemm(g, p["wdown"], None, h, epilogue=ops.EPI_GATE_RESID, gate=self.ones, resid=h)
+            k = rows[bi].numel() if rows is not None else 0
+            h, nn = self._prefill_row(t, ids[bi, :n], n, tab[0, bi], tab[1, bi], emb[at:at + k] if k else None, idx[at:at + k] if k else None)
+            at += k
             self._rms(h, self.final_ln, out[bi, :n])
         res = QwenTextEncoderOutput(out, bool(output_hidden_states))
         return res if return_dict else res.to_tuple()
+
+    # ---- greedy generate: the prefill above with a KV cache, then one-row decode steps (csrc/decode.hip) -----------------------------
+    def _generate_args(self, input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw):
+        """Every refusal of `generate`, before any launch; returns the eos ids (a possibly empty list)."""
+        gc = getattr(self.module, "generation_config", None)
+        if do_sample or (do_sample is None and getattr(gc, "do_sample", False)):
+            _refuse(self.what, "do_sample: sampling is not implemented (greedy search only" +
+                    ("; the module's generation_config.do_sample is true, pass do_sample=False to decode greedily)" if not do_sample else ")"))
+        beams = kw.get("num_beams")
+        if (beams is not None and beams != 1) or (beams is None and (getattr(gc, "num_beams", 1) or 1) > 1):
+            _refuse(self.what, "num_beams > 1: beam search is not implemented (greedy search only)")
+        for k in SAMPLING_ARGS:
+            if kw.get(k) is not None:
+                _refuse(self.what, f"{k}: sampling and penalty arguments are not implemented (greedy search only)")
+        if kw.get("past_key_values") is not None:
+            _refuse(self.what, "past_key_values: generate keeps its own KV cache")
+        if kw.get("streamer") is not None:
+            _refuse(self.what, "streamer is not implemented (the tokens stay on the device between host reads)")
+        for k in ("pixel_values_videos", "video_grid_thw", "second_per_grid_ts"):
+            if kw.get(k) is not None:
+                _refuse(self.what, f"{k}: videos are not implemented")
+        known = SAMPLING_ARGS + ("num_beams", "past_key_values", "streamer", "pixel_values_videos", "video_grid_thw", "second_per_grid_ts",
+                                 "use_cache")
+        extra = sorted(k for k in kw if k not in known)
+        if extra:
+            _refuse(self.what, f"arguments {extra} are not implemented")
+        if not isinstance(input_ids, torch.Tensor) or input_ids.dim() != 2:
+            _refuse(self.what, "input_ids must be a [B, L] tensor")
+        B, L = input_ids.shape
+        if B != 1:
+            _refuse(self.what, f"input_ids with B = {B}: generate is implemented for B == 1")
+        if attention_mask is not None and (tuple(attention_mask.shape) != (B, L) or not bool((attention_mask.detach().cpu() != 0).all())):
+            _refuse(self.what, "attention_mask must be all ones for generate (no padding inside a KV cache)")
+        if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
+            _refuse(self.what, "max_new_tokens is required and must be an int >= 1 (the decode loop is a `for` over it)")
+        if L + max_new_tokens > self.max_length:
+            _refuse(self.what, f"L + max_new_tokens = {L + max_new_tokens} exceeds max_length {self.max_length} of this adoption")
+        if isinstance(sync_every, bool) or not isinstance(sync_every, int) or sync_every < 1:
+            _refuse(self.what, "sync_every must be an int >= 1")
+        if eos_token_id is None:                                                  # transformers' default; an explicit [] asks for no EOS
+            eos_token_id = getattr(gc, "eos_token_id", None)
+        if eos_token_id is None:
+            return []
+        if isinstance(eos_token_id, torch.Tensor):
+            eos_token_id = eos_token_id.flatten().tolist()
+        eos = [eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id)
+        if not all(isinstance(e, int) and not isinstance(e, bool) for e in eos):
+            _refuse(self.what, "eos_token_id must be an int or a list of ints")
+        return eos
+
+    def _adopt_lm_head(self):
+        """`lm_head.weight` [V, d] bf16 on the device, adopted at the first generate; the token embedding under tie_word_embeddings."""
+        if self.lm_head is not None:
+            return self.lm_head
+        if self._tied:
+            self.lm_head = self.tok
+            return self.lm_head
+        w = self._lm_head_src
+        if w is None:
+            _refuse(self.what, "lm_head.weight is missing from the adopted state dict: generate needs it")
+        if w.dtype != torch.bfloat16 or tuple(w.shape) != tuple(self.tok.shape):
+            _refuse(self.what, f"lm_head.weight is {w.dtype} {tuple(w.shape)}, the kernels take bf16 {tuple(self.tok.shape)}")
+        self.lm_head = w.detach().to(self.device, torch.bfloat16).contiguous()
+        return self.lm_head
+
+    @torch.no_grad()
+    def generate(self, input_ids, attention_mask=None, pixel_values=None, image_grid_thw=None, max_new_tokens=None, eos_token_id=None,
+                 do_sample=None, return_dict_in_generate=False, output_logits=False, mm_token_type_ids=None, image_embeds=None,
+                 position_ids=None, sync_every=8, **kw):
+        """transformers' greedy `generate` for one sequence: LongTensor [1, L + n_new], the prompt followed by the new tokens, cut after the
+        first `eos_token_id` (an int or a list; EOS included; None: the module's generation_config.eos_token_id, []: no EOS).  The prefill is the layer loop of `__call__` with the k | v rows of every
+        layer appended to a cache; each further token is one row through rgn_lm_gemv_bf16 / rgn_lm_decode_attention_bf16, picked by
+        rgn_lm_head_argmax INTO the device id buffer the next rgn_text_embed reads: no token visits the host inside a step.  The host reads
+        the ids back every `sync_every` tokens to look for EOS (never without one); the result does not depend on `sync_every`."""
+        eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
+        ids_cpu, lengths, tables, pos = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids,
+                                                      mm_token_type_ids, image_embeds, {})
+        L, T = ids_cpu.shape[1], int(max_new_tokens)
+        new_tables = mrope_tables(self.inv_freq, decode_position_ids(pos, T), self.mrope_section)        # [2, 1, T, 128]
+        head = self._adopt_lm_head()                                               # may refuse: nothing has been launched yet
+        emb = self._image_embeds(pixel_values, image_grid_thw, image_embeds)
+        idx = None
+        if emb is not None:
+            if self.image_token_id is None:
+                _refuse(self.what, "the config has no image_token_id")
+            idx = image_rows(ids_cpu, lengths, int(self.image_token_id), emb.shape[0], self.what)[0].to(self.device)
+        lib, dev, d, V = _lib.lib(), self.device, self.d, self.tok.shape[0]
+        cap, kvw, nl = L + T, 2 * self.Hkv * HEAD_DIM, len(self.layers)
+        ws_a, ws_h = lib.rgn_lm_decode_attention_workspace_bytes(self.Hq, cap), lib.rgn_lm_head_workspace_bytes(V)
+        c = self.kv.get(cap, dict(cache=(nl, cap, kvw), h=(1, d), n=(1, d), qkv=(1, self.qkv_cols), a=(1, self.Hq * HEAD_DIM), ff=(1, 2 * self.F),
+                                  g=(1, self.F), ws_a=((ws_a + 1) // 2,), ws_h=((ws_h + 1) // 2,)))
+        t = self.buf.get(L, dict(h=(L, d), n=(L, d), qkv=(L, self.qkv_cols), a=(L, self.Hq * HEAD_DIM), ff=(L, 2 * self.F), g=(L, self.F)))
+        ids = torch.empty(cap, dtype=torch.int64, device=dev)
+        ids[:L] = input_ids[0].to(dev, torch.int64)
+        logits = torch.empty(T, V, dtype=torch.float32, device=dev) if output_logits else None
+        tab, ntab = tables.to(dev), new_tables.to(dev)                            # one host-to-device copy each
+        st = _stream()
+        ck = _lib.check
+
+        def pick(k):                                                              # token k from the normalised row in c["n"]
+            ck(lib.rgn_lm_head_argmax(_p(head), _p(c["n"]), V, d, ids.data_ptr() + 8 * (L + k), None if logits is None else _p(logits[k]),
+                                      _p(c["ws_h"]), ws_h, st), "rgn_lm_head_argmax")
+
+        h, _ = self._prefill_row(t, ids[:L], L, tab[0, 0], tab[1, 0], emb if emb is not None and emb.shape[0] else None, idx, cache=c["cache"])
+        self._rms(h[L - 1:L], self.final_ln, c["n"])                              # the final norm on the last row only
+        pick(0)
+        ph, pn, pqkv, pa, pff, pg, pws = (c[k].data_ptr() for k in ("h", "n", "qkv", "a", "ff", "g", "ws_a"))
+        lp = [(p["ln1"].data_ptr(), p["wqkv"].data_ptr(), p["bqkv"].data_ptr(), p["wo"].data_ptr(), p["ln2"].data_ptr(), p["wgu"].data_ptr(),
+               p["wdown"].data_ptr(), c["cache"][i].data_ptr()) for i, p in enumerate(self.layers)]
+        ptok, pfin, pcos, psin, pids = self.tok.data_ptr(), self.final_ln.data_ptr(), ntab[0, 0].data_ptr(), ntab[1, 0].data_ptr(), ids.data_ptr()
+        Hq, Hkv, F, eps, scale, qc, ad = self.Hq, self.Hkv, self.F, self.eps, float(self.scale), self.qkv_cols, self.Hq * HEAD_DIM
+        n_new = T
+
+        def first_eos(upto):                                                      # the host's look at the ids: the only synchronisation
+            got = ids[L:L + upto].cpu()
+            hit = torch.zeros(upto, dtype=torch.bool)
+            for e in eos:
+                hit |= got == e
+            return int(torch.nonzero(hit)[0]) + 1 if bool(hit.any()) else None
+        for k in range(1, T + 1):                                                 # bounded by max_new_tokens, never by device data
+            if eos and (k % sync_every == 0 or k == T):
+                cut = first_eos(k)
+                if cut is not None:
+                    n_new = cut
+                    break
+            if k == T:
+                break
+            row = L + k - 1                                                       # the token picked last: embed it, append it, attend over row + 1
+            ck(lib.rgn_text_embed(pids + 8 * row, 1, ptok, V, None, 0, ph, d, st), "rgn_text_embed")
+            for ln1, wqkv, bqkv, wo, ln2, wgu, wdown, pc in lp:
+                ck(lib.rgn_rms_norm_rows(ph, d, ln1, pn, d, 1, d, eps, st), "rgn_rms_norm_rows")
+                ck(lib.rgn_lm_gemv_bf16(wqkv, pn, bqkv, None, pqkv, qc, d, st), "rgn_lm_gemv_bf16")
+                ck(lib.rgn_mrope_bf16(pqkv, qc, pcos + 256 * (k - 1), psin + 256 * (k - 1), 1, Hq, Hkv, st), "rgn_mrope_bf16")
+                ck(lib.rgn_lm_kv_append_bf16(pqkv, qc, pc, cap, row, 1, Hq, Hkv, st), "rgn_lm_kv_append_bf16")
+                ck(lib.rgn_lm_decode_attention_bf16(pqkv, pc, pa, row + 1, Hq, Hkv, scale, pws, ws_a, st), "rgn_lm_decode_attention_bf16")
+                ck(lib.rgn_lm_gemv_bf16(wo, pa, None, ph, ph, d, ad, st), "rgn_lm_gemv_bf16")
+                ck(lib.rgn_rms_norm_rows(ph, d, ln2, pn, d, 1, d, eps, st), "rgn_rms_norm_rows")
+                ck(lib.rgn_lm_gemv_bf16(wgu, pn, None, None, pff, 2 * F, d, st), "rgn_lm_gemv_bf16")
+                ck(lib.rgn_swiglu_bf16(pff, 2 * F, pg, F, 1, F, st), "rgn_swiglu_bf16")
+                ck(lib.rgn_lm_gemv_bf16(wdown, pg, None, ph, ph, d, F, st), "rgn_lm_gemv_bf16")
+            ck(lib.rgn_rms_norm_rows(ph, d, pfin, pn, d, 1, d, eps, st), "rgn_rms_norm_rows")
+            pick(k)
+        seq = ids[:L + n_new].to(input_ids.device)[None]
+        if not return_dict_in_generate:
+            return seq
+        return QwenGenerateOutput(seq, tuple(logits[k][None] for k in range(n_new)) if logits is not None else None)

@@ -1,0 +1,190 @@
+"""Qwen2.5-VL prompt encoder, greedy generate(): HIP (HipQwen25VLTextEncoder.generate, csrc/decode.hip) against the eager bf16 transformers
+module's `generate(do_sample=False)`, same process, alternating.
+
+The language model at full size (tools/qwen_text_encoder_bench.py: hidden 3584, 28 layers, 28 / 4 heads, intermediate 18944, vocab 152064;
+seeded init on the device), text-only prompts of L = 300 and L = 1500, 64 new tokens, no EOS.  Per length and side: the median (and
+min / max) of `--iters` warm runs of a 1-token call (prefill + the first pick) and of a 64-token call; ms per new token =
+(t64 - t1) / 63 of the medians.  Batch-1 decode streams every weight once per token: the bytes of one step (decoder weights + lm_head +
+the KV cache rows read at the middle of the run) over the measured time, against the 6.3 TB/s the HBM sustains, is the share reported.
+
+The GEMV A/B: rgn_lm_gemv_bf16 against the AdaLN helper rgn_gemv_bf16 (B = 1) at the five (N, K) of a decode step, arms alternating
+(new, parent, new again: the A/A arm gives the box's noise).  Each timed pass walks a ring of weight copies larger than the last-level
+cache, as a decode step finds its weights in HBM.  `not_slower`: new's median minus parent's is at most the A/A spread.
+
+    python tools/qwen_generate_bench.py [--iters 5] [--out profiles/r14_qwen_generate_bench.json] [--ab-out profiles/r14_lm_gemv_ab.txt]
+    rocprofv3 --kernel-trace --stats -d DIR -o kt -- python tools/qwen_generate_bench.py --hip-only --no-ab --iters 2    # the kernel listing
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from qwen_text_encoder_bench import full_size_config  # noqa: E402
+
+HBM_BYTES_PER_S = 6.3e12          # measured stream bandwidth (the microarchitecture guide's figure for HBM)
+LENGTHS = (300, 1500)
+NEW = 64
+AB_SHAPES = ((4608, 3584), (3584, 3584), (37888, 3584), (3584, 18944), (152064, 3584))
+RING_BYTES = 1 << 30              # weight copies walked per timed pass: four times the 256 MB last-level cache
+
+
+def _ms(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def _stat(ts):
+    return {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts)}
+
+
+def step_bytes(tc, n):
+    """Bytes one decode step reads: every decoder weight, lm_head, and n cache rows per layer."""
+    d, F, hq, hkv, nl = tc.hidden_size, tc.intermediate_size, tc.num_attention_heads, tc.num_key_value_heads, tc.num_hidden_layers
+    w = 2 * nl * (d * (hq + 2 * hkv) * 128 + hq * 128 * d + 3 * d * F)
+    return {"decoder_weights": w, "lm_head": 2 * tc.vocab_size * d, "kv_cache": 2 * nl * n * 2 * hkv * 128}
+
+
+def gemv_ab(rounds=7):
+    from regione_amd import _lib
+    lib = _lib.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    rows = []
+    for N, K in AB_SHAPES:
+        copies = max(2, -(-RING_BYTES // (2 * N * K)))
+        g = torch.Generator(device="cuda").manual_seed(N + K)
+        W = torch.stack([(torch.randn(N, K, device="cuda", generator=g) * K ** -0.5).bfloat16() for _ in range(copies)])
+        x = torch.randn(K, device="cuda", generator=g).bfloat16()
+        y = torch.empty(N, dtype=torch.bfloat16, device="cuda")
+        ptrs, px, py = [W[c].data_ptr() for c in range(copies)], x.data_ptr(), y.data_ptr()
+
+        def new():
+            for p in ptrs:
+                lib.rgn_lm_gemv_bf16(p, px, None, None, py, N, K, st)
+
+        def parent():
+            for p in ptrs:
+                lib.rgn_gemv_bf16(px, K, p, None, py, N, 1, N, K, 0, st)
+        new()
+        a = y.clone()
+        parent()
+        max_diff = float((a.float() - y.float()).abs().max())
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) * 1e3 / copies                            # us per GEMV
+        for fn in (new, parent, new):
+            timed(fn)
+        t = {"new": [], "parent": [], "new_again": []}
+        for _ in range(rounds):                                                  # the arms alternate
+            t["new"].append(timed(new))
+            t["parent"].append(timed(parent))
+            t["new_again"].append(timed(new))
+        med = {k: statistics.median(v) for k, v in t.items()}
+        aa = abs(med["new"] - med["new_again"])
+        rows.append(dict(N=N, K=K, copies=copies, new_us=med["new"], parent_us=med["parent"], new_again_us=med["new_again"], aa_spread_us=aa,
+                         new_min_us=min(t["new"]), new_max_us=max(t["new"]), parent_min_us=min(t["parent"]), parent_max_us=max(t["parent"]),
+                         new_tb_per_s=2 * N * K / med["new"] / 1e6, parent_tb_per_s=2 * N * K / med["parent"] / 1e6,
+                         not_slower=bool(med["new"] - med["parent"] <= aa), max_abs_diff_of_outputs=max_diff))
+        del W
+        torch.cuda.empty_cache()
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--ab-out", default=None)
+    ap.add_argument("--hip-only", action="store_true", help="only the HIP calls (for a kernel-trace run)")
+    ap.add_argument("--no-ab", action="store_true", help="skip the GEMV A/B")
+    ap.add_argument("--no-generate", action="store_true", help="only the GEMV A/B")
+    a = ap.parse_args()
+    from regione_amd import build
+    sha = build.csrc_hash()
+    res = {"device": torch.cuda.get_device_name(0), "csrc_sha16": sha, "iters": a.iters, "new_tokens": NEW,
+           "stat": "median and min / max of warm, synchronised runs, the two sides alternating; ms per new token = (t64 - t1) / 63 of the medians",
+           "model": "Qwen2.5-VL-7B language model, seeded init, text-only ids, no EOS", "hbm_bytes_per_s": HBM_BYTES_PER_S}
+    if not a.no_ab:
+        rows = gemv_ab()
+        res["gemv_ab"] = rows
+        lines = [f"# rgn_lm_gemv_bf16 (new) against rgn_gemv_bf16 B = 1 (parent): median us per GEMV of 7 alternating rounds, each pass over a",
+                 f"# ring of weight copies >= {RING_BYTES >> 20} MiB; A/A = |median(new) - median(new again)|.  csrc_sha16 {sha}  {res['device']}",
+                 f"{'N':>7} {'K':>6} {'copies':>6} {'new us':>9} {'parent us':>10} {'new again':>10} {'A/A us':>8} {'new TB/s':>9} {'parent TB/s':>11}  not_slower"]
+        for r in rows:
+            lines.append(f"{r['N']:>7} {r['K']:>6} {r['copies']:>6} {r['new_us']:>9.2f} {r['parent_us']:>10.2f} {r['new_again_us']:>10.2f} "
+                         f"{r['aa_spread_us']:>8.2f} {r['new_tb_per_s']:>9.2f} {r['parent_tb_per_s']:>11.2f}  {r['not_slower']}")
+        lines.append("# why one row per wave and non-temporal weight loads (variant builds, not reproducible from this tree): profiles/r14_qwen_generate_notes.md")
+        print("\n".join(lines), flush=True)
+        if a.ab_out:
+            with open(a.ab_out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+    if not a.no_generate:
+        from transformers import Qwen2_5_VLForConditionalGeneration
+        from regione_amd import qwen_text_encoder as QT
+        cfg = full_size_config()
+        tc = cfg.text_config
+        torch.manual_seed(0)
+        with torch.device("cuda"):
+            mod = Qwen2_5_VLForConditionalGeneration(cfg).eval()
+        mod = mod.to(torch.bfloat16)
+        torch.cuda.empty_cache()
+        hip = QT.HipQwen25VLTextEncoder(mod)
+        g = torch.Generator().manual_seed(1)
+        for L in LENGTHS:
+            ids = torch.randint(0, 151000, (1, L), generator=g).cuda()
+            kw = dict(input_ids=ids, attention_mask=torch.ones_like(ids))
+            arms = {"hip_1": lambda: hip.generate(**kw, max_new_tokens=1, eos_token_id=[]),
+                    "hip_64": lambda: hip.generate(**kw, max_new_tokens=NEW, eos_token_id=[])}
+            if not a.hip_only:
+                ek = dict(do_sample=False, eos_token_id=None, pad_token_id=0)
+                arms["eager_1"] = lambda: mod.generate(**kw, max_new_tokens=1, min_new_tokens=1, **ek)
+                arms["eager_64"] = lambda: mod.generate(**kw, max_new_tokens=NEW, min_new_tokens=NEW, **ek)
+            ts = {k: [] for k in arms}
+            with torch.no_grad():
+                for k, fn in arms.items():
+                    fn()                                                         # warm
+                for _ in range(a.iters):
+                    for k, fn in arms.items():                                   # the sides alternate
+                        ts[k].append(_ms(fn))
+                r = {"L": L, **{k: _stat(v) for k, v in ts.items()}}
+                assert hip.generate(**kw, max_new_tokens=NEW, eos_token_id=[]).shape[1] == L + NEW
+                if not a.hip_only:
+                    he, ee = hip.generate(**kw, max_new_tokens=NEW, eos_token_id=[]), mod.generate(**kw, max_new_tokens=NEW, min_new_tokens=NEW, **ek)
+                    assert he.shape[1] == ee.shape[1] == L + NEW, "both sides must decode the full length"
+                    r["tokens_equal_to_eager"] = int((he[0, L:] == ee[0, L:he.shape[1]]).sum())
+                    r["tokens_equal_to_eager_note"] = ("of 64; informative only: the logits of a seeded-init model over 152064 words are near-ties that "
+                                                       "bf16 rounding decides, and after the first difference the two sides decode different "
+                                                       "sequences (tests/test_gpu_qwen_generate.py bounds the logits against fp32 instead)")
+            b = step_bytes(tc, L + NEW // 2)
+            r["step_bytes"] = dict(b, total=sum(b.values()))
+            r["streaming_floor_ms"] = sum(b.values()) / HBM_BYTES_PER_S * 1e3
+            for side in ("hip", "eager"):
+                if f"{side}_64" in r:
+                    per = (r[f"{side}_64"]["median_ms"] - r[f"{side}_1"]["median_ms"]) / (NEW - 1)
+                    r[f"{side}_ms_per_new_token"], r[f"{side}_prefill_ms"] = per, r[f"{side}_1"]["median_ms"]
+                    r[f"{side}_share_of_hbm_bw"] = sum(b.values()) / (per * 1e-3) / HBM_BYTES_PER_S
+            res[f"L{L}"] = r
+            print(f"L{L}", json.dumps(r), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
