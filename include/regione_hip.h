@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 111
+#define RGN_ABI_VERSION 112
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -475,9 +475,11 @@ size_t rgn_lm_head_workspace_bytes(int V);
  * straight from the fused QKV GEMM output: QKV [L, 3 H Dp] bf16 (all q heads | all k heads | all v heads), O [L, H Dp] bf16.  Dp in
  * {32, 64, 96, 128} is the head width padded with ZERO columns to a multiple of 32 (zero weight rows and bias entries: the dot products
  * and the real output columns are unchanged, the output's pad columns are exactly 0); `scale` is the caller's (real width ^ -0.5).
- * items: int32 [n_items, 4] on the device = (q0, n_q, k_lo, k_hi): queries [q0, q0 + n_q), 1 <= n_q <= 64, attend to keys [k_lo, k_hi),
- * their segment; no item crosses a segment; one workgroup per (item, head).  An item outside [0, L) is skipped; rows no item names are
- * not written.  Replaces the per-chunk attention interface calls of Qwen2_5_VLVisionAttention.forward.  Arithmetic and determinism as
+ * items: int32 [n_items, 4] on the device = (q0, n_q, k_lo, k_hi): queries [q0, q0 + n_q), 1 <= n_q <= 64, attend to keys [k_lo, k_hi);
+ * one workgroup per (item, head).  The kernel relates queries to keys through the item alone: the vision tower names a segment as the
+ * key range of its own queries (no item crosses a segment), the Step1X connector names keys [0, n_valid) for runs of valid rows and key
+ * 0 alone, (q0, n_q, 0, 1), for runs of padded rows, whose output is then v[0] of the head bit for bit.  An item outside [0, L) is
+ * skipped; rows no item names are not written.  Replaces the per-chunk attention interface calls of Qwen2_5_VLVisionAttention.forward.  Arithmetic and determinism as
  * rgn_lm_attention_bf16 (same tile core).  QKV, O, items 16-byte aligned; 1 <= H <= 1024; 0 < scale < inf. */
 int rgn_vision_attention_bf16(const void* QKV, void* O, int L, int H, int Dp, float scale, const int* items, int n_items, void* stream);
 /* apply_rotary_pos_emb_vision on the q and k columns (the first 2 H Dp of each row) of that QKV buffer, in place:
@@ -492,6 +494,29 @@ int rgn_gelu_erf_bf16(const void* x, void* y, size_t n, void* stream);
 /* y[m, :K] = bf16(x[m, :K]), y[m, K:Kp] = 0: x [M, K] fp32 (RGN_F32) or bf16 (RGN_BF16) with row stride ldx, y [M, Kp] bf16 contiguous,
  * 16-byte aligned, Kp % 8 == 0.  `pixel_values.to(bfloat16)` padded to a GEMM reduction width (K = 1176 -> Kp = 1216). */
 int rgn_cast_pad_rows(const void* x, int x_dtype, int ldx, void* y, int M, int K, int Kp, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * f4  Step1X-Edit's per-step `connector` ([EXT] Qwen2Connector, a token refiner conditioned on the timestep; Step1XEdit/inplace.py:514-516,
+ * Step1XEditV1P2/inplace.py:602-609 call it once per CFG branch per computed step).  Projections are rgn_gemm_group, the embedders
+ * rgn_gemv_bf16, the norms rgn_layer_norm_rows, the attention rgn_vision_attention_bf16 with Dp = 128; these are the row kernels around
+ * them (csrc/connector.hip).  No atomics, fixed reduction orders: a repeated call is bit-identical.
+ *
+ * The pooled context `(x * m).sum(1) / m.sum(1)` for a mask of n_valid leading ones, times a scalar:
+ *   out[c] = bf16(bf16(sum_{l < n_valid} x[l, c] / n_valid) * scale),   the sum in fp32
+ * scale = 1 gives the plain mean (the inner rounding is then the only one).  x [L, d] bf16 with row stride ldx, out [d] bf16; d % 8 == 0,
+ * ldx >= d (a multiple of 8), 1 <= n_valid <= L, scale finite; x and out 16-byte aligned.  Rows >= n_valid are not read. */
+int rgn_masked_mean_rows(const void* x, int ldx, int L, int d, int n_valid, float scale, void* out, void* stream);
+/* Per-head RMSNorm of width 128 on the q and k columns (the first 2 H 128) of packed QKV rows [L, 3 H 128], in place; the v columns and
+ * anything past them up to ld are not written.  x <- bf16(bf16(x * rsqrt(mean x^2 + eps)) * w), w = wq for the q heads and wk for the k
+ * heads (bf16 [128] each): the roundings, and the summation order, of rgn_rms_norm_rows on the heads as [L H, 128] rows - bit-equal to
+ * it.  rgn_qk_norm_rope_store without RoPE and without the slabs.  ld >= 3 H 128 (a multiple of 8), 1 <= H <= 1024, 0 <= eps < inf; QKV,
+ * wq, wk 16-byte aligned. */
+int rgn_head_rms_norm_bf16(void* QKV, int ld, const void* wq, const void* wk, int L, int H, float eps, void* stream);
+/* y[m, n] = bf16(f32(resid[m, n]) + f32(bf16(gate[n] * p[m, n]))): the elementwise half of RGN_EPI_GATE_RESID, for a projection p that
+ * was computed once (bias included, rounded to bf16) and a gate that changes per step - bit-equal to the fused epilogue on the same
+ * p.  p, resid, y [M, N] bf16 with row strides ldp, ldr, ldy (>= N, multiples of 8), gate bf16 [N]; N % 8 == 0; all 16-byte aligned.
+ * y may be resid. */
+int rgn_gate_resid_rows(const void* p, int ldp, const void* gate, const void* resid, int ldr, void* y, int ldy, int M, int N, void* stream);
 
 /* Device properties the host side needs for roofline reporting (no torch types). */
 int rgn_device_info(int* cu_count, int* clock_khz, size_t* hbm_bytes);

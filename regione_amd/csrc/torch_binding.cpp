@@ -345,6 +345,42 @@ void region_attention(const Tensor& q, const Tensor& k_cache, const Tensor& vt_c
                                    ws.data_ptr(), (size_t)ws.numel() * 4, stream_of(q)), "rgn_attention_bounded");
 }
 
+// ---- Step1X-Edit connector row kernels (csrc/connector.hip) ------------------------------------------------------------------
+void bf16_rows(const char* what, std::initializer_list<const Tensor*> ts) {
+    const Tensor* first = *ts.begin();
+    for (const Tensor* t : ts)
+        TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->dim() >= 1 && t->stride(-1) == 1 && t->device() == first->device(),
+                    what, ": bf16 HIP tensors with unit column stride on one device");
+}
+
+Tensor masked_mean_rows(const Tensor& x, int64_t n_valid, double scale) {
+    RGN_DEVICE_GUARD(x);
+    bf16_rows("masked_mean_rows", {&x});
+    TORCH_CHECK(x.dim() == 2, "masked_mean_rows: x [L, d]");
+    Tensor out = at::empty({x.size(1)}, x.options());
+    check_rc(rgn_masked_mean_rows(ptr(x), (int)x.stride(0), (int)x.size(0), (int)x.size(1), (int)n_valid, (float)scale, out.data_ptr(),
+                                  stream_of(x)), "rgn_masked_mean_rows");
+    return out;
+}
+
+void head_rms_norm_(Tensor qkv, const Tensor& wq, const Tensor& wk, int64_t heads, double eps) {
+    RGN_DEVICE_GUARD(qkv);
+    bf16_rows("head_rms_norm_", {&qkv, &wq, &wk});
+    TORCH_CHECK(qkv.dim() == 2 && heads >= 1 && qkv.size(1) >= 3 * heads * 128 && wq.numel() == 128 && wk.numel() == 128,
+                "head_rms_norm_: qkv [L, >= 3 H 128], norm weights bf16 [128]");
+    check_rc(rgn_head_rms_norm_bf16(qkv.data_ptr(), (int)qkv.stride(0), ptr(wq), ptr(wk), (int)qkv.size(0), (int)heads, (float)eps,
+                                    stream_of(qkv)), "rgn_head_rms_norm_bf16");
+}
+
+void gate_resid_rows_(const Tensor& p, const Tensor& gate, const Tensor& resid, Tensor out) {
+    RGN_DEVICE_GUARD(p);
+    bf16_rows("gate_resid_rows_", {&p, &gate, &resid, &out});
+    TORCH_CHECK(p.dim() == 2 && resid.sizes() == p.sizes() && out.sizes() == p.sizes() && gate.numel() == p.size(1),
+                "gate_resid_rows_: p, resid, out [M, N], gate [N]");
+    check_rc(rgn_gate_resid_rows(ptr(p), (int)p.stride(0), ptr(gate), ptr(resid), (int)resid.stride(0), out.data_ptr(), (int)out.stride(0),
+                                 (int)p.size(0), (int)p.size(1), stream_of(p)), "rgn_gate_resid_rows");
+}
+
 }  // namespace
 
 // the header this binding was compiled against: regione_amd/torch_ops.py compares both with libregione_hip.so's rgn_version() /
@@ -374,6 +410,10 @@ TORCH_LIBRARY(regione_mi, m) {
     m.def("region_attention(Tensor q, Tensor k_cache, Tensor vt_cache, Tensor(a!) out, int skv, int heads, float scale=-1.0, "
           "float score_bound=0.0) -> ()");
     m.def("workspace(Tensor like, int kind) -> Tensor");
+    // the connector's row kernels (regione_amd/torch_ops.py: ROW_SCHEMAS)
+    m.def("masked_mean_rows(Tensor x, int n_valid, float scale=1.0) -> Tensor");
+    m.def("head_rms_norm_(Tensor(a!) qkv, Tensor wq, Tensor wk, int heads, float eps=1e-6) -> ()");
+    m.def("gate_resid_rows_(Tensor p, Tensor gate, Tensor resid, Tensor(a!) out) -> ()");
 }
 
 // CUDA is the dispatch key of HIP tensors in PyTorch-ROCm; no CPU kernels are registered (a CPU tensor fails loudly)
@@ -389,4 +429,7 @@ TORCH_LIBRARY_IMPL(regione_mi, CUDA, m) {
     m.impl("kv_partial_update_group_", &kv_partial_update_group_);
     m.impl("region_attention", &region_attention);
     m.impl("workspace", &workspace_op);
+    m.impl("masked_mean_rows", &masked_mean_rows);
+    m.impl("head_rms_norm_", &head_rms_norm_);
+    m.impl("gate_resid_rows_", &gate_resid_rows_);
 }

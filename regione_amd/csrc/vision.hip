@@ -14,10 +14,11 @@
 namespace rgn {
 
 // ---- attention over packed segments ---------------------------------------------------------------------------------------------------
-// Block = one head x one item of the host-built table items[n][4] = (q0, n_q, k_lo, k_hi): queries [q0, q0 + n_q), n_q <= 64, all of ONE
-// segment whose keys are [k_lo, k_hi).  Keys outside the segment are never staged; keys of the last tile past k_hi are masked to -inf.
-// The first tile starts at k_lo, a key of the segment, so it holds a valid key for every query of the item (the invariant of
-// AttnTile::step).  Lanes past n_q compute on the item's last query and store nothing.  An item that does not lie inside [0, L) is
+// Block = one head x one item of the host-built table items[n][4] = (q0, n_q, k_lo, k_hi): queries [q0, q0 + n_q), n_q <= 64, which all
+// attend to the keys [k_lo, k_hi).  Queries and keys are related through the item alone: the vision tower names the segment of its queries
+// (a window, an image), the Step1X connector the valid keys for runs of valid rows and key 0 alone for runs of padded rows.  Keys outside
+// [k_lo, k_hi) are never staged; keys of the last tile past k_hi are masked to -inf.  The first tile starts at k_lo < k_hi, a key every
+// query of the item attends to, so it holds a valid key for every query (the invariant of AttnTile::step).  Lanes past n_q compute on the item's last query and store nothing.  An item that does not lie inside [0, L) is
 // skipped as a whole (the table is device data the launcher cannot read).
 template <int D>
 __global__ __launch_bounds__(256) void vision_attention_kernel(const uint16_t* __restrict__ QKV, uint16_t* __restrict__ O, int L, int H,

@@ -410,6 +410,51 @@ def add_bf16(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = Non
     return out
 
 
+def _bf16_rows(what: str, **tensors):
+    """The row kernels read bf16 rows through 16-byte vectors: dtype, unit column stride and one device, checked where the C ABI cannot."""
+    dev = None
+    for k, t in tensors.items():
+        if t.dtype != torch.bfloat16 or t.stride(-1) != 1 or (dev is not None and t.device != dev):
+            raise _lib.RegionEHipError(f"{what}: {k} must be bf16 with unit column stride on one device (got {t.dtype}, strides {t.stride()}, {t.device})")
+        dev = t.device
+
+
+def masked_mean_rows(x: torch.Tensor, n_valid: int, scale: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16(bf16(mean of the first `n_valid` rows of x [L, d]) * scale) -> [d] (rgn_masked_mean_rows): the connector's pooled context."""
+    L, d = x.shape
+    if out is None:
+        out = torch.empty(d, dtype=torch.bfloat16, device=x.device)
+    _bf16_rows("masked_mean_rows", x=x, out=out)
+    if out.numel() != d:
+        raise _lib.RegionEHipError(f"masked_mean_rows: out has {out.numel()} elements, x has {d} columns")
+    rc = _lib.lib().rgn_masked_mean_rows(_p(x), x.stride(0), L, d, int(n_valid), float(scale), _p(out), _stream())
+    _lib.check(rc, "rgn_masked_mean_rows")
+    return out
+
+
+def head_rms_norm_(qkv: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, H: int, eps: float = 1e-6) -> torch.Tensor:
+    """Per-head RMSNorm (width 128) of the q and k columns of packed [L, >= 3 H 128] rows, in place (rgn_head_rms_norm_bf16)."""
+    _bf16_rows("head_rms_norm_", qkv=qkv, wq=wq, wk=wk)
+    if qkv.dim() != 2 or qkv.shape[1] < 3 * H * 128 or wq.numel() != 128 or wk.numel() != 128:
+        raise _lib.RegionEHipError(f"head_rms_norm_: qkv {tuple(qkv.shape)} for {H} heads of 128, weights of {wq.numel()} / {wk.numel()} elements")
+    rc = _lib.lib().rgn_head_rms_norm_bf16(_p(qkv), qkv.stride(0), _p(wq), _p(wk), qkv.shape[0], int(H), float(eps), _stream())
+    _lib.check(rc, "rgn_head_rms_norm_bf16")
+    return qkv
+
+
+def gate_resid_rows(p: torch.Tensor, gate: torch.Tensor, resid: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 `resid + gate * p` with torch's two roundings (rgn_gate_resid_rows); p, resid [M, N], gate [N]; `out` may be resid."""
+    if out is None:
+        out = torch.empty_like(resid)
+    _bf16_rows("gate_resid_rows", p=p, gate=gate, resid=resid, out=out)
+    M, N = p.shape
+    if tuple(resid.shape) != (M, N) or tuple(out.shape) != (M, N) or gate.numel() != N:
+        raise _lib.RegionEHipError(f"gate_resid_rows: p {tuple(p.shape)}, resid {tuple(resid.shape)}, out {tuple(out.shape)}, gate of {gate.numel()}")
+    rc = _lib.lib().rgn_gate_resid_rows(_p(p), p.stride(0), _p(gate), _p(resid), resid.stride(0), _p(out), out.stride(0), M, N, _stream())
+    _lib.check(rc, "rgn_gate_resid_rows")
+    return out
+
+
 def sel_rows(edited_ids: torch.Tensor, T: int) -> torch.Tensor:
     """int64 [T + K]: [0..T) then T + edited_ids - the cache rows of a region step (inplace.py:732-733)."""
     idv = edited_ids.reshape(-1)

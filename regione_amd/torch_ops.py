@@ -75,15 +75,19 @@ _defined = set()
 SCHEMAS = {}
 
 
-def _define(name: str, schema: str, impl, fake):
-    if name in _defined:
+ROW_SCHEMAS = {}                # the row kernels of the Step1X connector: registered alike, listed apart (SCHEMAS is the region-op surface)
+_row_defined = set()
+
+
+def _define(name: str, schema: str, impl, fake, schemas=SCHEMAS, names=_defined):
+    if name in names:
         return
-    SCHEMAS[name] = schema
+    schemas[name] = schema
     if _lib is not None:
         _lib.define(f"{name}{schema}")
         torch.library.impl(_lib, name, "CUDA")(impl)
     torch.library.register_fake(f"{NS}::{name}")(fake)
-    _defined.add(name)
+    names.add(name)
 
 
 # ---- region ops ---------------------------------------------------------------------------------
@@ -214,8 +218,30 @@ _define("workspace", "(Tensor like, int kind) -> Tensor", _workspace,
         lambda like, kind: like.new_empty((1,), dtype=torch.float32))
 
 
+# ---- Step1X-Edit connector row kernels (csrc/connector.hip) -----------------------------------------
+def _head_rms_norm(qkv, wq, wk, heads, eps=1e-6):
+    ops.head_rms_norm_(qkv, wq, wk, heads, eps)
+
+
+def _gate_resid_rows(p, gate, resid, out):
+    ops.gate_resid_rows(p, gate, resid, out)
+
+
+_define("masked_mean_rows", "(Tensor x, int n_valid, float scale=1.0) -> Tensor",
+        lambda x, n_valid, scale=1.0: ops.masked_mean_rows(x, n_valid, scale),
+        lambda x, n_valid, scale=1.0: x.new_empty((x.shape[1],)), ROW_SCHEMAS, _row_defined)
+_define("head_rms_norm_", "(Tensor(a!) qkv, Tensor wq, Tensor wk, int heads, float eps=1e-6) -> ()", _head_rms_norm,
+        lambda *a, **k: None, ROW_SCHEMAS, _row_defined)
+_define("gate_resid_rows_", "(Tensor p, Tensor gate, Tensor resid, Tensor(a!) out) -> ()", _gate_resid_rows,
+        lambda *a, **k: None, ROW_SCHEMAS, _row_defined)
+
+
 def registered() -> Tuple[str, ...]:
     return tuple(sorted(_defined))
+
+
+def registered_row_ops() -> Tuple[str, ...]:
+    return tuple(sorted(_row_defined))
 
 
 def _sc(w):
