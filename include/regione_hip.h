@@ -284,6 +284,12 @@ int rgn_qk_norm_rope_store(void* qkv, int ld, int k_col, int v_col, int q_col, i
  *   Q [Sq, H*128] (row stride ldq) ; K slab / V^T slab as written by rgn_qk_norm_rope_store;
  *   O [Sq, H*128] (row stride ldo), may alias Q (each workgroup reads its Q tile before writing;
  *   with a workspace, split items write O only in the final combine pass).
+ * What the kernels read behind Skv (skv_pad >= Skv rounded up to 64; tests/test_gpu_region_attn_probes.py):
+ *   K slab rows [Skv, round_up(Skv, 64)): the pad rows of the last 64-key tile are LOADED and their scores masked to -inf before
+ *     the row maximum - any bits, NaN included, are harmless;
+ *   V^T slab columns of that tile that hold no key (kvpos(r) of no r < Skv): LOADED and multiplied by P = 0 - they must be FINITE
+ *     (0 * NaN and 0 * inf would reach the output), any finite value is harmless;
+ *   nothing at or behind row / column round_up(Skv, 64) of either slab is read, and nothing outside [Sq, H*128] of O is written.
  */
 int rgn_attention(const void* Q, int ldq, const void* k_slab, const void* vt_slab, int skv_pad, void* O,
                   int ldo, int Sq, int Skv, int H, float scale, void* workspace, size_t workspace_bytes,

@@ -337,10 +337,15 @@ def counting_allowed(case):
     hm = head_map(case.q.shape[0], case.k.shape[0]).to(case.q.device)
     vh = case.v[hm]
     mask = dense_mask(case)
-    if mask is None:
-        mask = torch.ones(vh.shape[1], vh.shape[1], dtype=torch.bool, device=vh.device)
+    if mask is None:                                                # every key, for every query (Sq != Skv: the region kernels)
+        mask = torch.ones(case.q.shape[1], vh.shape[1], dtype=torch.bool, device=vh.device)
     total = mask.double() @ vh.double()                             # exact
     count = mask.sum(-1).double()[None, :, None]
+    return two_roundings(total, count)
+
+
+def two_roundings(total, count):
+    """The two-value rule of counting_allowed on an exact fp64 sum and count (broadcast against each other)."""
     a = (total.float() * (1.0 / count.float())).to(BF16)
     b = (total / count).float().to(BF16)
     return a, b

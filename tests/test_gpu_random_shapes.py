@@ -155,8 +155,10 @@ def test_gemm_fp8_weights_random_shapes(seed):
 def test_attention_random_shapes(seed):
     import numpy as np
     from regione_amd import ops
+    from attn_tile_model import bound
     rng = np.random.default_rng(4000 + seed)
     g = torch.Generator(device="cuda").manual_seed(300 + seed)
+    worst = 0.0
     for case in range(7):
         H = int(rng.integers(1, 25))
         Sq = int(rng.integers(1, 3000 if H <= 8 else 1300))
@@ -180,12 +182,17 @@ def test_attention_random_shapes(seed):
         scale = 1.0 / math.sqrt(128)
         ops.attention(q, kc, vt, out, Skv, H, scale=scale)
         p = torch.softmax((q.double().view(Sq, H, 128).transpose(0, 1) @ k.double().view(Skv, H, 128).permute(1, 2, 0)) * scale, dim=-1)
-        ref = (p @ v.double().view(Skv, H, 128).transpose(0, 1)).transpose(0, 1).reshape(Sq, D)
+        vd = v.double().view(Skv, H, 128).transpose(0, 1)
+        ref = (p @ vd).transpose(0, 1).reshape(Sq, D)
+        a_ref = (p @ vd.abs()).transpose(0, 1).reshape(Sq, D)
         err = (out.double() - ref).abs()
-        # P is rounded to bf16 before the PV product (2^-9 relative per term, averaging down over Skv terms) + one bf16 rounding of O
-        tol = 2 ** -7 * ref.abs() + 6e-3
+        # the element-wise bound of the tile arithmetic (attn_tile_model.bound: P rounded to bf16 for the PV product, one bf16 rounding
+        # of O): 2^-8 A_ref + 2^-8 |ref| + 1e-6, the one tests/test_gpu_region_attn_probes.py holds every launch path to
+        tol = bound(ref, a_ref)
+        worst = max(worst, float((err / tol).max()))
         assert bool((err <= tol).all()), f"seed {seed} case {case}: Sq={Sq} Skv={Skv} H={H}: worst {float((err / tol).max()):.2f} x tolerance"
         assert bool(torch.isfinite(out.float()).all())
+    print(f"seed {seed}: worst err / bound {worst:.3f}")
 
 
 @pytest.mark.parametrize("seed", range(8))
