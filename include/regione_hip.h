@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 112
+#define RGN_ABI_VERSION 113
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -44,7 +44,8 @@ const char* rgn_last_error(void);
  * models decide) in a shipped run.  `key` in {gemm_pieces (1 = one plain launch, n >= 2 = n K pieces of a round's remainder),
  * gemm_geometry (128 | 256), gemm_asm (0 = compiler-scheduled kernels only), gemm_quarter (0 never | 1 always), attn_waves (4 | 8),
  * attn_split (0 = never cut KV), attn_streamk (0 = equal pieces only | 1 = wherever possible), attn_asm (0 = compiler-scheduled
- * loop)}; value -1 restores the default; key NULL resets every knob.  Process-wide, not synchronised with launches in flight on other
+ * loop), rowbands (0 = rgn_rowband_fork does nothing | 1 = on, the default | 2..98 = on, band 0 takes that share in percent of the row
+ * tiles)}; value -1 restores the default; key NULL resets every knob.  Process-wide, not synchronised with launches in flight on other
  * threads.  The same knobs can be preset once per process with RGN_PLAN_OVERRIDE="key=value,key=value" - the only environment
  * variable libregione_hip.so reads, at the first launch.  Results never depend on a knob beyond fp32 summation order. */
 int rgn_plan_override(const char* key, int value);
@@ -53,13 +54,38 @@ int rgn_plan_override(const char* key, int value);
 int rgn_plan_override_get(const char* key, int* value);
 /* The launch plan the GEMM planner chose for the last rgn_gemm_group call on this thread (introspection for tests and traces; the
  * reference has no counterpart): bits 0-7 = K pieces of the remainder (1 = none), bit 8 = quarter-tile remainder, bit 10 =
- * 256 x 256 tile geometry. */
+ * 256 x 256 tile geometry, bit 11 = launched as two row bands (rgn_rowband_fork). */
 int rgn_gemm_last_plan(void);
 /* The plan the planner WOULD choose for a group of `nprob` (<= 4) problems with M = Ms[i] rows, N output channels, depth K, `distinct_w`
  * different weight matrices (problems of one stream share W), bf16 (w8 = 0) or fp8 (w8 = 1) weights and a workspace of
  * `workspace_bytes` (0 = none): same bits as rgn_gemm_last_plan.  Pure host arithmetic on the launch cost model - no launch, no GPU
  * (CPU tests pin the planner's decisions for the region-step shapes with it); negative RGN_E_* on a bad argument. */
 int rgn_gemm_plan_query(const int* Ms, int nprob, int N, int K, int distinct_w, int w8, size_t workspace_bytes);
+
+/* Row bands (no reference counterpart: scheduling only).  Between two attentions every stage of a transformer block is row-wise - output
+ * projection, LN-modulate, the feed-forward GEMMs, the next block's Q/K/V projection - so the rows can be cut ONCE into two bands whose
+ * chains run on two streams: the partially filled last round of one band's GEMM is filled by the other band's next launch.
+ *   rgn_rowband_fork(stream): the library's side stream (one per thread and device, created at the first fork) waits for everything
+ *     enqueued on `stream`; from here on rgn_gemm_group and rgn_ln_modulate / rgn_ln_modulate_segs calls of THIS thread on `stream` cut
+ *     their rows at the band boundary and launch band 0 on `stream`, band 1 on the side stream.
+ *   rgn_rowband_join(stream): `stream` waits for the side stream; launches are whole again.  Without a fork it does nothing.
+ * Ordering is hipEventRecord / hipStreamWaitEvent only.  The CALLER guarantees that every call between fork and join is row-wise in the
+ * same rows (reads only the rows it writes, of buffers the earlier calls wrote with the same problem sizes) and joins before anything
+ * that is not (attention, a call with other row counts, another stream).
+ * Boundary: the problem (LN: row segment) with the most rows - of equal ones the one highest in memory - is cut at a multiple of 256 rows
+ * from its first row, so that band 0 (every other problem whole + its first rows) holds its share (half) of the 256-row tiles; a problem of
+ * fewer than two tiles is not cut (everything is band 0).  A band launch uses the tile geometry the planner picks for the whole group and
+ * runs whole tiles only - no K pieces, no reduce pass, no quarter tiles, no workspace - so banded results are bit-identical to the
+ * unbanded launch under gemm_pieces = 1; the fused Q/K/V epilogue's row_base advances with the pointers (rotary rows, kv_rows, K slab
+ * rows and V^T positions stay those of the unbanded launch).
+ *   rgn_rowband_query: the boundary for `nprob` (1..4) problems of Ms[i] rows listed in memory order - returns 1 and the cut (problem
+ *     *cut_problem keeps rows [0, *cut_row) in band 0, its rows from *cut_row on are band 1), 0 when nothing is cut (*cut_problem = -1);
+ *     pure host arithmetic, no GPU.
+ *   rgn_rowband_side_launches: how many band-1 launches this thread has sent to a side stream so far (tests). */
+int rgn_rowband_fork(void* stream);
+int rgn_rowband_join(void* stream);
+int rgn_rowband_query(const int* Ms, int nprob, int* cut_problem, int* cut_row);
+long long rgn_rowband_side_launches(void);
 
 /* ------------------------------------------------------------------------------------------
  * a1/a2  Adaptive Region Partition.  Replaces token_selector (utils.py:282-354) + morphology

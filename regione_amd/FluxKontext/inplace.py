@@ -284,6 +284,7 @@ class RegionEFluxAttnProcessor(H.FluxAttnProcessor):
                     c = (ops.zeros((pad, d), dtype=torch.bfloat16, device=ws.device),
                          ops.zeros((d, pad), dtype=torch.bfloat16, device=ws.device), skv)
                 cur.wait_stream(dflt)            # the zero fill is ordered before this forward's writes
+                H.rowband_meet(ctx)              # ... of BOTH row bands (harness.flux.ROW_BANDS): the side stream must see the fill too
                 if cur != dflt:
                     c[0].record_stream(cur)
                     c[1].record_stream(cur)

@@ -53,6 +53,10 @@ SIGNATURES = {
     "rgn_attention_last_plan": [],
     "rgn_attention_plan_query": [_c_int, _c_int, _c_int, C.c_size_t],
     "rgn_gemm_plan_query": [C.POINTER(C.c_int), _c_int, _c_int, _c_int, _c_int, _c_int, C.c_size_t],
+    "rgn_rowband_fork": [_c_void_p],
+    "rgn_rowband_join": [_c_void_p],
+    "rgn_rowband_query": [C.POINTER(C.c_int), _c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "rgn_rowband_side_launches": [],
     "rgn_last_error": [],
     "rgn_device_info": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)],
     "rgn_arp_partition": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_float, _c_float,
@@ -133,7 +137,7 @@ SIGNATURES = {
 _RESTYPE = {"rgn_last_error": C.c_char_p, "rgn_abi_struct_bytes": C.c_size_t, "rgn_attention_workspace_bytes": C.c_size_t,
             "rgn_gemm_workspace_bytes": C.c_size_t, "rgn_groupnorm_workspace_bytes": C.c_size_t,
             "rgn_groupnorm_partial_bytes": C.c_size_t, "rgn_lm_decode_attention_workspace_bytes": C.c_size_t,
-            "rgn_lm_head_workspace_bytes": C.c_size_t}
+            "rgn_lm_head_workspace_bytes": C.c_size_t, "rgn_rowband_side_launches": C.c_longlong}
 
 _lib = None
 
@@ -174,7 +178,7 @@ def lib():
 
 import contextlib as _contextlib
 
-PLAN_KEYS = ("gemm_pieces", "gemm_geometry", "gemm_asm", "gemm_quarter", "attn_waves", "attn_split", "attn_streamk", "attn_asm")
+PLAN_KEYS = ("gemm_pieces", "gemm_geometry", "gemm_asm", "gemm_quarter", "attn_waves", "attn_split", "attn_streamk", "attn_asm", "rowbands")
 
 
 @_contextlib.contextmanager

@@ -56,8 +56,18 @@ struct PlanOverride {
     int attn_split;       // 0 = never cut the KV range of remainder items
     int attn_streamk;     // 0 = equal KV pieces only, 1 = stream-K wherever it is possible
     int attn_asm;         // 0 = the compiler-scheduled KV loop (the ragged-KV fallback)
+    int rowbands;         // 0 = rgn_rowband_fork does nothing, 1 = on (the default), 2..98 = on, band 0 takes that share (%) of the row tiles
 };
 PlanOverride& plan_override();          // region.hip
+
+// Row bands (rgn_rowband_fork / rgn_rowband_join, region.hip): between a fork and the join on `st` the row-wise entry points (rgn_gemm_group,
+// rgn_ln_modulate*) cut their rows at rowband_cut() and launch band 0 on `st`, band 1 on the library's side stream.
+bool rowband_active(hipStream_t st, hipStream_t* side);      // forked on this thread for `st`?  *side = where band 1 goes
+void rowband_count_side_launch();
+// The band boundary of `n` row problems (Ms[i] rows each; addr[i], optional, orders problems of equal size: the one highest in memory is
+// cut): problem *which keeps rows [0, *row) in band 0 and sends [*row, M) to band 1, every other problem stays whole in band 0.  *row is a
+// multiple of 256.  false: nothing to cut (the largest problem has fewer than two row tiles) - everything is band 0.  Pure host arithmetic.
+bool rowband_cut(const int* Ms, const uintptr_t* addr, int n, int* which, int* row);
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;    // 8 bf16 = 4 VGPRs (MFMA A/B fragment)
 typedef __attribute__((ext_vector_type(4))) float f32x4;

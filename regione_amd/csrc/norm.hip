@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void ln_modulate_wave_kernel(const uint16_t* _
     }
 }
 
-static int launch_ln(const uint16_t* x, int ldx, uint16_t* out, int ldo, int M, int d, float eps, const LnSegs& segs, hipStream_t st) {
+static int launch_ln_rows(const uint16_t* x, int ldx, uint16_t* out, int ldo, int M, int d, float eps, const LnSegs& segs, hipStream_t st) {
     if (d % 512 == 0) {          // the wave-per-row kernel; other widths (toy trunks, d = 256): the block-per-row kernel below
         const dim3 grid((M + 3) / 4), blk(256);
         switch (d / 512) {
@@ -163,6 +163,32 @@ static int launch_ln(const uint16_t* x, int ldx, uint16_t* out, int ldo, int M, 
     }
     hipLaunchKernelGGL(ln_modulate_kernel, dim3(M), dim3(256), 0, st, x, ldx, out, ldo, d, eps, segs);
     return check_launch("ln_modulate_kernel");
+}
+
+// Row bands (rgn_rowband_fork, region.hip): while `st` is forked the rows are cut where the GEMMs of the same chain cut theirs - the row
+// segments are the GEMM group's problems - and the rows behind the cut go to the side stream.  Per row nothing changes.
+static int launch_ln(const uint16_t* x, int ldx, uint16_t* out, int ldo, int M, int d, float eps, const LnSegs& segs, hipStream_t st) {
+    hipStream_t side = nullptr;
+    if (!rowband_active(st, &side)) return launch_ln_rows(x, ldx, out, ldo, M, d, eps, segs, st);
+    int Ms[LN_MAXSEG], n = 0, start[LN_MAXSEG], prev = 0, which = 0, row = 0;
+    for (int i = 0; i < LN_MAXSEG; ++i) {
+        const int end = segs.end[i] < M ? segs.end[i] : M;
+        if (end > prev) { Ms[n] = end - prev; start[n] = prev; ++n; prev = end; }
+    }
+    if (!rowband_cut(Ms, nullptr, n, &which, &row)) return launch_ln_rows(x, ldx, out, ldo, M, d, eps, segs, st);
+    // band 1 = rows [c, e) of the cut segment; band 0 = everything else: rows [0, c) and, when the cut segment is not the last, [e, M)
+    const int c = start[which] + row, e = start[which] + Ms[which];
+    auto shifted = [&](int by) {
+        LnSegs t = segs;
+        for (int i = 0; i < LN_MAXSEG; ++i) t.end[i] = segs.end[i] < by ? 0 : segs.end[i] - by;
+        return t;
+    };
+    int rc = launch_ln_rows(x, ldx, out, ldo, c, d, eps, segs, st);
+    if (rc == 0 && e < M) rc = launch_ln_rows(x + (size_t)e * ldx, ldx, out + (size_t)e * ldo, ldo, M - e, d, eps, shifted(e), st);
+    if (rc) return rc;
+    const LnSegs hi = shifted(c);
+    rowband_count_side_launch();
+    return launch_ln_rows(x + (size_t)c * ldx, ldx, out + (size_t)c * ldo, ldo, e - c, d, eps, hi, side);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -323,7 +323,8 @@ __global__ void sel_rows_kernel(const int64_t* __restrict__ ids, int K, int T, i
 static int* plan_field(PlanOverride& o, const char* key) {
     struct { const char* name; int* field; } tab[] = {
         {"gemm_pieces", &o.gemm_pieces}, {"gemm_geometry", &o.gemm_geometry}, {"gemm_asm", &o.gemm_asm}, {"gemm_quarter", &o.gemm_quarter},
-        {"attn_waves", &o.attn_waves}, {"attn_split", &o.attn_split}, {"attn_streamk", &o.attn_streamk}, {"attn_asm", &o.attn_asm}};
+        {"attn_waves", &o.attn_waves}, {"attn_split", &o.attn_split}, {"attn_streamk", &o.attn_streamk}, {"attn_asm", &o.attn_asm},
+        {"rowbands", &o.rowbands}};
     for (auto& t : tab)
         if (strcmp(t.name, key) == 0) return t.field;
     return nullptr;
@@ -337,7 +338,7 @@ static bool plan_set(PlanOverride& o, const char* key, int value) {
 
 PlanOverride& plan_override() {
     static PlanOverride o = [] {
-        PlanOverride v{-1, -1, -1, -1, -1, -1, -1, -1};
+        PlanOverride v{-1, -1, -1, -1, -1, -1, -1, -1, -1};
         const char* e = getenv("RGN_PLAN_OVERRIDE");
         if (e != nullptr) {
             char buf[256];
@@ -354,11 +355,106 @@ PlanOverride& plan_override() {
     return o;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Row bands.  Between two attentions of a full step every stage is row-wise (projection -> LN-modulate -> FF -> ... -> Q/K/V projection):
+// the rows are cut once, at a tile boundary, and each band's chain runs on its own stream - one band's partially filled last round of
+// 256 x 256 tiles is filled by the other band's next launch (another weight, K, epilogue), which no single launch can do.  Ordering is
+// two events per fork / join pair, nothing spins and no kernel knows about it.  State is per thread and device: the thread that forks is
+// the thread whose launches are cut, and only launches on the stream it forked.  The side stream and the events live as long as the
+// process (created at the first fork on a device).
+// ------------------------------------------------------------------------------------------------
+struct RowBandState {
+    hipStream_t side = nullptr, main = nullptr;
+    hipEvent_t forked = nullptr, joined = nullptr;
+    bool on = false;
+};
+static thread_local RowBandState g_rowband[64];
+static thread_local long long g_rowband_side_launches = 0;
+
+static RowBandState* rowband_state() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    return &g_rowband[dev];
+}
+
+bool rowband_active(hipStream_t st, hipStream_t* side) {
+    RowBandState* s = rowband_state();
+    if (s == nullptr || !s->on || s->main != st) return false;
+    *side = s->side;
+    return true;
+}
+
+void rowband_count_side_launch() { ++g_rowband_side_launches; }
+
+bool rowband_cut(const int* Ms, const uintptr_t* addr, int n, int* which, int* row) {
+    int total = 0, best = -1;
+    for (int i = 0; i < n; ++i) {
+        if (Ms[i] <= 0) continue;
+        total += (Ms[i] + 255) / 256;
+        // the problem that is cut: the one with the most rows; of equal ones the one highest in memory (the later rows of a shared
+        // buffer), else the later one - every stage of a chain names the same rows whatever order it lists its problems in
+        if (best < 0 || Ms[i] > Ms[best] || (Ms[i] == Ms[best] && (addr == nullptr || addr[i] >= addr[best]))) best = i;
+    }
+    if (best < 0) return false;
+    const int mine = (Ms[best] + 255) / 256, others = total - mine;
+    if (mine < 2) return false;
+    const int pct = plan_override().rowbands;
+    const int share = (pct >= 2 && pct <= 98) ? pct : 50;       // band 0's share of the row tiles; 50: see profiles/r17_rowband_ab.txt
+    int k = (total * share + 50) / 100 - others;                // row tiles of the cut problem that stay in band 0
+    k = k < 1 ? 1 : (k > mine - 1 ? mine - 1 : k);
+    *which = best;
+    *row = k * 256;
+    return true;
+}
+
 }  // namespace rgn
 
 using namespace rgn;
 
 extern "C" {
+
+int rgn_rowband_fork(void* stream) {
+    if (plan_override().rowbands == 0) return 0;
+    RowBandState* s = rowband_state();
+    if (s == nullptr) return fail(RGN_E_UNSUPPORTED, "rowband_fork: no device");
+    if (s->on && s->main != (hipStream_t)stream) return fail(RGN_E_BADARG, "rowband_fork: this thread has forked another stream (join it first)");
+    hipError_t e = hipSuccess;
+    if (s->side == nullptr) {
+        hipStream_t side = nullptr;
+        hipEvent_t a = nullptr, b = nullptr;
+        e = hipStreamCreateWithFlags(&side, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&a, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&b, hipEventDisableTiming);
+        if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
+        s->side = side; s->forked = a; s->joined = b;
+    }
+    e = hipEventRecord(s->forked, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s->side, s->forked, 0);
+    if (e != hipSuccess) return fail((int)e, hipGetErrorString(e));
+    s->main = (hipStream_t)stream;
+    s->on = true;
+    return 0;
+}
+
+int rgn_rowband_join(void* stream) {
+    RowBandState* s = rowband_state();
+    if (s == nullptr || !s->on) return 0;
+    if (s->main != (hipStream_t)stream) return fail(RGN_E_BADARG, "rowband_join: another stream was forked");
+    s->on = false;
+    hipError_t e = hipEventRecord(s->joined, s->side);
+    if (e == hipSuccess) e = hipStreamWaitEvent((hipStream_t)stream, s->joined, 0);
+    return e == hipSuccess ? 0 : fail((int)e, hipGetErrorString(e));
+}
+
+int rgn_rowband_query(const int* Ms, int nprob, int* cut_problem, int* cut_row) {
+    if (!Ms || nprob < 1 || nprob > 4 || !cut_problem || !cut_row) return fail(RGN_E_BADARG, "rowband_query: 1..4 problems");
+    for (int i = 0; i < nprob; ++i)
+        if (Ms[i] < 0) return fail(RGN_E_BADARG, "rowband_query: negative row count");
+    *cut_problem = -1; *cut_row = 0;
+    return rowband_cut(Ms, nullptr, nprob, cut_problem, cut_row) ? 1 : 0;
+}
+
+long long rgn_rowband_side_launches(void) { return g_rowband_side_launches; }
 
 int rgn_version(void) { return RGN_ABI_VERSION; }
 size_t rgn_abi_struct_bytes(void) { return sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem); }
@@ -379,7 +475,7 @@ int rgn_fill_zero(void* ptr, size_t bytes, void* stream) {
 
 int rgn_plan_override(const char* key, int value) {
     PlanOverride& o = plan_override();
-    if (key == nullptr) { o = PlanOverride{-1, -1, -1, -1, -1, -1, -1, -1}; return 0; }
+    if (key == nullptr) { o = PlanOverride{-1, -1, -1, -1, -1, -1, -1, -1, -1}; return 0; }
     return plan_set(o, key, value) ? 0 : fail(RGN_E_BADARG, "plan_override: unknown key");
 }
 int rgn_plan_override_get(const char* key, int* value) {

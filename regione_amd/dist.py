@@ -196,6 +196,17 @@ def run_cfg_branches(pair: Optional[CfgBranchPair], run_cond: Callable[[], torch
     CUs, a drain and a fill at every kernel boundary) interleave with the other branch's instead of leaving CUs idle.
     The engine keeps one activation workspace and one split-K / KV-split scratch per stream.  With a pair: one branch per
     rank + exchange."""
+    # the forwards of a CFG step never run as row bands (harness.flux.ROW_BANDS): as two forwards they keep the launch plans of the
+    # batched pass, to which they are bit-identical
+    from .harness import flux as _HF
+    prev, _HF.CFG_PAIR = _HF.CFG_PAIR, True
+    try:
+        return _run_cfg_branches(pair, run_cond, run_uncond, concurrent, batch_on)
+    finally:
+        _HF.CFG_PAIR = prev
+
+
+def _run_cfg_branches(pair, run_cond, run_uncond, concurrent, batch_on):
     if pair is not None:
         return pair.exchange(run_cond() if pair.role == "cond" else run_uncond())
     if batch_on is not None and branch_batching() and hasattr(batch_on, "begin_batch"):

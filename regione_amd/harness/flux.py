@@ -318,6 +318,10 @@ class FwdCtx:
         # the caller only reads the first `out_rows` image rows of the forward's output (pipelines slice
         # `[:, :latents.size(1)]`, inplace.py:346): the LAST block may skip every row nothing downstream reads
         self.out_rows = out_rows
+        # row bands (ops.rowband_fork): set by a single-branch FLUX forward; the processor forks after a full step's attention, the
+        # next block's processor joins before its own
+        self.rowbands = False
+        self.forked = False               # between ops.rowband_fork and ops.rowband_join
 
 
 # ---------------------------------------------------------------------------------------------
@@ -332,6 +336,12 @@ SKIP_UNREAD_ROWS = True
 # ATTN_BRANCH_STREAMS: in a batched CFG pass the second branch's attention runs on a side stream (bench.py's per-launch timer
 # switches it off while it is installed: per-launch durations need launches that do not share the chip).
 ATTN_BRANCH_STREAMS = True
+# ROW_BANDS: in a full step of a single-branch FLUX forward the row-wise stages between two attentions (output projection, LN-modulate,
+# feed-forward, the next block's Q/K/V projection) run as two row bands on two streams (rgn_rowband_fork, include/regione_hip.h): one band's
+# partial last GEMM round is filled by the other band's next launch.  Off whenever ATTN_BRANCH_STREAMS is (per-launch timing needs launches
+# that have the chip to themselves) and under the plan override rowbands=0.
+ROW_BANDS = True
+CFG_PAIR = False          # set by dist.run_cfg_branches while the forwards of a CFG step run: no row bands there
 
 
 class Attention:
@@ -396,6 +406,16 @@ class FluxAttnProcessor:
     def __init__(self, single: bool = False):
         self.single = single
 
+    @staticmethod
+    def _attention(ctx, band: bool, q, k_slab, vt_slab, skv, H, bound):
+        """Attention reads every row: the bands of the stages before it join here, and fork again behind it (`band`: this block's
+        remaining stages and the next block's up to its attention are row-wise in the same rows)."""
+        ops.rowband_join()
+        TO.R.region_attention(q, k_slab, vt_slab, q, skv, H, -1.0, bound)
+        ctx.forked = bool(band)
+        if band:
+            ops.rowband_fork()
+
     # -- the three K/V destinations ---------------------------------------------------------------
     def kv_target(self, attn: Attention, ctx: FwdCtx):
         """-> (k_slab, vt_slab, kv_rows, skv, rope_k).  Vanilla: scratch slab, identity rows."""
@@ -419,6 +439,11 @@ class FluxAttnProcessor:
         ctx.partial_kv = partial
         (cos_q, sin_q), (cos_k, sin_k) = image_rotary_emb, rope_k
         n_out = ctx.out_rows if (block is not None and getattr(block, "is_last", False)) else None
+        # the last block stays whole with or without SKIP_UNREAD_ROWS (its launches plan as they always did)
+        band = ctx.rowbands and not partial and not getattr(block, "is_last", False)
+        if not fuse:
+            ctx.forked = False
+            ops.rowband_join()         # the separate norm / RoPE / cache pass reads every row of the projection
         if not self.single:
             if n_out is not None and not partial:
                 # last block of a double-stream-only trunk (Qwen-Image), full step: keys / values of every row of both
@@ -446,7 +471,7 @@ class FluxAttnProcessor:
                 ops.qk_norm_rope_store(wide, 0, d, 2 * d, H, attn.norm_q, attn.norm_k, image_rotary_emb, rope_k,
                                        k_slab, vt_slab, kv_rows, split_row=T, wq0=attn.norm_added_q, wk0=attn.norm_added_k)
             q = wide[:, 2 * d:3 * d]
-            TO.R.region_attention(q, k_slab, vt_slab, q, skv, H, -1.0, attn.score_bound())
+            self._attention(ctx, band, q, k_slab, vt_slab, skv, H, attn.score_bound())
             g_img, g_txt = block.gates_msa(ctx)
             ops.gemm_pair(q[T:R], attn.w_out, attn.b_out, ws.x[T:R], q[:T], attn.w_add_out, attn.b_add_out, ws.x[:T],
                           epilogue=ops.EPI_GATE_RESID, gate0=g_img, resid0=ws.x[T:R], gate1=g_txt, resid1=ws.x[:T])
@@ -473,7 +498,7 @@ class FluxAttnProcessor:
             ops.qk_norm_rope_store(wide, 0, d, 2 * d, H, attn.norm_q, attn.norm_k, image_rotary_emb, rope_k, k_slab,
                                    vt_slab, kv_rows)
         q = wide[:, 2 * d:3 * d]
-        TO.R.region_attention(q, k_slab, vt_slab, q, skv, H, -1.0, attn.score_bound())
+        self._attention(ctx, band, q, k_slab, vt_slab, skv, H, attn.score_bound())
         return wide[:, 2 * d:]                                       # cat([attn_output, mlp_hidden], dim=2)
 
 
@@ -534,6 +559,20 @@ class FluxAttnProcessor:
         ops.gemm_group(group, epilogue=ops.EPI_GATE_RESID)
 
 
+def rowband_meet(ctx):
+    """Inside a forked stretch: both bands wait for everything enqueued so far, then go on as two (the side stream only waits for what
+    the caller's stream held AT the fork - a fill or copy enqueued later, or rows cut elsewhere, need the bands to meet)."""
+    if getattr(ctx, "forked", False):
+        ops.rowband_join()
+        ops.rowband_fork()
+
+
+def _band_row(Ms):
+    """Band 1's rows [start, end) of problems laid out back to back, None when nothing is cut (ops.rowband_query)."""
+    cut = ops.rowband_query(Ms)
+    return None if cut is None else (sum(Ms[:cut[0]]) + cut[1], sum(Ms[:cut[0] + 1]))
+
+
 def _branch_rows(ctxs) -> int:
     last = ctxs[-1]
     return last.ws.base + last.T + last.M
@@ -556,6 +595,9 @@ class FluxTransformerBlock:
         ws, T, M, mods = ctx.ws, ctx.T, ctx.M, ctx.mods
         R = T + M
         d = ws.cfg.d
+        if getattr(self, "is_last", False):
+            ctx.forked = False
+            ops.rowband_join()             # the last block may skip rows: not the bands' rows
         # norm1 / norm1_context: LN * (1 + scale_msa) + shift_msa   (chunks: shift, scale, gate, shift, scale, gate)
         ops.ln_modulate(ws.x[:R], ws.nrm[:R], mods.chunk(self.mo_img, 0), mods.chunk(self.mo_img, 1), split_row=T,
                         shift0=mods.chunk(self.mo_ctx, 0), scale0=mods.chunk(self.mo_ctx, 1))
@@ -621,6 +663,9 @@ class FluxSingleTransformerBlock:
         ctx = temb
         ws, T, M, mods = ctx.ws, ctx.T, ctx.M, ctx.mods
         R = T + M
+        if getattr(self, "is_last", False):
+            ctx.forked = False
+            ops.rowband_join()             # the last block may skip rows: not the bands' rows
         ops.ln_modulate(ws.x[:R], ws.nrm[:R], mods.chunk(self.mo, 0), mods.chunk(self.mo, 1))
         self.attn.fwd_ctx, self.attn.block = ctx, self
         cat = self.attn(hidden_states=ws.nrm[:R], image_rotary_emb=image_rotary_emb)
@@ -645,6 +690,7 @@ class FluxTransformer2DModel:
     """[EXT] module tree of diffusers' FluxTransformer2DModel with HIP-backed blocks."""
 
     accepts_row_cat = True            # `hidden_states` may arrive as a RowCat (cat_tokens): the x_embedder reads the pieces
+    row_bands = True                  # full steps run the stages between two attentions as two row bands (ROW_BANDS); subclasses: off
 
     def __init__(self, cfg: FluxConfig, device="cuda"):
         self.cfg_model = cfg
@@ -941,10 +987,20 @@ class FluxTransformer2DModel:
             temb = self.time_text_embed(ts, gd, pooled)
             mods = Modulation(ops.gemv(temb, self.mod_w, self.mod_b, silu_input=True), d)
         ctx = FwdCtx(ws, T, M, mods, tag=(joint_attention_kwargs or {}).get("tag"), out_rows=Mo if SKIP_UNREAD_ROWS else None)
-        for block in self.transformer_blocks:
-            block(hidden_states=ws.x[T:R], encoder_hidden_states=ws.x[:T], temb=ctx, image_rotary_emb=image_rotary_emb)
-        for block in self.single_transformer_blocks:
-            block(hidden_states=ws.x[T:R], encoder_hidden_states=ws.x[:T], temb=ctx, image_rotary_emb=image_rotary_emb)
+        # row bands: FLUX only, no CFG step's forwards, never while launches are timed one by one (ATTN_BRANCH_STREAMS False); the
+        # processors fork / join around their attention in full steps.  The double blocks cut [text | image] in the image rows, the
+        # single blocks the joint rows: where the two boundaries differ (T not a multiple of 256) the bands meet once in between.
+        ctx.rowbands = bool(ROW_BANDS and ATTN_BRANCH_STREAMS and self.row_bands and not CFG_PAIR)
+        try:
+            for block in self.transformer_blocks:
+                block(hidden_states=ws.x[T:R], encoder_hidden_states=ws.x[:T], temb=ctx, image_rotary_emb=image_rotary_emb)
+            if ctx.forked and self.single_transformer_blocks and _band_row((T, M)) != _band_row((R,)):
+                rowband_meet(ctx)
+            for block in self.single_transformer_blocks:
+                block(hidden_states=ws.x[T:R], encoder_hidden_states=ws.x[:T], temb=ctx, image_rotary_emb=image_rotary_emb)
+        finally:
+            ctx.forked = False
+            ops.rowband_join()             # embedders, norm_out / proj_out and whatever follows see whole launches
         # norm_out (AdaLayerNormContinuous: scale, shift = chunk(emb, 2)) + proj_out
         Ro = T + Mo
         ops.ln_modulate(ws.x[T:Ro], ws.nrm[T:Ro], mods.chunk(self.mo_out, 1), mods.chunk(self.mo_out, 0))

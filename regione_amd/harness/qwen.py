@@ -71,6 +71,8 @@ class QwenDoubleStreamAttnProcessor2_0(H.FluxAttnProcessor):
 
 
 class QwenImageTransformer2DModel(H.FluxTransformer2DModel):
+    row_bands = False                 # row bands (harness.flux.ROW_BANDS) are measured and enabled for the FLUX trunk only
+
     def __init__(self, cfg: FluxConfig, device="cuda"):
         assert cfg.n_single == 0 and not cfg.pooled_embeds and not cfg.guidance_embeds
         super().__init__(cfg, device)

@@ -27,6 +27,8 @@ class Step1XEditAttnProcessor(H.FluxAttnProcessor):
 
 
 class Step1XEditTransformer2DModel(H.FluxTransformer2DModel):
+    row_bands = False                 # row bands (harness.flux.ROW_BANDS) are measured and enabled for the FLUX trunk only
+
     def __init__(self, cfg: FluxConfig, device="cuda"):
         assert not cfg.guidance_embeds, "Step1X-Edit has no guidance embedder"
         super().__init__(cfg, device)

@@ -372,6 +372,32 @@ def gemm_group(problems, *, epilogue: int = EPI_BIAS, gelu_from_col: int = 0):
     _launch(probs, epilogue, gelu_from_col)
 
 
+# row bands (rgn_rowband_fork / rgn_rowband_join, include/regione_hip.h): between fork and join on the current stream the GEMM and
+# LN-modulate launches above / below run as two row bands on two streams; the harness forks after a block's attention and joins before
+# the next one
+def rowband_fork():
+    _lib.check(_lib.lib().rgn_rowband_fork(_stream()), "rgn_rowband_fork")
+
+
+def rowband_join():
+    _lib.check(_lib.lib().rgn_rowband_join(_stream()), "rgn_rowband_join")
+
+
+def rowband_query(Ms):
+    """The band boundary for problems of `Ms` rows listed in memory order: (problem, row) - that problem's rows from `row` on are band 1,
+    everything else band 0 - or None when nothing is cut.  Host arithmetic only (no GPU)."""
+    n = len(Ms)
+    which, row = ctypes.c_int(-1), ctypes.c_int(0)
+    rc = _lib.lib().rgn_rowband_query((ctypes.c_int * n)(*[int(m) for m in Ms]), n, ctypes.byref(which), ctypes.byref(row))
+    if rc < 0:
+        _lib.check(rc, "rgn_rowband_query")
+    return (which.value, row.value) if rc == 1 else None
+
+
+def rowband_side_launches() -> int:
+    return int(_lib.lib().rgn_rowband_side_launches())
+
+
 def gemv(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], silu_input: bool = False,
          out: Optional[torch.Tensor] = None) -> torch.Tensor:
     B, K = x.shape
