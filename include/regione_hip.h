@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 113
+#define RGN_ABI_VERSION 114
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -478,6 +478,13 @@ int rgn_swiglu_bf16(const void* x, int ldx, void* y, int ldy, int M, int F, void
  * accumulation in a fixed order; W [N, K] row-major and dense, W and x 16-byte aligned, K % 64 == 0; bias may be NULL.  Weights go from
  * global memory straight to registers (8 16-byte loads per lane in flight); HBM-bound on W. */
 int rgn_lm_gemv_bf16(const void* W, const void* x, const void* bias, const void* resid, void* y, int N, int K, void* stream);
+/* The same one-row linear layer over fp8 weights (ops.quantize_w8: OCP e4m3fn bytes W8 [N, K] dense, one fp32 scale per output channel):
+ * v = wscale[n] * sum_k f32(W8[n,k]) x[k] (+ bias[n]) in fp32, y[n] = bf16(v), with resid != NULL y[n] = bf16(bf16(v) + resid[n]); what
+ * rgn_gemm_group computes for one row of A with `wscale`.  The conversion is exact (v_cvt_pk_f32_fp8), the scale multiplies the reduced
+ * sum once; fixed reduction order, no atomics.  K % 16 == 0, K >= 64; W8, wscale, x and y 16-byte aligned; x, bias, resid, y bf16; y may
+ * be resid.  Half the bytes of rgn_lm_gemv_bf16 per row. */
+int rgn_lm_gemv_w8(const void* W8, const float* wscale, const void* x, const void* bias, const void* resid, void* y, int N, int K,
+                   void* stream);
 /* cache[row0 + i, :] = QKV[i, Hq 128 : (Hq + 2 Hkv) 128] for i < L: the k | v columns of packed QKV rows (after rgn_mrope_bf16) into a
  * cache [cap, 2 Hkv 128] bf16, bit for bit.  ld = row stride of QKV in elements; 0 <= row0, row0 + L <= cap <= 4096; QKV and cache 16-byte
  * aligned.  The prefill appends its L rows, a decode step one. */

@@ -119,6 +119,7 @@ SIGNATURES = {
     "rgn_swiglu_bf16": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
     # f4: greedy decode of that language model (csrc/decode.hip)
     "rgn_lm_gemv_bf16": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p],
+    "rgn_lm_gemv_w8": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p],
     "rgn_lm_kv_append_bf16": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p],
     "rgn_lm_decode_attention_bf16": [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p, C.c_size_t, _c_void_p],
     "rgn_lm_decode_attention_workspace_bytes": [_c_int, _c_int],

@@ -394,12 +394,17 @@ def hip_qwen_text_encoder_for(host, dev):
     as `vision=`; a tower `vision_refusal` names (or one with non-bf16 weights) stays the host's eager module under the adopted language
     model, with one "vision tower kept on the host module: ..." warning; `pipe._regione_hip_vision = False` keeps it there on purpose,
     silently.  A `text_encoder` that is not a `Qwen2_5_VLForConditionalGeneration` is left alone silently;
-    `pipe._regione_hip_text = False` before the first call keeps the whole host module on purpose."""
+    `pipe._regione_hip_text = False` before the first call keeps the whole host module on purpose.
+    `pipe._regione_hip_text_weights = "fp8"` before the first call adopts the layers' projection matrices as fp8 e4m3fn with per-channel
+    scales (HipQwen25VLTextEncoder(weights="fp8")); absent, the adoption is "bf16"; another value raises ValueError naming the two."""
     if host.__dict__.get("_regione_hip_text", _NO_HIP_VAE) is False:
         return None
     cached = host.__dict__.get("_regione_hip_qwen_text", _NO_HIP_VAE)
     if cached is not _NO_HIP_VAE:
         return cached
+    fmt = host.__dict__.get("_regione_hip_text_weights", "bf16")
+    if fmt not in ("bf16", "fp8"):
+        raise ValueError(f"pipe._regione_hip_text_weights = {fmt!r}: \"bf16\" and \"fp8\" are accepted")
     mod = getattr(host, "text_encoder", None)
     enc = None
     if type(mod).__name__ == "Qwen2_5_VLForConditionalGeneration" and getattr(mod, "config", None) is not None:
@@ -409,7 +414,7 @@ def hip_qwen_text_encoder_for(host, dev):
             why = "PEFT / LoRA layers in the module"
         if why is None:
             try:
-                enc = QT.HipQwen25VLTextEncoder(mod, dev)
+                enc = QT.HipQwen25VLTextEncoder(mod, dev, weights=fmt)
             except _lib.RegionEHipError as e:
                 why = str(e)
         if why is not None:

@@ -4,6 +4,8 @@
 //   lm_gemv_kernel              y = W x (+ bias) (+ resid) for ONE row x: one wave per row, weights straight from global memory to VGPRs in
 //                               non-temporal 16-byte vectors with 8 loads per lane in flight before the first use; no LDS for W
 //   lm_gemv_kernel<ARGMAX>      the same dot products over the vocabulary in fp32 with a per-block (value, index) maximum, then
+//   lm_gemv_w8_kernel           the same one-row product over OCP e4m3fn weights with one fp32 scale per row: half the bytes per row, the
+//                               conversion exact in registers, the scale applied once to the fp32 sum
 //   lm_head_finalize_kernel     one block that folds the per-block maxima: the LOWEST index among equal fp32 values wins
 //   lm_kv_append_kernel         the k | v columns of packed QKV rows (after mRoPE) into rows of the cache, bit for bit
 //   lm_decode_attention_kernel  one query token: a block takes one KV head and one slice of 64 cache rows for all Hq / Hkv query heads of
@@ -79,6 +81,72 @@ __global__ __launch_bounds__(256) void lm_gemv_kernel(const uint16_t* __restrict
     } else if (lane == 0 && n < N) {
         const float v = s + (bias ? bf2f(bias[n]) : 0.f);
         y[n] = resid ? f2bf(rbf(v) + bf2f(resid[n])) : f2bf(v);                  // torch's `h + linear(a)`: two roundings
+    }
+}
+
+// ---- the same product over fp8 weights (ops.quantize_w8: OCP e4m3fn, one fp32 scale per output channel) ------------------------------
+// v_cvt_pk_f32_fp8 decodes two bytes of a word exactly (gfx950: OCP e4m3fn, not the fnuz form of gfx942); the products and the sum are fp32
+// in ascending k per lane, the scale multiplies the reduced sum once.
+__device__ __forceinline__ float dot16_w8(const u32x4 w, const uint4 xa, const uint4 xb, float acc) {
+    const uint32_t a[4] = {w.x, w.y, w.z, w.w}, b[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)a[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)a[e], true);
+        acc = fmaf(lo[0], __uint_as_float(b[2 * e] << 16), acc);
+        acc = fmaf(lo[1], __uint_as_float(b[2 * e] & 0xffff0000u), acc);
+        acc = fmaf(hi[0], __uint_as_float(b[2 * e + 1] << 16), acc);
+        acc = fmaf(hi[1], __uint_as_float(b[2 * e + 1] & 0xffff0000u), acc);
+    }
+    return acc;
+}
+
+// Block = 4 waves, wave = W8_ROWS consecutive rows, lane = k in [16 lane, 16 lane + 16) of every 1024-wide step: a 16-byte load carries 16
+// weights and meets two 16-byte loads of x (shared by the rows of the wave).  The W8_ROWS x W8_U weight loads of a round are issued before
+// the first fma; a lane past K loads nothing and adds 0, a row past N re-reads row N - 1 and writes nothing.  A row is half the bytes of a
+// bf16 row, so one row per wave with 8 loads in flight (the bf16 shape) keeps half of its slots empty at K = 3584 and costs 126 VGPRs:
+// two rows per wave with 4 loads each (one round covers K <= 4096; 86 VGPRs) measured 6 % faster over the four layer matrices than one
+// row with 4 loads, and 20 % faster than the bf16 shape; four rows per wave lost at every shape (profiles/r17_lm_gemv_w8_ab.txt).
+constexpr int W8_ROWS = 2, W8_U = 4, W8_STEP = 64 * 16;
+
+template <int ROWS, int U>
+__global__ __launch_bounds__(256) void lm_gemv_w8_kernel(const uint8_t* __restrict__ W, const float* __restrict__ wscale,
+                                                         const uint16_t* __restrict__ x, const uint16_t* __restrict__ bias,
+                                                         const uint16_t* resid, uint16_t* y, int N, int K) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n0 = (blockIdx.x * 4 + wave) * ROWS;
+    if (n0 >= N) return;                                                         // wave-uniform; the kernel has no barrier
+    const uint8_t* wr[ROWS];
+    float acc[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        wr[r] = W + (size_t)(n0 + r < N ? n0 + r : N - 1) * (size_t)K;
+        acc[r] = 0.f;
+    }
+    for (int k0 = lane * 16; k0 < K; k0 += W8_STEP * U) {
+        u32x4 wv[ROWS][U];
+        uint4 xa[U], xb[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int k = k0 + W8_STEP * u;
+            const bool ok = k < K;
+            xa[u] = ok ? *(const uint4*)(x + k) : make_uint4(0u, 0u, 0u, 0u);
+            xb[u] = ok ? *(const uint4*)(x + k + 8) : make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) wv[r][u] = ok ? __builtin_nontemporal_load((const u32x4*)(wr[r] + k)) : u32x4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) acc[r] = dot16_w8(wv[r][u], xa[u], xb[u], acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        const float s = wave_sum(acc[r]);
+        const int n = n0 + r;
+        if (lane == 0 && n < N) {
+            const float v = fmaf(s, wscale[n], bias ? bf2f(bias[n]) : 0.f);      // the scale once, on the reduced sum
+            y[n] = resid ? f2bf(rbf(v) + bf2f(resid[n])) : f2bf(v);              // the two roundings of lm_gemv_kernel
+        }
     }
 }
 
@@ -279,6 +347,19 @@ int rgn_lm_gemv_bf16(const void* W, const void* x, const void* bias, const void*
     hipLaunchKernelGGL((lm_gemv_kernel<false>), dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)W, (const uint16_t*)x,
                        (const uint16_t*)bias, (const uint16_t*)resid, (uint16_t*)y, (float*)nullptr, (float*)nullptr, (int*)nullptr, N, K);
     return check_launch("lm_gemv_kernel");
+}
+
+int rgn_lm_gemv_w8(const void* W8, const float* wscale, const void* x, const void* bias, const void* resid, void* y, int N, int K,
+                   void* stream) {
+    if (!W8 || !wscale || !x || !y || N < 1 || K < 64)
+        return fail(RGN_E_BADARG, "lm_gemv_w8: bad argument (W8, wscale, x, y non-null; N >= 1; K >= 64)");
+    if (K % 16) return fail(RGN_E_BADARG, "lm_gemv_w8: K must be a multiple of 16");
+    if (!dal16(W8) || !dal16(wscale) || !dal16(x) || !dal16(y)) return fail(RGN_E_BADARG, "lm_gemv_w8: W8, wscale, x and y must be 16-byte aligned");
+    if (((uintptr_t)bias | (uintptr_t)resid) & 1u) return fail(RGN_E_BADARG, "lm_gemv_w8: bias and resid must be 2-byte aligned");
+    constexpr int rows = 4 * W8_ROWS;
+    hipLaunchKernelGGL((lm_gemv_w8_kernel<W8_ROWS, W8_U>), dim3((N + rows - 1) / rows), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)W8,
+                       wscale, (const uint16_t*)x, (const uint16_t*)bias, (const uint16_t*)resid, (uint16_t*)y, N, K);
+    return check_launch("lm_gemv_w8_kernel");
 }
 
 static inline int head_parts(int V) { return (V + 3) / 4; }                 // lm_gemv_kernel<true>: 4 rows per block

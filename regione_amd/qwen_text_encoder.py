@@ -27,6 +27,12 @@ logits, the lowest index on a tie), which writes the token into the device id bu
 max(prompt positions) + 1 + k on all three axes (`decode_position_ids`).  The loop is a `for` over `max_new_tokens`; the host reads the ids
 every `sync_every` tokens to look for EOS.
 
+`weights="fp8"` stores the four packed matrices of every layer (q|k|v, o, gate|up, down) as OCP e4m3fn with one fp32 scale per output
+channel (ops.quantize_w8, after the concatenation: the scale is per row, so the concatenation of the parts' quantisations is the
+quantisation of the concatenation), layer by layer on the device; norms, the q|k|v bias, the embedding and `lm_head` stay bf16.  The prefill
+is unchanged (ops.gemm takes the scale from the weight tensor, rgn_gemm_group converts exactly and scales the accumulator); the decode loop
+calls rgn_lm_gemv_w8 instead of rgn_lm_gemv_bf16: half the bytes per token for those matrices.  Opt-in: the default "bf16" is the path above.
+
 There is no eager fallback inside: what the kernels do not implement raises RegionEHipError before any launch, and the adapter
 (regione_amd/adapters.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
 only; every call returns freshly allocated outputs.
@@ -45,6 +51,7 @@ _p, _stream = ops._p, ops._stream
 HEAD_DIM = 128
 LM = "model.language_model."
 NOT_ADOPTED = ("lm_head.", "model.visual.")                  # lm_head.weight: adopted by the first generate()
+WEIGHT_FORMATS = ("bf16", "fp8")                             # of the layers' projection matrices (`weights=`)
 
 
 class QwenTextEncoderOutput:
@@ -199,7 +206,10 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
     states) are absent.  Padded positions are zero rows."""
     what = "HipQwen25VLTextEncoder"
 
-    def __init__(self, module_or_state_dict, device=None, config=None, max_length: int = 4096, vision=None):
+    def __init__(self, module_or_state_dict, device=None, config=None, max_length: int = 4096, vision=None, weights: str = "bf16"):
+        if weights not in WEIGHT_FORMATS:
+            _refuse(self.what, f"weights={weights!r} (the layer matrices are kept as one of {WEIGHT_FORMATS})")
+        self.weights = weights
         sd, cfg, dev, mod = _source(module_or_state_dict, config, device, self.what)
         self.vision = vision                               # a HipQwen25VLVisionTower, or None: the adopted module's eager tower
         why = qwen25vl_refusal(cfg)
@@ -225,15 +235,17 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
 
         def cat(b, names, kind):
             return torch.cat([lm[f"{LM}{b}{n}.{kind}"].to(dev, torch.bfloat16) for n in names]).contiguous()
+        # "fp8": each packed matrix is quantised on the device as soon as it is there; its bf16 form is dropped before the next one
+        mat = ops.quantize_w8 if weights == "fp8" else (lambda t: t)
         self.tok = w("embed_tokens.weight")                                            # in place: no copy when it is already there
         self.layers = []
         for i in range(tc.num_hidden_layers):
             b = f"layers.{i}."
             qkv = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")
             self.layers.append(dict(
-                ln1=w(b + "input_layernorm.weight"), wqkv=cat(b, qkv, "weight"), bqkv=cat(b, qkv, "bias"),
-                wo=w(b + "self_attn.o_proj.weight"), ln2=w(b + "post_attention_layernorm.weight"),
-                wgu=cat(b, ("mlp.gate_proj", "mlp.up_proj"), "weight"), wdown=w(b + "mlp.down_proj.weight")))
+                ln1=w(b + "input_layernorm.weight"), wqkv=mat(cat(b, qkv, "weight")), bqkv=cat(b, qkv, "bias"),
+                wo=mat(w(b + "self_attn.o_proj.weight")), ln2=w(b + "post_attention_layernorm.weight"),
+                wgu=mat(cat(b, ("mlp.gate_proj", "mlp.up_proj"), "weight")), wdown=mat(w(b + "mlp.down_proj.weight"))))
         self.final_ln = w("norm.weight")
         # the module's own inv_freq buffer (a `.to(bfloat16)` of the module rounds it; the eager forward then uses the rounded one)
         rot = getattr(getattr(getattr(mod, "model", None), "language_model", None), "rotary_emb", None) if mod is not None else None
@@ -440,7 +452,8 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
                  position_ids=None, sync_every=8, **kw):
         """transformers' greedy `generate` for one sequence: LongTensor [1, L + n_new], the prompt followed by the new tokens, cut after the
         first `eos_token_id` (an int or a list; EOS included; None: the module's generation_config.eos_token_id, []: no EOS).  The prefill is the layer loop of `__call__` with the k | v rows of every
-        layer appended to a cache; each further token is one row through rgn_lm_gemv_bf16 / rgn_lm_decode_attention_bf16, picked by
+        layer appended to a cache; each further token is one row through rgn_lm_gemv_bf16 (rgn_lm_gemv_w8 under weights="fp8") /
+        rgn_lm_decode_attention_bf16, picked by
         rgn_lm_head_argmax INTO the device id buffer the next rgn_text_embed reads: no token visits the host inside a step.  The host reads
         the ids back every `sync_every` tokens to look for EOS (never without one); the result does not depend on `sync_every`."""
         eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
@@ -476,8 +489,15 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         self._rms(h[L - 1:L], self.final_ln, c["n"])                              # the final norm on the last row only
         pick(0)
         ph, pn, pqkv, pa, pff, pg, pws = (c[k].data_ptr() for k in ("h", "n", "qkv", "a", "ff", "g", "ws_a"))
-        lp = [(p["ln1"].data_ptr(), p["wqkv"].data_ptr(), p["bqkv"].data_ptr(), p["wo"].data_ptr(), p["ln2"].data_ptr(), p["wgu"].data_ptr(),
-               p["wdown"].data_ptr(), c["cache"][i].data_ptr()) for i, p in enumerate(self.layers)]
+        # the one-row linear layer of this adoption, picked once: a weight is the leading argument(s) of its entry, (W,) or (W8, scale)
+        if self.weights == "fp8":
+            gemv, gemv_name = lib.rgn_lm_gemv_w8, "rgn_lm_gemv_w8"
+            wp = lambda t: (t.data_ptr(), ops._wscale(t).data_ptr())
+        else:
+            gemv, gemv_name = lib.rgn_lm_gemv_bf16, "rgn_lm_gemv_bf16"
+            wp = lambda t: (t.data_ptr(),)
+        lp = [(p["ln1"].data_ptr(), wp(p["wqkv"]), p["bqkv"].data_ptr(), wp(p["wo"]), p["ln2"].data_ptr(), wp(p["wgu"]),
+               wp(p["wdown"]), c["cache"][i].data_ptr()) for i, p in enumerate(self.layers)]
         ptok, pfin, pcos, psin, pids = self.tok.data_ptr(), self.final_ln.data_ptr(), ntab[0, 0].data_ptr(), ntab[1, 0].data_ptr(), ids.data_ptr()
         Hq, Hkv, F, eps, scale, qc, ad = self.Hq, self.Hkv, self.F, self.eps, float(self.scale), self.qkv_cols, self.Hq * HEAD_DIM
         n_new = T
@@ -500,15 +520,15 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             ck(lib.rgn_text_embed(pids + 8 * row, 1, ptok, V, None, 0, ph, d, st), "rgn_text_embed")
             for ln1, wqkv, bqkv, wo, ln2, wgu, wdown, pc in lp:
                 ck(lib.rgn_rms_norm_rows(ph, d, ln1, pn, d, 1, d, eps, st), "rgn_rms_norm_rows")
-                ck(lib.rgn_lm_gemv_bf16(wqkv, pn, bqkv, None, pqkv, qc, d, st), "rgn_lm_gemv_bf16")
+                ck(gemv(*wqkv, pn, bqkv, None, pqkv, qc, d, st), gemv_name)
                 ck(lib.rgn_mrope_bf16(pqkv, qc, pcos + 256 * (k - 1), psin + 256 * (k - 1), 1, Hq, Hkv, st), "rgn_mrope_bf16")
                 ck(lib.rgn_lm_kv_append_bf16(pqkv, qc, pc, cap, row, 1, Hq, Hkv, st), "rgn_lm_kv_append_bf16")
                 ck(lib.rgn_lm_decode_attention_bf16(pqkv, pc, pa, row + 1, Hq, Hkv, scale, pws, ws_a, st), "rgn_lm_decode_attention_bf16")
-                ck(lib.rgn_lm_gemv_bf16(wo, pa, None, ph, ph, d, ad, st), "rgn_lm_gemv_bf16")
+                ck(gemv(*wo, pa, None, ph, ph, d, ad, st), gemv_name)
                 ck(lib.rgn_rms_norm_rows(ph, d, ln2, pn, d, 1, d, eps, st), "rgn_rms_norm_rows")
-                ck(lib.rgn_lm_gemv_bf16(wgu, pn, None, None, pff, 2 * F, d, st), "rgn_lm_gemv_bf16")
+                ck(gemv(*wgu, pn, None, None, pff, 2 * F, d, st), gemv_name)
                 ck(lib.rgn_swiglu_bf16(pff, 2 * F, pg, F, 1, F, st), "rgn_swiglu_bf16")
-                ck(lib.rgn_lm_gemv_bf16(wdown, pg, None, ph, ph, d, F, st), "rgn_lm_gemv_bf16")
+                ck(gemv(*wdown, pg, None, ph, ph, d, F, st), gemv_name)
             ck(lib.rgn_rms_norm_rows(ph, d, pfin, pn, d, 1, d, eps, st), "rgn_rms_norm_rows")
             pick(k)
         seq = ids[:L + n_new].to(input_ids.device)[None]

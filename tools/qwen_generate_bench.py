@@ -11,7 +11,13 @@ The GEMV A/B: rgn_lm_gemv_bf16 against the AdaLN helper rgn_gemv_bf16 (B = 1) at
 (new, parent, new again: the A/A arm gives the box's noise).  Each timed pass walks a ring of weight copies larger than the last-level
 cache, as a decode step finds its weights in HBM.  `not_slower`: new's median minus parent's is at most the A/A spread.
 
+`--weights fp8 | both` adopts the same module with the layers' projection matrices as fp8 e4m3fn (HipQwen25VLTextEncoder(weights="fp8"));
+with `both` the bf16 and the fp8 encoder are built from the one synthetic state dict and alternate run by run (keys `hip_*` and `hip_fp8_*`),
+the encoder call (`__call__`, the prefill alone) is timed for both, and every ratio is taken against the format's OWN streaming floor.  The
+GEMV A/B leg is then rgn_lm_gemv_w8 against rgn_lm_gemv_bf16 on the four layer shapes, each format walking its own ring of weight copies.
+
     python tools/qwen_generate_bench.py [--iters 5] [--out profiles/r14_qwen_generate_bench.json] [--ab-out profiles/r14_lm_gemv_ab.txt]
+    python tools/qwen_generate_bench.py --weights both --out profiles/r17_qwen_fp8_generate_bench.json --ab-out profiles/r17_lm_gemv_w8_ab.txt
     rocprofv3 --kernel-trace --stats -d DIR -o kt -- python tools/qwen_generate_bench.py --hip-only --no-ab --iters 2    # the kernel listing
 """
 import argparse
@@ -33,6 +39,7 @@ HBM_BYTES_PER_S = 6.3e12          # measured stream bandwidth (the microarchitec
 LENGTHS = (300, 1500)
 NEW = 64
 AB_SHAPES = ((4608, 3584), (3584, 3584), (37888, 3584), (3584, 18944), (152064, 3584))
+LAYER_SHAPES = AB_SHAPES[:4]      # q|k|v, o, gate|up, down: the matrices `weights="fp8"` quantises (lm_head stays bf16)
 RING_BYTES = 1 << 30              # weight copies walked per timed pass: four times the 256 MB last-level cache
 
 
@@ -48,10 +55,13 @@ def _stat(ts):
     return {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts)}
 
 
-def step_bytes(tc, n):
-    """Bytes one decode step reads: every decoder weight, lm_head, and n cache rows per layer."""
+def step_bytes(tc, n, weights="bf16"):
+    """Bytes one decode step reads: every decoder weight (fp8: one byte each plus one fp32 scale per output channel), lm_head (bf16 in
+    both formats), and n cache rows per layer."""
     d, F, hq, hkv, nl = tc.hidden_size, tc.intermediate_size, tc.num_attention_heads, tc.num_key_value_heads, tc.num_hidden_layers
     w = 2 * nl * (d * (hq + 2 * hkv) * 128 + hq * 128 * d + 3 * d * F)
+    if weights == "fp8":
+        w = w // 2 + 4 * nl * ((hq + 2 * hkv) * 128 + d + 2 * F + d)
     return {"decoder_weights": w, "lm_head": 2 * tc.vocab_size * d, "kv_cache": 2 * nl * n * 2 * hkv * 128}
 
 
@@ -105,6 +115,64 @@ def gemv_ab(rounds=7):
     return rows
 
 
+def gemv_w8_ab(rounds=7):
+    """rgn_lm_gemv_w8 against rgn_lm_gemv_bf16 on the layer shapes: arms alternating (fp8, bf16, fp8 again), each format over its own ring
+    of weight copies >= RING_BYTES (twice as many copies for fp8).  `not_slower`: the fp8 median is at most the bf16 median."""
+    from regione_amd import _lib, ops
+    lib = _lib.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    rows = []
+    for N, K in LAYER_SHAPES:
+        c16, c8 = max(2, -(-RING_BYTES // (2 * N * K))), max(2, -(-RING_BYTES // (N * K)))
+        g = torch.Generator(device="cuda").manual_seed(N + K)
+        W = torch.stack([(torch.randn(N, K, device="cuda", generator=g) * K ** -0.5).bfloat16() for _ in range(c16)])
+        W8 = torch.empty(c8, N, K, dtype=ops.FP8, device="cuda")
+        scales = []
+        for c in range(c8):
+            q = ops.quantize_w8(W[c % c16])
+            W8[c] = q
+            scales.append(q._rgn_scale)
+        x = torch.randn(K, device="cuda", generator=g).bfloat16()
+        y = torch.empty(N, dtype=torch.bfloat16, device="cuda")
+        p16, p8, px, py = [W[c].data_ptr() for c in range(c16)], [(W8[c].data_ptr(), scales[c].data_ptr()) for c in range(c8)], x.data_ptr(), y.data_ptr()
+
+        def fp8():
+            for p, s in p8:
+                lib.rgn_lm_gemv_w8(p, s, px, None, None, py, N, K, st)
+
+        def bf16():
+            for p in p16:
+                lib.rgn_lm_gemv_bf16(p, px, None, None, py, N, K, st)
+        lib.rgn_lm_gemv_w8(p8[0][0], p8[0][1], px, None, None, py, N, K, st)
+        a = y.clone()
+        lib.rgn_lm_gemv_bf16(p16[0], px, None, None, py, N, K, st)
+        max_diff = float((a.float() - y.float()).abs().max())                    # the quantisation of W, not a kernel error
+
+        def timed(fn, copies):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) * 1e3 / copies                            # us per GEMV
+        for fn, c in ((fp8, c8), (bf16, c16), (fp8, c8)):
+            timed(fn, c)
+        t = {"fp8": [], "bf16": [], "fp8_again": []}
+        for _ in range(rounds):                                                  # the arms alternate
+            t["fp8"].append(timed(fp8, c8))
+            t["bf16"].append(timed(bf16, c16))
+            t["fp8_again"].append(timed(fp8, c8))
+        med = {k: statistics.median(v) for k, v in t.items()}
+        rows.append(dict(N=N, K=K, copies_fp8=c8, copies_bf16=c16, fp8_us=med["fp8"], bf16_us=med["bf16"], fp8_again_us=med["fp8_again"],
+                         aa_spread_us=abs(med["fp8"] - med["fp8_again"]), fp8_min_us=min(t["fp8"]), fp8_max_us=max(t["fp8"]),
+                         bf16_min_us=min(t["bf16"]), bf16_max_us=max(t["bf16"]), fp8_tb_per_s=N * K / med["fp8"] / 1e6,
+                         bf16_tb_per_s=2 * N * K / med["bf16"] / 1e6, fp8_over_bf16=med["fp8"] / med["bf16"],
+                         not_slower=bool(med["fp8"] <= med["bf16"]), max_abs_diff_of_outputs=max_diff))
+        del W, W8
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
@@ -113,13 +181,30 @@ def main():
     ap.add_argument("--hip-only", action="store_true", help="only the HIP calls (for a kernel-trace run)")
     ap.add_argument("--no-ab", action="store_true", help="skip the GEMV A/B")
     ap.add_argument("--no-generate", action="store_true", help="only the GEMV A/B")
+    ap.add_argument("--weights", choices=("bf16", "fp8", "both"), default="bf16", help="format of the layers' projection matrices")
     a = ap.parse_args()
     from regione_amd import build
     sha = build.csrc_hash()
     res = {"device": torch.cuda.get_device_name(0), "csrc_sha16": sha, "iters": a.iters, "new_tokens": NEW,
            "stat": "median and min / max of warm, synchronised runs, the two sides alternating; ms per new token = (t64 - t1) / 63 of the medians",
            "model": "Qwen2.5-VL-7B language model, seeded init, text-only ids, no EOS", "hbm_bytes_per_s": HBM_BYTES_PER_S}
-    if not a.no_ab:
+    if not a.no_ab and a.weights != "bf16":
+        rows = gemv_w8_ab()
+        res["gemv_w8_ab"] = rows
+        lines = [f"# rgn_lm_gemv_w8 (fp8 e4m3fn weights, per-channel scale) against rgn_lm_gemv_bf16 on the four layer shapes: median us per GEMV of 7",
+                 f"# alternating rounds, each format over its own ring of weight copies >= {RING_BYTES >> 20} MiB; A/A = |median(fp8) - median(fp8 again)|.",
+                 f"# csrc_sha16 {sha}  {res['device']}",
+                 f"{'N':>7} {'K':>6} {'fp8 us':>9} {'[min':>8} {'max]':>8} {'bf16 us':>9} {'[min':>8} {'max]':>8} {'fp8 again':>10} {'A/A us':>7} {'fp8 TB/s':>9} "
+                 f"{'bf16 TB/s':>10} {'fp8/bf16':>9}  not_slower"]
+        for r in rows:
+            lines.append(f"{r['N']:>7} {r['K']:>6} {r['fp8_us']:>9.2f} {r['fp8_min_us']:>8.2f} {r['fp8_max_us']:>8.2f} {r['bf16_us']:>9.2f} "
+                         f"{r['bf16_min_us']:>8.2f} {r['bf16_max_us']:>8.2f} {r['fp8_again_us']:>10.2f} {r['aa_spread_us']:>7.2f} "
+                         f"{r['fp8_tb_per_s']:>9.2f} {r['bf16_tb_per_s']:>10.2f} {r['fp8_over_bf16']:>9.3f}  {r['not_slower']}")
+        print("\n".join(lines), flush=True)
+        if a.ab_out:
+            with open(a.ab_out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+    elif not a.no_ab:
         rows = gemv_ab()
         res["gemv_ab"] = rows
         lines = [f"# rgn_lm_gemv_bf16 (new) against rgn_gemv_bf16 B = 1 (parent): median us per GEMV of 7 alternating rounds, each pass over a",
@@ -143,13 +228,25 @@ def main():
             mod = Qwen2_5_VLForConditionalGeneration(cfg).eval()
         mod = mod.to(torch.bfloat16)
         torch.cuda.empty_cache()
-        hip = QT.HipQwen25VLTextEncoder(mod)
+        # the encoders by key prefix: "hip" is the bf16 adoption (today's keys), "hip_fp8" the fp8 one; both read the one module
+        encs = {}
+        if a.weights in ("bf16", "both"):
+            encs["hip"] = QT.HipQwen25VLTextEncoder(mod)
+        if a.weights in ("fp8", "both"):
+            encs["hip_fp8"] = QT.HipQwen25VLTextEncoder(mod, weights="fp8")
+        fmt = {"hip": "bf16", "hip_fp8": "fp8"}
+        res["weights"] = a.weights
+        hip = next(iter(encs.values()))
         g = torch.Generator().manual_seed(1)
         for L in LENGTHS:
             ids = torch.randint(0, 151000, (1, L), generator=g).cuda()
             kw = dict(input_ids=ids, attention_mask=torch.ones_like(ids))
-            arms = {"hip_1": lambda: hip.generate(**kw, max_new_tokens=1, eos_token_id=[]),
-                    "hip_64": lambda: hip.generate(**kw, max_new_tokens=NEW, eos_token_id=[])}
+            arms = {}
+            for name, enc in encs.items():
+                arms[f"{name}_1"] = lambda enc=enc: enc.generate(**kw, max_new_tokens=1, eos_token_id=[])
+                arms[f"{name}_64"] = lambda enc=enc: enc.generate(**kw, max_new_tokens=NEW, eos_token_id=[])
+                if a.weights != "bf16":
+                    arms[f"{name}_call"] = lambda enc=enc: enc(**kw)             # the encoder call: the prefill alone
             if not a.hip_only:
                 ek = dict(do_sample=False, eos_token_id=None, pad_token_id=0)
                 arms["eager_1"] = lambda: mod.generate(**kw, max_new_tokens=1, min_new_tokens=1, **ek)
@@ -170,14 +267,24 @@ def main():
                     r["tokens_equal_to_eager_note"] = ("of 64; informative only: the logits of a seeded-init model over 152064 words are near-ties that "
                                                        "bf16 rounding decides, and after the first difference the two sides decode different "
                                                        "sequences (tests/test_gpu_qwen_generate.py bounds the logits against fp32 instead)")
-            b = step_bytes(tc, L + NEW // 2)
+            for name in list(encs)[1:]:
+                assert encs[name].generate(**kw, max_new_tokens=NEW, eos_token_id=[]).shape[1] == L + NEW
+            bytes_of = {side: step_bytes(tc, L + NEW // 2, fmt.get(side, "bf16")) for side in (*encs, "eager")}
+            b = bytes_of[next(iter(encs))]                                       # the printed floor: fp8's when fp8 is what runs
             r["step_bytes"] = dict(b, total=sum(b.values()))
             r["streaming_floor_ms"] = sum(b.values()) / HBM_BYTES_PER_S * 1e3
-            for side in ("hip", "eager"):
+            for side in (*encs, "eager"):
                 if f"{side}_64" in r:
+                    sb = sum(bytes_of[side].values())
                     per = (r[f"{side}_64"]["median_ms"] - r[f"{side}_1"]["median_ms"]) / (NEW - 1)
                     r[f"{side}_ms_per_new_token"], r[f"{side}_prefill_ms"] = per, r[f"{side}_1"]["median_ms"]
-                    r[f"{side}_share_of_hbm_bw"] = sum(b.values()) / (per * 1e-3) / HBM_BYTES_PER_S
+                    r[f"{side}_share_of_hbm_bw"] = sb / (per * 1e-3) / HBM_BYTES_PER_S
+                    if a.weights != "bf16":
+                        r[f"{side}_step_bytes"], r[f"{side}_streaming_floor_ms"] = sb, sb / HBM_BYTES_PER_S * 1e3
+                        r[f"{side}_ms_per_new_token_over_its_floor"] = per / (sb / HBM_BYTES_PER_S * 1e3)
+            if len(encs) == 2:
+                r["fp8_over_bf16_ms_per_new_token"] = r["hip_fp8_ms_per_new_token"] / r["hip_ms_per_new_token"]
+                r["fp8_over_bf16_call"] = r["hip_fp8_call"]["median_ms"] / r["hip_call"]["median_ms"]
             res[f"L{L}"] = r
             print(f"L{L}", json.dumps(r), flush=True)
     if a.out:
