@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 114
+#define RGN_ABI_VERSION 115
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -556,6 +556,70 @@ int rgn_head_rms_norm_bf16(void* QKV, int ld, const void* wq, const void* wk, in
  * p.  p, resid, y [M, N] bf16 with row strides ldp, ldr, ldy (>= N, multiples of 8), gate bf16 [N]; N % 8 == 0; all 16-byte aligned.
  * y may be resid. */
 int rgn_gate_resid_rows(const void* p, int ldp, const void* gate, const void* resid, int ldr, void* y, int ldy, int M, int N, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * a10  one masked MMDiT block per call (csrc/block.hip: host code only, no kernel of its own).  The entries make the launches the
+ * harness blocks make (regione_amd/harness/flux.py, FUSE_QKV path), in their order and with their arguments, through the library's own
+ * rgn_ln_modulate, rgn_gemm_group (RGN_EPI_QKV / RGN_EPI_GELU / RGN_EPI_GATE_RESID), rgn_attention_bounded and rgn_rowband_*: a caller
+ * needs neither the launch order, nor the buffer layout, nor the K / V^T slab protocol, nor the row-band rules.
+ *
+ * Buffers (caller-owned, bf16, rows [text 0..T) ; image T..T+M)): x [T+M, d] the residual stream, updated in place; nrm [T+M, d]
+ * scratch (LN-modulate output); wide [T+M, 3 d + d_ff] scratch, columns [k | v | q | mlp] (K and V columns are never written: they go
+ * to the slabs).  heads * 128 == d.
+ * AdaLN vectors (bf16, Modulation.chunk order): double block adaln / adaln_txt = [6 d] of the image / text stream =
+ * (shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp); single block adaln = [3 d] = (shift, scale, gate), adaln_txt unused.
+ * Weights: rgn_block_weight = (W, wscale, bias) with wscale != NULL meaning fp8 exactly as in rgn_gemm_problem; every W is dense.
+ *   double: w_kvq / w_add_kvq [3 d, d] (rows k | v | q), w_out / w_add_out [d, d], ff_w1 / ffc_w1 [d_ff, d], ff_w2 / ffc_w2 [d, d_ff]
+ *           (the `add` / `ffc` ones belong to the text stream); norm_q, norm_k, norm_added_q, norm_added_k [128];
+ *   single: w_kvqm [3 d + d_ff, d] (rows k | v | q | mlp), w_po [d, d + d_ff]; norm_q, norm_k.
+ * K / V destination, as the attention processor's kv_target returns it: k_slab [skv_pad, d], vt_slab [d, skv_pad], attention over the
+ * first skv rows.  kv_rows == NULL: identity rows (a plain or a store step; skv_pad >= T + M).  kv_rows != NULL (int64 [T + M]): a
+ * partial update, the K / V columns take the fp16 round trip (fp16_roundtrip = 1: every row of a single block, the image rows of a
+ * double block).  cos_q / sin_q: rotary rows of this call's rows; cos_k / sin_k: rotary rows by CACHE row.
+ * score_bound: as rgn_attention_bounded (0 = running maximum).  gemm_ws / attn_ws: the workspaces of rgn_gemm_group / rgn_attention,
+ * same rules (NULL = plain launches, one per stream).
+ * rowbands = 1: rgn_rowband_join(stream) before the attention and rgn_rowband_fork(stream) behind it, so that the row-wise stages from
+ * there to the next block's attention run as two bands; the caller joins behind the last block of the chain.
+ * RGN_E_UNSUPPORTED (these stay with the caller): an odd head count, out_rows != 0 (the row-skipping last block), branches != 1
+ * (several CFG branches in one call).  Bad arguments (a NULL buffer, d % 64, d_ff % 64, heads * 128 != d, T < 0, M <= 0, a pointer that
+ * is not 16-byte aligned, a stride that is no multiple of 8, skv_pad % 64, skv_pad < skv, skv < 1) give RGN_E_BADARG before any launch.
+ * Zero the descriptor first: the fields a block kind does not read (single block: adaln_txt, norm_added_q / k and the eight double-block
+ * weights; double block: w_kvqm, w_po) must be NULL - the pointer checks run over the whole struct, so garbage there is RGN_E_BADARG.
+ * M is explicit (not derived from the buffers): x, nrm and wide may hold more rows than the T + M this call uses.
+ *
+ * rgn_mmdit_double_block replaces FluxTransformerBlock.forward [EXT] with RegoionEFluxAttnProcessor2_0.__call__ inside it,
+ *   FluxKontext/inplace.py:518-524 (call site) and :704-824: LN-modulate (two segments) -> Q/K/V pair with the fused epilogue ->
+ *   attention -> output-projection pair (gate + residual) -> LN-modulate -> FF-up pair (GELU) -> FF-down pair (gate + residual).
+ * rgn_mmdit_single_block replaces FluxSingleTransformerBlock.forward [EXT], FluxKontext/inplace.py:549-555 and :704-824:
+ *   LN-modulate -> fused k | v | q | mlp GEMM -> attention -> proj_out (gate + residual).
+ * rgn_mmdit_block_bytes() = sizeof(rgn_mmdit_block) as the library sees it (a binding compares it at load). */
+typedef struct rgn_block_weight {
+    const void* W;
+    const float* wscale;
+    const void* bias;
+} rgn_block_weight;
+typedef struct rgn_mmdit_block {
+    void* x; void* nrm; void* wide;
+    int ldx, ldnrm, ldwide;
+    int T, M, d, d_ff, heads;
+    const void* adaln; const void* adaln_txt;
+    rgn_block_weight w_kvq, w_add_kvq, w_out, w_add_out, ff_w1, ffc_w1, ff_w2, ffc_w2;     /* double block */
+    rgn_block_weight w_kvqm, w_po;                                                         /* single block */
+    const void* norm_q; const void* norm_k; const void* norm_added_q; const void* norm_added_k;
+    void* k_slab; void* vt_slab;
+    const int64_t* kv_rows;
+    const float* cos_q; const float* sin_q; const float* cos_k; const float* sin_k;
+    int skv, skv_pad;
+    float score_bound;
+    int rowbands;
+    int out_rows;              /* 0; anything else asks for the row-skipping last block: RGN_E_UNSUPPORTED */
+    int branches;              /* 1; anything else asks for several CFG branches in one call: RGN_E_UNSUPPORTED */
+    void* gemm_ws; size_t gemm_ws_bytes;
+    void* attn_ws; size_t attn_ws_bytes;
+} rgn_mmdit_block;
+int rgn_mmdit_double_block(const rgn_mmdit_block* b, void* stream);
+int rgn_mmdit_single_block(const rgn_mmdit_block* b, void* stream);
+size_t rgn_mmdit_block_bytes(void);
 
 /* Device properties the host side needs for roofline reporting (no torch types). */
 int rgn_device_info(int* cu_count, int* clock_khz, size_t* hbm_bytes);

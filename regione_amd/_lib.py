@@ -43,6 +43,26 @@ class GemmProblem(C.Structure):
 
 _prob_p = C.POINTER(GemmProblem)
 
+
+class BlockWeight(C.Structure):
+    """struct rgn_block_weight (include/regione_hip.h): W, its fp8 per-channel scale (NULL = bf16 weights) and the bias."""
+    _fields_ = [("W", _c_void_p), ("wscale", _c_void_p), ("bias", _c_void_p)]
+
+
+class MmditBlock(C.Structure):
+    """struct rgn_mmdit_block (include/regione_hip.h): one masked MMDiT block, the descriptor of rgn_mmdit_double_block /
+    rgn_mmdit_single_block.  lib() compares its size with rgn_mmdit_block_bytes()."""
+    _fields_ = ([("x", _c_void_p), ("nrm", _c_void_p), ("wide", _c_void_p), ("ldx", _c_int), ("ldnrm", _c_int), ("ldwide", _c_int),
+                 ("T", _c_int), ("M", _c_int), ("d", _c_int), ("d_ff", _c_int), ("heads", _c_int), ("adaln", _c_void_p), ("adaln_txt", _c_void_p)]
+                + [(n, BlockWeight) for n in ("w_kvq", "w_add_kvq", "w_out", "w_add_out", "ff_w1", "ffc_w1", "ff_w2", "ffc_w2", "w_kvqm", "w_po")]
+                + [(n, _c_void_p) for n in ("norm_q", "norm_k", "norm_added_q", "norm_added_k", "k_slab", "vt_slab", "kv_rows", "cos_q", "sin_q",
+                                            "cos_k", "sin_k")]
+                + [("skv", _c_int), ("skv_pad", _c_int), ("score_bound", _c_float), ("rowbands", _c_int), ("out_rows", _c_int), ("branches", _c_int),
+                   ("gemm_ws", _c_void_p), ("gemm_ws_bytes", C.c_size_t), ("attn_ws", _c_void_p), ("attn_ws_bytes", C.c_size_t)])
+
+
+_block_p = C.POINTER(MmditBlock)
+
 # name -> argtypes (restype is always int unless listed in _RESTYPE)
 SIGNATURES = {
     "rgn_version": [],
@@ -134,11 +154,15 @@ SIGNATURES = {
     "rgn_masked_mean_rows": [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_void_p, _c_void_p],
     "rgn_head_rms_norm_bf16": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_float, _c_void_p],
     "rgn_gate_resid_rows": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p],
+    # a10: one masked MMDiT block per call (csrc/block.hip)
+    "rgn_mmdit_double_block": [_block_p, _c_void_p],
+    "rgn_mmdit_single_block": [_block_p, _c_void_p],
+    "rgn_mmdit_block_bytes": [],
 }
 _RESTYPE = {"rgn_last_error": C.c_char_p, "rgn_abi_struct_bytes": C.c_size_t, "rgn_attention_workspace_bytes": C.c_size_t,
             "rgn_gemm_workspace_bytes": C.c_size_t, "rgn_groupnorm_workspace_bytes": C.c_size_t,
             "rgn_groupnorm_partial_bytes": C.c_size_t, "rgn_lm_decode_attention_workspace_bytes": C.c_size_t,
-            "rgn_lm_head_workspace_bytes": C.c_size_t, "rgn_rowband_side_launches": C.c_longlong}
+            "rgn_lm_head_workspace_bytes": C.c_size_t, "rgn_rowband_side_launches": C.c_longlong, "rgn_mmdit_block_bytes": C.c_size_t}
 
 _lib = None
 
@@ -173,6 +197,9 @@ def lib():
     if h.rgn_abi_struct_bytes() != want:
         raise RegionEHipError(f"{LIB_PATH}: struct layout {h.rgn_abi_struct_bytes()} != the Python binding's {want} "
                               f"(library ABI version {h.rgn_version()}): rebuild with `python -m regione_amd.build --force`")
+    if h.rgn_mmdit_block_bytes() != C.sizeof(MmditBlock):
+        raise RegionEHipError(f"{LIB_PATH}: sizeof(rgn_mmdit_block) {h.rgn_mmdit_block_bytes()} != the Python binding's {C.sizeof(MmditBlock)}: "
+                              "rebuild with `python -m regione_amd.build --force`")
     _lib = h
     return h
 

@@ -18,6 +18,7 @@
 // | cfg_combine              | inplace.py:364; Step1XEdit/inplace.py:401-410; QwenImageEdit/inplace.py:401-405         |
 // | kv_partial_update_[pair_|group_] | _partially_linear x2 + norm_k + RoPE into the caches, inplace.py:734-794, fused_kernels.py:81-101 |
 // | region_attention         | flash_attn_func / SDPA of the edited-token queries vs the full cache, inplace.py:796-806 |
+// | mmdit_double_block_ / mmdit_single_block_ | one whole masked block, inplace.py:518-524 / :549-555 with :704-824 inside      |
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -381,12 +382,140 @@ void gate_resid_rows_(const Tensor& p, const Tensor& gate, const Tensor& resid, 
                                  (int)p.size(0), (int)p.size(1), stream_of(p)), "rgn_gate_resid_rows");
 }
 
+// ---- one masked MMDiT block per call (csrc/block.hip) --------------------------------------------------------------------------
+// Everything the C entry reads is checked here by EXTENT (rows of the activation buffers, weight shapes, AdaLN vector lengths, rotary
+// rows, slab shapes against skv, kv_rows length): a C++ / AOT caller gets a TORCH_CHECK failure, never an out-of-bounds device access.
+rgn_block_weight block_weight(const char* op, const char* name, const Tensor& like, at::TensorList w, const c10::List<OptTensor>& sc,
+                              const c10::List<OptTensor>& bs, size_t i, int64_t N, int64_t K) {
+    const Tensor& t = w[i];
+    TORCH_CHECK(t.device() == like.device() && t.dim() == 2 && t.size(0) == N && t.size(1) == K && t.is_contiguous() &&
+                    (t.scalar_type() == at::kBFloat16 || is_fp8(t)), op, ": ", name, " must be a contiguous bf16 or fp8 [", N, ", ", K, "] on the activations' device");
+    OptTensor s = sc.size() ? OptTensor(sc.get(i)) : OptTensor(), b = OptTensor(bs.get(i));
+    const bool have_s = s.has_value() && s->defined();
+    TORCH_CHECK(is_fp8(t) == have_s, op, ": ", name, ": an fp8 weight needs its per-output-channel scale, a bf16 weight takes none");
+    TORCH_CHECK(!have_s || (s->scalar_type() == at::kFloat && s->numel() == N && s->is_contiguous() && s->device() == like.device()),
+                op, ": scale of ", name, " must be fp32 [", N, "], contiguous, on the activations' device");
+    TORCH_CHECK(!(b.has_value() && b->defined()) || (b->scalar_type() == at::kBFloat16 && b->dim() == 1 && b->numel() == N && b->is_contiguous() &&
+                                                     b->device() == like.device()), op, ": bias of ", name, " must be bf16 [", N, "], contiguous");
+    rgn_block_weight r;
+    r.W = ptr(t); r.wscale = (const float*)ptr(s); r.bias = ptr(b);
+    return r;
+}
+
+// the part of the descriptor both block kinds share
+rgn_mmdit_block block_common(const char* op, const Tensor& x, const Tensor& nrm, const Tensor& wide, int64_t d_ff, at::TensorList norms, size_t n_norms,
+                             const Tensor& cos_q, const Tensor& sin_q, const Tensor& cos_k, const Tensor& sin_k, const OptTensor& kv_rows,
+                             const Tensor& k_cache, const Tensor& vt_cache, int64_t T, int64_t M, int64_t heads, int64_t skv, double score_bound,
+                             bool rowbands) {
+    TORCH_CHECK(heads > 0 && T >= 0 && M > 0 && T + M < (int64_t(1) << 31), op, ": heads > 0, T >= 0, M > 0");
+    const int64_t d = heads * 128, R = T + M;
+    TORCH_CHECK(d_ff > 0, op, ": d_ff must be positive");
+    for (const Tensor* t : {&x, &nrm, &wide})
+        TORCH_CHECK(t->is_cuda() && t->device() == x.device() && t->scalar_type() == at::kBFloat16 && t->dim() == 2 && t->stride(1) == 1 && t->size(0) >= R,
+                    op, ": x / nrm / wide must be bf16 [>= T + M = ", R, " rows, cols] HIP tensors with unit column stride on one device");
+    for (const Tensor* t : {&x, &nrm, &wide})        // the descriptor carries row strides as int
+        TORCH_CHECK(t->stride(0) >= t->size(1) && t->stride(0) < (int64_t(1) << 31), op, ": row stride ", t->stride(0), " of x / nrm / wide out of range");
+    TORCH_CHECK(x.size(1) == d && nrm.size(1) == d, op, ": x / nrm need heads * 128 = ", d, " columns");
+    TORCH_CHECK(wide.size(1) == 3 * d + d_ff, op, ": wide needs 3 d + d_ff = ", 3 * d + d_ff, " columns [k | v | q | mlp], got ", wide.size(1));
+    TORCH_CHECK(norms.size() == n_norms, op, ": ", n_norms, " per-head RMSNorm weight vectors");
+    for (const Tensor& t : norms)
+        TORCH_CHECK(t.device() == x.device() && t.scalar_type() == at::kBFloat16 && t.numel() == 128 && t.is_contiguous(), op, ": per-head RMSNorm weights: bf16 [128]");
+    TORCH_CHECK(cos_q.sizes() == sin_q.sizes() && cos_k.sizes() == sin_k.sizes(), op, ": cos / sin of one rotary table differ in shape");
+    for (const Tensor* t : {&cos_q, &sin_q, &cos_k, &sin_k})
+        TORCH_CHECK(t->device() == x.device() && t->scalar_type() == at::kFloat && t->dim() == 2 && t->size(1) == 128 && t->is_contiguous(),
+                    op, ": rotary tables: fp32 [rows, 128], contiguous, on the activations' device");
+    TORCH_CHECK(cos_q.size(0) >= R, op, ": rotary table of the queries has ", cos_q.size(0), " rows, the block needs ", R);
+    TORCH_CHECK(k_cache.device() == x.device() && vt_cache.device() == x.device() && k_cache.scalar_type() == at::kBFloat16 &&
+                    vt_cache.scalar_type() == at::kBFloat16 && k_cache.dim() == 2 && vt_cache.dim() == 2 && k_cache.size(1) == d && vt_cache.size(0) == d &&
+                    vt_cache.size(1) == k_cache.size(0) && k_cache.is_contiguous() && vt_cache.is_contiguous() && k_cache.size(0) % 64 == 0,
+                op, ": K slab bf16 [skv_pad, d] / V^T slab bf16 [d, skv_pad], contiguous, skv_pad a multiple of 64");
+    const int64_t skv_pad = k_cache.size(0);
+    TORCH_CHECK(skv >= 1 && skv <= skv_pad, op, ": skv = ", skv, " outside the cache slab's ", skv_pad, " rows");
+    const bool have_rows = kv_rows.has_value() && kv_rows->defined();
+    if (have_rows) {
+        // the VALUES are device data and are not checked (no host sync per launch): the caller guarantees max(kv_rows) < min(cos_k rows, skv)
+        TORCH_CHECK(kv_rows->device() == x.device() && kv_rows->scalar_type() == at::kLong && kv_rows->dim() == 1 && kv_rows->is_contiguous() &&
+                        kv_rows->numel() == R, op, ": kv_rows must be int64 [T + M = ", R, "], contiguous");
+        TORCH_CHECK(cos_k.size(0) >= skv && skv >= R, op, ": the key rotary table (", cos_k.size(0), " rows) must cover the ", skv,
+                    " cache rows, which must hold the ", R, " distinct rows kv_rows names");
+    } else {
+        TORCH_CHECK(R <= skv, op, ": identity cache rows [0, ", R, ") exceed skv = ", skv);
+        TORCH_CHECK(cos_k.size(0) >= R, op, ": rotary table of the keys has ", cos_k.size(0), " rows, the block needs ", R);
+    }
+    Tensor gws = gemm_ws(x), aws = attn_ws(x);
+    rgn_mmdit_block b = {};
+    b.x = x.data_ptr(); b.nrm = nrm.data_ptr(); b.wide = wide.data_ptr();
+    b.ldx = (int)x.stride(0); b.ldnrm = (int)nrm.stride(0); b.ldwide = (int)wide.stride(0);
+    b.T = (int)T; b.M = (int)M; b.d = (int)d; b.d_ff = (int)d_ff; b.heads = (int)heads;
+    b.norm_q = ptr(norms[0]); b.norm_k = ptr(norms[1]);
+    if (n_norms == 4) { b.norm_added_q = ptr(norms[2]); b.norm_added_k = ptr(norms[3]); }
+    b.k_slab = k_cache.data_ptr(); b.vt_slab = vt_cache.data_ptr(); b.kv_rows = (const int64_t*)ptr(kv_rows);
+    b.cos_q = (const float*)ptr(cos_q); b.sin_q = (const float*)ptr(sin_q); b.cos_k = (const float*)ptr(cos_k); b.sin_k = (const float*)ptr(sin_k);
+    b.skv = (int)skv; b.skv_pad = (int)skv_pad; b.score_bound = (float)score_bound; b.rowbands = rowbands ? 1 : 0; b.out_rows = 0; b.branches = 1;
+    b.gemm_ws = gws.data_ptr(); b.gemm_ws_bytes = (size_t)gws.numel() * 4; b.attn_ws = aws.data_ptr(); b.attn_ws_bytes = (size_t)aws.numel() * 4;
+    return b;
+}
+
+const void* adaln_vec(const char* op, const Tensor& v, const Tensor& like, int64_t n) {
+    TORCH_CHECK(v.device() == like.device() && v.scalar_type() == at::kBFloat16 && v.is_contiguous() && v.numel() == n, op,
+                ": AdaLN vector must be bf16 [", n, "], contiguous, on the activations' device (got ", v.numel(), " elements)");
+    return ptr(v);
+}
+
+void check_lists(const char* op, at::TensorList w, const c10::List<OptTensor>& sc, const c10::List<OptTensor>& bs, size_t n) {
+    TORCH_CHECK(w.size() == n && (sc.size() == 0 || sc.size() == n) && bs.size() == n, op, ": ", n, " weights, ", n, " (or no) scales, ", n, " biases");
+}
+
+void mmdit_double_block_(Tensor x, Tensor nrm, Tensor wide, const Tensor& adaln_img, const Tensor& adaln_txt, at::TensorList weights,
+                         const c10::List<OptTensor>& scales, const c10::List<OptTensor>& biases, at::TensorList norms, const Tensor& cos_q,
+                         const Tensor& sin_q, const Tensor& cos_k, const Tensor& sin_k, const OptTensor& kv_rows, Tensor k_cache, Tensor vt_cache,
+                         int64_t T, int64_t M, int64_t heads, int64_t skv, double score_bound, bool rowbands) {
+    const char* op = "mmdit_double_block_";
+    ptr(x);
+    RGN_DEVICE_GUARD(x);
+    check_lists(op, weights, scales, biases, 8);
+    TORCH_CHECK(weights[4].dim() == 2, op, ": ff_w1 must be [d_ff, d]");
+    const int64_t d = heads * 128, ff = weights[4].size(0);
+    rgn_mmdit_block b = block_common(op, x, nrm, wide, ff, norms, 4, cos_q, sin_q, cos_k, sin_k, kv_rows, k_cache, vt_cache, T, M, heads, skv,
+                                     score_bound, rowbands);
+    b.adaln = adaln_vec(op, adaln_img, x, 6 * d);
+    b.adaln_txt = adaln_vec(op, adaln_txt, x, 6 * d);
+    b.w_kvq = block_weight(op, "w_kvq", x, weights, scales, biases, 0, 3 * d, d);
+    b.w_add_kvq = block_weight(op, "w_add_kvq", x, weights, scales, biases, 1, 3 * d, d);
+    b.w_out = block_weight(op, "w_out", x, weights, scales, biases, 2, d, d);
+    b.w_add_out = block_weight(op, "w_add_out", x, weights, scales, biases, 3, d, d);
+    b.ff_w1 = block_weight(op, "ff_w1", x, weights, scales, biases, 4, ff, d);
+    b.ffc_w1 = block_weight(op, "ffc_w1", x, weights, scales, biases, 5, ff, d);
+    b.ff_w2 = block_weight(op, "ff_w2", x, weights, scales, biases, 6, d, ff);
+    b.ffc_w2 = block_weight(op, "ffc_w2", x, weights, scales, biases, 7, d, ff);
+    check_rc(rgn_mmdit_double_block(&b, stream_of(x)), "rgn_mmdit_double_block");
+}
+
+void mmdit_single_block_(Tensor x, Tensor nrm, Tensor wide, const Tensor& adaln, at::TensorList weights, const c10::List<OptTensor>& scales,
+                         const c10::List<OptTensor>& biases, at::TensorList norms, const Tensor& cos_q, const Tensor& sin_q, const Tensor& cos_k,
+                         const Tensor& sin_k, const OptTensor& kv_rows, Tensor k_cache, Tensor vt_cache, int64_t T, int64_t M, int64_t heads,
+                         int64_t skv, double score_bound, bool rowbands) {
+    const char* op = "mmdit_single_block_";
+    ptr(x);
+    RGN_DEVICE_GUARD(x);
+    check_lists(op, weights, scales, biases, 2);
+    TORCH_CHECK(weights[1].dim() == 2, op, ": w_po must be [d, d + d_ff]");
+    const int64_t d = heads * 128, ff = weights[1].size(1) - d;
+    rgn_mmdit_block b = block_common(op, x, nrm, wide, ff, norms, 2, cos_q, sin_q, cos_k, sin_k, kv_rows, k_cache, vt_cache, T, M, heads, skv,
+                                     score_bound, rowbands);
+    b.adaln = adaln_vec(op, adaln, x, 3 * d);
+    b.w_kvqm = block_weight(op, "w_kvqm", x, weights, scales, biases, 0, 3 * d + ff, d);
+    b.w_po = block_weight(op, "w_po", x, weights, scales, biases, 1, d, d + ff);
+    check_rc(rgn_mmdit_single_block(&b, stream_of(x)), "rgn_mmdit_single_block");
+}
+
 }  // namespace
 
 // the header this binding was compiled against: regione_amd/torch_ops.py compares both with libregione_hip.so's rgn_version() /
 // rgn_abi_struct_bytes() before the first op runs (rgn_qkv_epilogue / rgn_gemm_problem travel by pointer)
 extern "C" int rgn_torch_binding_abi_version(void) { return RGN_ABI_VERSION; }
 extern "C" size_t rgn_torch_binding_struct_bytes(void) { return sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem); }
+extern "C" size_t rgn_torch_binding_block_bytes(void) { return sizeof(rgn_mmdit_block); }
 
 // the schemas: identical to regione_amd/torch_ops.py (SCHEMAS there is the single source the tests compare both against)
 TORCH_LIBRARY(regione_mi, m) {
@@ -414,6 +543,13 @@ TORCH_LIBRARY(regione_mi, m) {
     m.def("masked_mean_rows(Tensor x, int n_valid, float scale=1.0) -> Tensor");
     m.def("head_rms_norm_(Tensor(a!) qkv, Tensor wq, Tensor wk, int heads, float eps=1e-6) -> ()");
     m.def("gate_resid_rows_(Tensor p, Tensor gate, Tensor resid, Tensor(a!) out) -> ()");
+    // one masked MMDiT block per call (regione_amd/torch_ops.py: BLOCK_SCHEMAS)
+    m.def("mmdit_double_block_(Tensor(a!) x, Tensor(b!) nrm, Tensor(c!) wide, Tensor adaln_img, Tensor adaln_txt, Tensor[] weights, "
+          "Tensor?[] scales, Tensor?[] biases, Tensor[] norms, Tensor cos_q, Tensor sin_q, Tensor cos_k, Tensor sin_k, Tensor? kv_rows, "
+          "Tensor(d!) k_cache, Tensor(e!) vt_cache, int T, int M, int heads, int skv, float score_bound, bool rowbands=False) -> ()");
+    m.def("mmdit_single_block_(Tensor(a!) x, Tensor(b!) nrm, Tensor(c!) wide, Tensor adaln, Tensor[] weights, "
+          "Tensor?[] scales, Tensor?[] biases, Tensor[] norms, Tensor cos_q, Tensor sin_q, Tensor cos_k, Tensor sin_k, Tensor? kv_rows, "
+          "Tensor(d!) k_cache, Tensor(e!) vt_cache, int T, int M, int heads, int skv, float score_bound, bool rowbands=False) -> ()");
 }
 
 // CUDA is the dispatch key of HIP tensors in PyTorch-ROCm; no CPU kernels are registered (a CPU tensor fails loudly)
@@ -432,4 +568,6 @@ TORCH_LIBRARY_IMPL(regione_mi, CUDA, m) {
     m.impl("masked_mean_rows", &masked_mean_rows);
     m.impl("head_rms_norm_", &head_rms_norm_);
     m.impl("gate_resid_rows_", &gate_resid_rows_);
+    m.impl("mmdit_double_block_", &mmdit_double_block_);
+    m.impl("mmdit_single_block_", &mmdit_single_block_);
 }

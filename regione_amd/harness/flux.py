@@ -322,6 +322,7 @@ class FwdCtx:
         # next block's processor joins before its own
         self.rowbands = False
         self.forked = False               # between ops.rowband_fork and ops.rowband_join
+        self.block_ops = False            # set by a forward of a trunk whose blocks BLOCK_OPS covers
 
 
 # ---------------------------------------------------------------------------------------------
@@ -342,6 +343,12 @@ ATTN_BRANCH_STREAMS = True
 # that have the chip to themselves) and under the plan override rowbands=0.
 ROW_BANDS = True
 CFG_PAIR = False          # set by dist.run_cfg_branches while the forwards of a CFG step run: no row bands there
+# BLOCK_OPS: a block of a single-branch forward is ONE op call (regione_mi.mmdit_double_block_ / mmdit_single_block_ -> rgn_mmdit_*_block,
+# csrc/block.hip) instead of the launch-by-launch sequence below: the same launches with the same arguments, bit-identical.  Taken only
+# with FUSE_QKV, an even head count, a FluxAttnProcessor (or a subclass that keeps its __call__: the RegionE processors) and not for the
+# row-skipping last block, and only in trunks that declare it (`FluxTransformer2DModel.block_ops`: FLUX and Step1X; Qwen's double-stream
+# trunk is not covered); everything else, and every `multi` path, runs the Python sequence.
+BLOCK_OPS = False
 
 
 class Attention:
@@ -559,6 +566,29 @@ class FluxAttnProcessor:
         ops.gemm_group(group, epilogue=ops.EPI_GATE_RESID)
 
 
+def _block_op_target(block, ctx, image_rotary_emb):
+    """BLOCK_OPS: None when `block` has to run its Python sequence, else what the op call needs from the processor - the block prologue
+    (the last block joins the row bands), the K / V destination of `kv_target`, the key rotary table, and whether row bands go on behind
+    the attention.  Sets `ctx.partial_kv` as the processor would.  One difference in ORDER, none in bits: `kv_target` runs here, before the
+    block's first LN-modulate is enqueued, while the Python sequence asks for it after that launch - so what a store step's `kv_target`
+    puts on the stream (the slab's zero fill, `rowband_meet`'s join / fork) sits one launch earlier in the chain."""
+    attn = block.attn
+    proc = attn.processor
+    last = getattr(block, "is_last", False)
+    if not (BLOCK_OPS and getattr(ctx, "block_ops", False) and FUSE_QKV and attn.heads % 2 == 0 and isinstance(proc, FluxAttnProcessor)
+            and type(proc).__call__ is FluxAttnProcessor.__call__ and not (last and ctx.out_rows is not None)):
+        return None
+    if last:
+        ctx.forked = False
+        ops.rowband_join()
+    attn.fwd_ctx, attn.block = ctx, block
+    k_slab, vt_slab, kv_rows, skv, rope_k = proc.kv_target(attn, ctx)
+    rope_k = rope_k if rope_k is not None else image_rotary_emb
+    ctx.partial_kv = kv_rows is not None
+    band = bool(ctx.rowbands and not ctx.partial_kv and not last)
+    return k_slab, vt_slab, kv_rows, skv, image_rotary_emb, rope_k, band
+
+
 def rowband_meet(ctx):
     """Inside a forked stretch: both bands wait for everything enqueued so far, then go on as two (the side stream only waits for what
     the caller's stream held AT the fork - a fill or copy enqueued later, or rows cut elsewhere, need the bands to meet)."""
@@ -595,6 +625,17 @@ class FluxTransformerBlock:
         ws, T, M, mods = ctx.ws, ctx.T, ctx.M, ctx.mods
         R = T + M
         d = ws.cfg.d
+        tgt = _block_op_target(self, ctx, image_rotary_emb)
+        if tgt is not None:
+            k_slab, vt_slab, kv_rows, skv, (cos_q, sin_q), (cos_k, sin_k), band = tgt
+            a, vec = self.attn, mods.vec[0]
+            TO.R.mmdit_double_block_(ws.x, ws.nrm, ws.wide, vec[self.mo_img:self.mo_img + 6 * d], vec[self.mo_ctx:self.mo_ctx + 6 * d],
+                                     [a.w_kvq, a.w_add_kvq, a.w_out, a.w_add_out, self.ff_w1, self.ffc_w1, self.ff_w2, self.ffc_w2],
+                                     [a.b_kvq, a.b_add_kvq, a.b_out, a.b_add_out, self.ff_b1, self.ffc_b1, self.ff_b2, self.ffc_b2],
+                                     [a.norm_q, a.norm_k, a.norm_added_q, a.norm_added_k], cos_q, sin_q, cos_k, sin_k, kv_rows, k_slab, vt_slab,
+                                     T, M, a.heads, skv, a.score_bound(), band)
+            ctx.forked = band
+            return ws.x[:T], ws.x[T:R]
         if getattr(self, "is_last", False):
             ctx.forked = False
             ops.rowband_join()             # the last block may skip rows: not the bands' rows
@@ -663,6 +704,15 @@ class FluxSingleTransformerBlock:
         ctx = temb
         ws, T, M, mods = ctx.ws, ctx.T, ctx.M, ctx.mods
         R = T + M
+        tgt = _block_op_target(self, ctx, image_rotary_emb)
+        if tgt is not None:
+            k_slab, vt_slab, kv_rows, skv, (cos_q, sin_q), (cos_k, sin_k), band = tgt
+            a, d = self.attn, ws.cfg.d
+            TO.R.mmdit_single_block_(ws.x, ws.nrm, ws.wide, mods.vec[0][self.mo:self.mo + 3 * d], [a.w_kvqm, self.w_po], [a.b_kvqm, self.b_po],
+                                     [a.norm_q, a.norm_k], cos_q, sin_q, cos_k, sin_k, kv_rows, k_slab, vt_slab, T, M, a.heads, skv,
+                                     a.score_bound(), band)
+            ctx.forked = band
+            return ws.x[:T], ws.x[T:R]
         if getattr(self, "is_last", False):
             ctx.forked = False
             ops.rowband_join()             # the last block may skip rows: not the bands' rows
@@ -691,6 +741,7 @@ class FluxTransformer2DModel:
 
     accepts_row_cat = True            # `hidden_states` may arrive as a RowCat (cat_tokens): the x_embedder reads the pieces
     row_bands = True                  # full steps run the stages between two attentions as two row bands (ROW_BANDS); subclasses: off
+    block_ops = True                  # BLOCK_OPS may run this trunk's blocks as one op call each (tested for FLUX and Step1X; Qwen: off)
 
     def __init__(self, cfg: FluxConfig, device="cuda"):
         self.cfg_model = cfg
@@ -991,6 +1042,7 @@ class FluxTransformer2DModel:
         # processors fork / join around their attention in full steps.  The double blocks cut [text | image] in the image rows, the
         # single blocks the joint rows: where the two boundaries differ (T not a multiple of 256) the bands meet once in between.
         ctx.rowbands = bool(ROW_BANDS and ATTN_BRANCH_STREAMS and self.row_bands and not CFG_PAIR)
+        ctx.block_ops = bool(self.block_ops)
         try:
             for block in self.transformer_blocks:
                 block(hidden_states=ws.x[T:R], encoder_hidden_states=ws.x[:T], temb=ctx, image_rotary_emb=image_rotary_emb)

@@ -72,6 +72,7 @@ class QwenDoubleStreamAttnProcessor2_0(H.FluxAttnProcessor):
 
 class QwenImageTransformer2DModel(H.FluxTransformer2DModel):
     row_bands = False                 # row bands (harness.flux.ROW_BANDS) are measured and enabled for the FLUX trunk only
+    block_ops = False                 # harness.flux.BLOCK_OPS does not cover this trunk's double-stream block
 
     def __init__(self, cfg: FluxConfig, device="cuda"):
         assert cfg.n_single == 0 and not cfg.pooled_embeds and not cfg.guidance_embeds

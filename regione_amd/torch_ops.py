@@ -36,6 +36,8 @@ accessor `R` fills it in from the attribute.
 | kv_partial_update_   | `_partially_linear` x2 + norm_k + RoPE into the K / V^T caches, inplace.py:734-794, fused_kernels.py:81-101 |
 | kv_partial_update_pair_ | the same for the two streams of a double-stream block (one launch), inplace.py:734-794 |
 | region_attention     | flash_attn_func / SDPA of the edited-token queries against the full cache, inplace.py:796-806 |
+| mmdit_double_block_  | one whole masked double-stream block (BLOCK_SCHEMAS), inplace.py:518-524 with :704-824 inside |
+| mmdit_single_block_  | one whole masked single-stream block, inplace.py:549-555 with :704-824 inside |
 """
 from __future__ import annotations
 
@@ -66,6 +68,11 @@ if _mode == "cpp":
         raise ops._lib.RegionEHipError(
             f"{CPP_LIB} was built against ABI {_b.rgn_torch_binding_abi_version()} / struct bytes {_b.rgn_torch_binding_struct_bytes()}, "
             f"libregione_hip.so is {_h.rgn_version()} / {_h.rgn_abi_struct_bytes()}: rebuild (python -m regione_amd.build --force)")
+    _b.rgn_torch_binding_block_bytes.restype = _C.c_size_t
+    if _b.rgn_torch_binding_block_bytes() != _h.rgn_mmdit_block_bytes():
+        raise ops._lib.RegionEHipError(
+            f"{CPP_LIB} was built with sizeof(rgn_mmdit_block) = {_b.rgn_torch_binding_block_bytes()}, libregione_hip.so has "
+            f"{_h.rgn_mmdit_block_bytes()}: rebuild (python -m regione_amd.build --force)")
     _lib = None
 else:
     _lib = torch.library.Library(NS, "FRAGMENT")   # (the dispatcher omits trailing arguments that equal their schema default:
@@ -236,6 +243,126 @@ _define("gate_resid_rows_", "(Tensor p, Tensor gate, Tensor resid, Tensor(a!) ou
         lambda *a, **k: None, ROW_SCHEMAS, _row_defined)
 
 
+# ---- one masked MMDiT block per call (csrc/block.hip) ------------------------------------------------
+BLOCK_SCHEMAS = {}              # listed apart like ROW_SCHEMAS: SCHEMAS stays the region-op surface
+_block_defined = set()
+_BLOCK_TAIL = ("Tensor[] weights, Tensor?[] scales, Tensor?[] biases, Tensor[] norms, Tensor cos_q, Tensor sin_q, Tensor cos_k, Tensor sin_k, "
+               "Tensor? kv_rows, Tensor(d!) k_cache, Tensor(e!) vt_cache, int T, int M, int heads, int skv, float score_bound, "
+               "bool rowbands=False) -> ()")
+DOUBLE_WEIGHTS = ("w_kvq", "w_add_kvq", "w_out", "w_add_out", "ff_w1", "ffc_w1", "ff_w2", "ffc_w2")     # order of `weights` / `scales` / `biases`
+SINGLE_WEIGHTS = ("w_kvqm", "w_po")
+
+
+def _need(ok, op, msg):
+    if not ok:
+        raise ops._lib.RegionEHipError(f"{op}: {msg}")
+
+
+def _block_desc(op, x, nrm, wide, d_ff, names, shapes, weights, scales, biases, norms, n_norms, cos_q, sin_q, cos_k, sin_k, kv_rows, k_cache,
+                vt_cache, T, M, heads, skv, score_bound, rowbands):
+    """The extent checks of csrc/torch_binding.cpp:block_common / block_weight, then struct rgn_mmdit_block; returns (descriptor, keep-alive)."""
+    L = ops._lib
+    bf, dev = torch.bfloat16, x.device
+    _need(x.is_cuda, op, "needs CUDA/HIP tensors: there is no CPU fallback")
+    _need(heads > 0 and T >= 0 and M > 0, op, "heads > 0, T >= 0, M > 0")
+    d, R = heads * 128, T + M
+    _need(d_ff > 0, op, "d_ff must be positive")
+    for t in (x, nrm, wide):
+        _need(t.device == dev and t.dtype == bf and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= R, op,
+              f"x / nrm / wide must be bf16 [>= T + M = {R} rows, cols] with unit column stride on one device")
+    for t in (x, nrm, wide):                 # the descriptor carries row strides as int
+        _need(t.shape[1] <= t.stride(0) < 2 ** 31, op, f"row stride {t.stride(0)} of x / nrm / wide out of range")
+    _need(x.shape[1] == d and nrm.shape[1] == d, op, f"x / nrm need heads * 128 = {d} columns")
+    _need(wide.shape[1] == 3 * d + d_ff, op, f"wide needs 3 d + d_ff = {3 * d + d_ff} columns [k | v | q | mlp], got {wide.shape[1]}")
+    n = len(names)
+    _need(len(weights) == n and len(scales) in (0, n) and len(biases) == n, op, f"{n} weights, {n} (or no) scales, {n} biases")
+    ws = []
+    for i, (name, (N, K)) in enumerate(zip(names, shapes)):
+        w, sc, b = weights[i], (scales[i] if len(scales) else None), biases[i]
+        _need(w.device == dev and tuple(w.shape) == (N, K) and w.is_contiguous() and w.dtype in (bf, ops.FP8), op,
+              f"{name} must be a contiguous bf16 or fp8 [{N}, {K}] on the activations' device")
+        _need((w.dtype == ops.FP8) == (sc is not None), op, f"{name}: an fp8 weight needs its per-output-channel scale, a bf16 weight takes none")
+        _need(sc is None or (sc.dtype == torch.float32 and sc.numel() == N and sc.is_contiguous() and sc.device == dev), op,
+              f"scale of {name} must be fp32 [{N}], contiguous")
+        _need(b is None or (b.dtype == bf and b.dim() == 1 and b.numel() == N and b.is_contiguous() and b.device == dev), op,
+              f"bias of {name} must be bf16 [{N}], contiguous")
+        ws.append(L.BlockWeight(ops._p(w), ops._p(sc), ops._p(b)))
+    _need(len(norms) == n_norms, op, f"{n_norms} per-head RMSNorm weight vectors")
+    for t in norms:
+        _need(t.device == dev and t.dtype == bf and t.numel() == 128 and t.is_contiguous(), op, "per-head RMSNorm weights: bf16 [128]")
+    _need(cos_q.shape == sin_q.shape and cos_k.shape == sin_k.shape, op, "cos / sin of one rotary table differ in shape")
+    for t in (cos_q, sin_q, cos_k, sin_k):
+        _need(t.device == dev and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 128 and t.is_contiguous(), op,
+              "rotary tables: fp32 [rows, 128], contiguous, on the activations' device")
+    _need(cos_q.shape[0] >= R, op, f"rotary table of the queries has {cos_q.shape[0]} rows, the block needs {R}")
+    _need(k_cache.device == dev and vt_cache.device == dev and k_cache.dtype == bf and vt_cache.dtype == bf and k_cache.dim() == 2 and
+          vt_cache.dim() == 2 and k_cache.shape[1] == d and vt_cache.shape[0] == d and vt_cache.shape[1] == k_cache.shape[0] and
+          k_cache.is_contiguous() and vt_cache.is_contiguous() and k_cache.shape[0] % 64 == 0, op,
+          "K slab bf16 [skv_pad, d] / V^T slab bf16 [d, skv_pad], contiguous, skv_pad a multiple of 64")
+    skv_pad = k_cache.shape[0]
+    _need(1 <= skv <= skv_pad, op, f"skv = {skv} outside the cache slab's {skv_pad} rows")
+    if kv_rows is not None:
+        _need(kv_rows.device == dev and kv_rows.dtype == torch.int64 and kv_rows.dim() == 1 and kv_rows.is_contiguous() and kv_rows.numel() == R,
+              op, f"kv_rows must be int64 [T + M = {R}], contiguous")
+        _need(cos_k.shape[0] >= skv >= R, op, f"the key rotary table ({cos_k.shape[0]} rows) must cover the {skv} cache rows, which must hold "
+                                              f"the {R} distinct rows kv_rows names")
+    else:
+        _need(R <= skv, op, f"identity cache rows [0, {R}) exceed skv = {skv}")
+        _need(cos_k.shape[0] >= R, op, f"rotary table of the keys has {cos_k.shape[0]} rows, the block needs {R}")
+    gws, aws = ops.gemm_workspace(dev), ops.attention_workspace(dev)
+    b = L.MmditBlock()
+    b.x, b.nrm, b.wide = ops._p(x), ops._p(nrm), ops._p(wide)
+    b.ldx, b.ldnrm, b.ldwide = x.stride(0), nrm.stride(0), wide.stride(0)
+    b.T, b.M, b.d, b.d_ff, b.heads = T, M, d, d_ff, heads
+    for name, w in zip(names, ws):
+        setattr(b, name, w)
+    for name, t in zip(("norm_q", "norm_k", "norm_added_q", "norm_added_k"), norms):
+        setattr(b, name, ops._p(t))
+    b.k_slab, b.vt_slab, b.kv_rows = ops._p(k_cache), ops._p(vt_cache), ops._p(kv_rows)
+    b.cos_q, b.sin_q, b.cos_k, b.sin_k = ops._p(cos_q), ops._p(sin_q), ops._p(cos_k), ops._p(sin_k)
+    b.skv, b.skv_pad, b.score_bound, b.rowbands, b.out_rows, b.branches = skv, skv_pad, float(score_bound), int(bool(rowbands)), 0, 1
+    b.gemm_ws, b.gemm_ws_bytes, b.attn_ws, b.attn_ws_bytes = ops._p(gws), gws.numel() * 4, ops._p(aws), aws.numel() * 4
+    return b, (gws, aws)
+
+
+def _adaln(op, v, like, n):
+    _need(v.device == like.device and v.dtype == torch.bfloat16 and v.is_contiguous() and v.numel() == n, op,
+          f"AdaLN vector must be bf16 [{n}], contiguous, on the activations' device (got {v.numel()} elements)")
+    return ops._p(v)
+
+
+def _double_block(x, nrm, wide, adaln_img, adaln_txt, weights, scales, biases, norms, cos_q, sin_q, cos_k, sin_k, kv_rows, k_cache, vt_cache,
+                  T, M, heads, skv, score_bound, rowbands=False):
+    import ctypes
+    op = "mmdit_double_block_"
+    _need(len(weights) == 8 and weights[4].dim() == 2, op, "8 weights, ff_w1 = [d_ff, d]")
+    d, ff = heads * 128, weights[4].shape[0]
+    shapes = ((3 * d, d), (3 * d, d), (d, d), (d, d), (ff, d), (ff, d), (d, ff), (d, ff))
+    b, keep = _block_desc(op, x, nrm, wide, ff, DOUBLE_WEIGHTS, shapes, weights, scales, biases, norms, 4, cos_q, sin_q, cos_k, sin_k, kv_rows,
+                          k_cache, vt_cache, T, M, heads, skv, score_bound, rowbands)
+    b.adaln, b.adaln_txt = _adaln(op, adaln_img, x, 6 * d), _adaln(op, adaln_txt, x, 6 * d)
+    ops._lib.check(ops._lib.lib().rgn_mmdit_double_block(ctypes.byref(b), ops._stream()), "rgn_mmdit_double_block")
+
+
+def _single_block(x, nrm, wide, adaln, weights, scales, biases, norms, cos_q, sin_q, cos_k, sin_k, kv_rows, k_cache, vt_cache, T, M, heads, skv,
+                  score_bound, rowbands=False):
+    import ctypes
+    op = "mmdit_single_block_"
+    _need(len(weights) == 2 and weights[1].dim() == 2, op, "2 weights, w_po = [d, d + d_ff]")
+    d = heads * 128
+    ff = weights[1].shape[1] - d
+    b, keep = _block_desc(op, x, nrm, wide, ff, SINGLE_WEIGHTS, ((3 * d + ff, d), (d, d + ff)), weights, scales, biases, norms, 2, cos_q, sin_q,
+                          cos_k, sin_k, kv_rows, k_cache, vt_cache, T, M, heads, skv, score_bound, rowbands)
+    b.adaln = _adaln(op, adaln, x, 3 * d)
+    ops._lib.check(ops._lib.lib().rgn_mmdit_single_block(ctypes.byref(b), ops._stream()), "rgn_mmdit_single_block")
+
+
+_define("mmdit_double_block_", "(Tensor(a!) x, Tensor(b!) nrm, Tensor(c!) wide, Tensor adaln_img, Tensor adaln_txt, " + _BLOCK_TAIL,
+        _double_block, lambda *a, **k: None, BLOCK_SCHEMAS, _block_defined)
+_define("mmdit_single_block_", "(Tensor(a!) x, Tensor(b!) nrm, Tensor(c!) wide, Tensor adaln, " + _BLOCK_TAIL,
+        _single_block, lambda *a, **k: None, BLOCK_SCHEMAS, _block_defined)
+
+
 def registered() -> Tuple[str, ...]:
     return tuple(sorted(_defined))
 
@@ -244,8 +371,17 @@ def registered_row_ops() -> Tuple[str, ...]:
     return tuple(sorted(_row_defined))
 
 
+def registered_block_ops() -> Tuple[str, ...]:
+    return tuple(sorted(_block_defined))
+
+
 def _sc(w):
     return ops._wscale(w)
+
+
+def _scales(weights):
+    sc = [_sc(w) for w in weights]
+    return sc if any(s is not None for s in sc) else []
 
 
 class _Dispatched:
@@ -277,6 +413,15 @@ class _Dispatched:
             x, w_kvq, sc if any(s is not None for s in sc) else [], b_kvq, q_out, norm_q, norm_k, cos_q, sin_q, cos_k, sin_k, kv_rows,
             k_cache, vt_cache, heads, row_base, eps, [int(bool(f)) for f in fp16_roundtrip], gelu_from_col)
 
+    # the block ops take the weights as a list: the scales that ride on fp8 weights go in a list beside it
+    @staticmethod
+    def mmdit_double_block_(x, nrm, wide, adaln_img, adaln_txt, weights, biases, *a, **kw):
+        return torch.ops.regione_mi.mmdit_double_block_(x, nrm, wide, adaln_img, adaln_txt, weights, _scales(weights), biases, *a, **kw)
+
+    @staticmethod
+    def mmdit_single_block_(x, nrm, wide, adaln, weights, biases, *a, **kw):
+        return torch.ops.regione_mi.mmdit_single_block_(x, nrm, wide, adaln, weights, _scales(weights), biases, *a, **kw)
+
 
 class _Direct:
     """`RGN_TORCH_OPS=0`: the same names bound straight to regione_amd.ops (no dispatcher) - A/B switch only."""
@@ -293,6 +438,14 @@ class _Direct:
     @staticmethod
     def kv_partial_update_group_(x, w_kvq, b_kvq, *a, **kw):
         return _kv_update_group(x, w_kvq, [], b_kvq, *a, **kw)
+
+    @staticmethod
+    def mmdit_double_block_(x, nrm, wide, adaln_img, adaln_txt, weights, biases, *a, **kw):
+        return _double_block(x, nrm, wide, adaln_img, adaln_txt, weights, _scales(weights), biases, *a, **kw)
+
+    @staticmethod
+    def mmdit_single_block_(x, nrm, wide, adaln, weights, biases, *a, **kw):
+        return _single_block(x, nrm, wide, adaln, weights, _scales(weights), biases, *a, **kw)
 
 
 R = _Direct if _mode == "0" else _Dispatched()
