@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 115
+#define RGN_ABI_VERSION 116
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -504,6 +504,32 @@ size_t rgn_lm_decode_attention_workspace_bytes(int Hq, int n);
 int rgn_lm_head_argmax(const void* W, const void* x, int V, int K, void* token_out, float* logits_out, void* workspace,
                        size_t workspace_bytes, void* stream);
 size_t rgn_lm_head_workspace_bytes(int V);
+/* Repetition penalty and sampling for that decode (transformers' RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper,
+ * TopKLogitsWarper, TopPLogitsWarper and the multinomial draw, in the order of _get_logits_processor).
+ *
+ * seen[ids[i]] = 1 for i < n: the byte map [V] of the token ids of the sequence so far (int64 ids, 8-byte aligned; an id outside [0, V)
+ * marks nothing).  Plain byte stores, no atomics.  Called once per generate over the whole prompt, image placeholders included, after
+ * rgn_fill_zero; rgn_lm_pick marks every token it picks. */
+int rgn_lm_seen_mark(const void* ids, int n, void* seen, int V, void* stream);
+/* One pick over the fp32 logits z [V] that rgn_lm_head_argmax(..., logits_out) wrote, in ONE launch of one block; z is not modified.
+ *   1. penalty p > 0 over seen: z < 0 ? z * p : z / p (fp32, once per token id); p == 1 skips the stage
+ *   2. sample != 0: s = z / temperature in fp32 (IEEE division); sample == 0 skips stages 2 to 4
+ *   3. top_k > 0: every s[v] below the k-th largest VALUE becomes -inf; ties with the k-th value stay (0, or k >= V: off)
+ *   4. top_p < 1: with softmax(s) over what is left, in ascending order of s, a token is dropped while the mass up to and including it
+ *      and every token of the same score is <= 1 - top_p; the largest is never dropped (min_tokens_to_keep = 1).  Equal scores are kept
+ *      or dropped TOGETHER; transformers' sort splits such a group when it straddles the boundary, this entry keeps all of it.
+ *   5. sample == 0: token = argmax, the lowest index on a tie.  sample != 0: q = softmax over the kept tokens, token = the lowest kept
+ *      index v with sum_{w <= v} q[w] > uniform[0] (u in [0, 1), fp32 in device memory; the entry has no generator of its own), the
+ *      last kept token if rounding leaves none.  token_out[0] = token as int64, seen[token] = 1.
+ *   6. scores_out != NULL receives the processed scores (fp32 [V], -inf where filtered); it may not be z.
+ * The k-th value and the top-p threshold come from radix selects over the key bits of s (4 bits a round, per-thread fp64 bins in LDS
+ * folded in a fixed order), the draw from fp64 wave sums per 64 tokens and a block scan in token order: no atomics, no sort, a repeated
+ * call is bit-identical.  Masses are expf(s - max) in fp32 summed in fp64: a cumulative mass is within 2^-23 (ln V + 6) of the exact
+ * one (expf taken at 3 ulp).  1 <= V <= 1048576; token_out 8-byte, z / scores_out / workspace / uniform 4-byte aligned;
+ * workspace_bytes >= rgn_lm_pick_workspace_bytes(V).  temperature, top_k and top_p are validated whatever `sample` is. */
+int rgn_lm_pick(const float* logits, int V, void* seen, float penalty, int sample, float temperature, int top_k, double top_p,
+                const float* uniform, void* token_out, float* scores_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t rgn_lm_pick_workspace_bytes(int V);
 
 /* ------------------------------------------------------------------------------------------
  * f4  vision tower of the Qwen2.5-VL prompt encoder ([EXT] transformers Qwen2_5_VisionTransformerPretrainedModel: `get_image_features`

@@ -145,6 +145,10 @@ SIGNATURES = {
     "rgn_lm_decode_attention_workspace_bytes": [_c_int, _c_int],
     "rgn_lm_head_argmax": [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, C.c_size_t, _c_void_p],
     "rgn_lm_head_workspace_bytes": [_c_int],
+    "rgn_lm_seen_mark": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p],
+    "rgn_lm_pick": [_c_void_p, _c_int, _c_void_p, _c_float, _c_int, _c_float, _c_int, C.c_double, _c_void_p, _c_void_p, _c_void_p,
+                    _c_void_p, C.c_size_t, _c_void_p],
+    "rgn_lm_pick_workspace_bytes": [_c_int],
     # f4: vision tower of the Qwen2.5-VL prompt encoder (csrc/vision.hip)
     "rgn_vision_attention_bf16": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p, _c_int, _c_void_p],
     "rgn_vision_rope_bf16": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p],
@@ -162,7 +166,8 @@ SIGNATURES = {
 _RESTYPE = {"rgn_last_error": C.c_char_p, "rgn_abi_struct_bytes": C.c_size_t, "rgn_attention_workspace_bytes": C.c_size_t,
             "rgn_gemm_workspace_bytes": C.c_size_t, "rgn_groupnorm_workspace_bytes": C.c_size_t,
             "rgn_groupnorm_partial_bytes": C.c_size_t, "rgn_lm_decode_attention_workspace_bytes": C.c_size_t,
-            "rgn_lm_head_workspace_bytes": C.c_size_t, "rgn_rowband_side_launches": C.c_longlong, "rgn_mmdit_block_bytes": C.c_size_t}
+            "rgn_lm_head_workspace_bytes": C.c_size_t, "rgn_lm_pick_workspace_bytes": C.c_size_t,
+            "rgn_rowband_side_launches": C.c_longlong, "rgn_mmdit_block_bytes": C.c_size_t}
 
 _lib = None
 

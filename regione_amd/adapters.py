@@ -396,7 +396,9 @@ def hip_qwen_text_encoder_for(host, dev):
     silently.  A `text_encoder` that is not a `Qwen2_5_VLForConditionalGeneration` is left alone silently;
     `pipe._regione_hip_text = False` before the first call keeps the whole host module on purpose.
     `pipe._regione_hip_text_weights = "fp8"` before the first call adopts the layers' projection matrices as fp8 e4m3fn with per-channel
-    scales (HipQwen25VLTextEncoder(weights="fp8")); absent, the adoption is "bf16"; another value raises ValueError naming the two."""
+    scales (HipQwen25VLTextEncoder(weights="fp8")); absent, the adoption is "bf16"; another value raises ValueError naming the two.
+    `pipe._regione_hip_text_sampling = True` before the first call adopts with `sampling=True` (generate honours do_sample, temperature,
+    top_k, top_p and repetition_penalty); absent, it is False; a value that is not a bool raises ValueError."""
     if host.__dict__.get("_regione_hip_text", _NO_HIP_VAE) is False:
         return None
     cached = host.__dict__.get("_regione_hip_qwen_text", _NO_HIP_VAE)
@@ -405,6 +407,9 @@ def hip_qwen_text_encoder_for(host, dev):
     fmt = host.__dict__.get("_regione_hip_text_weights", "bf16")
     if fmt not in ("bf16", "fp8"):
         raise ValueError(f"pipe._regione_hip_text_weights = {fmt!r}: \"bf16\" and \"fp8\" are accepted")
+    sampling = host.__dict__.get("_regione_hip_text_sampling", False)
+    if not isinstance(sampling, bool):
+        raise ValueError(f"pipe._regione_hip_text_sampling = {sampling!r}: True and False are accepted")
     mod = getattr(host, "text_encoder", None)
     enc = None
     if type(mod).__name__ == "Qwen2_5_VLForConditionalGeneration" and getattr(mod, "config", None) is not None:
@@ -414,7 +419,7 @@ def hip_qwen_text_encoder_for(host, dev):
             why = "PEFT / LoRA layers in the module"
         if why is None:
             try:
-                enc = QT.HipQwen25VLTextEncoder(mod, dev, weights=fmt)
+                enc = QT.HipQwen25VLTextEncoder(mod, dev, weights=fmt, **({"sampling": True} if sampling else {}))
             except _lib.RegionEHipError as e:
                 why = str(e)
         if why is not None:

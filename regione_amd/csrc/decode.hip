@@ -11,6 +11,9 @@
 //   lm_decode_attention_kernel  one query token: a block takes one KV head and one slice of 64 cache rows for all Hq / Hkv query heads of
 //                               that KV head (K and V are read once per group) and writes fp32 partials (m, l, o[128]) per query head
 //   lm_decode_merge_kernel      folds the partials of a head in slice order and rounds O to bf16 once
+//   lm_seen_mark_kernel         seen[id] = 1 for the prompt ids: the byte map the repetition penalty reads
+//   lm_pick_kernel              one block between lm_head and the next embedding: repetition penalty, temperature, top-k, top-p and the
+//                               pick (argmax, or the inverse CDF at a uniform read from device memory) over the fp32 logits in L2
 // No atomics; every reduction has a fixed order (lanes: the butterfly of wave_sum; k, keys and slices: ascending), so a repeated call is
 // bit-identical.
 #include <math.h>
@@ -331,6 +334,265 @@ __global__ __launch_bounds__(128) void lm_decode_merge_kernel(const float* __res
     O[(size_t)h * 128 + d] = f2bf(o / l);
 }
 
+// ---- repetition penalty and sampling: the pick between lm_head and the next embedding -------------------------------------------------
+// seen[ids[i]] = 1: plain byte stores of the same value, so the order of the threads does not matter.  An id outside [0, V) marks nothing.
+__global__ __launch_bounds__(256) void lm_seen_mark_kernel(const int64_t* __restrict__ ids, int n, uint8_t* __restrict__ seen, int V) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const int64_t t = ids[i];
+        if (t >= 0 && t < (int64_t)V) seen[t] = 1;
+    }
+}
+
+// The stages of transformers' _get_logits_processor in its order, in ONE block of 16 waves: the 608 KB row of fp32 logits stays in L2 and
+// is re-read per pass instead of sorted (11 passes with top-p alone, 19 with top-k and top-p).
+//   element v belongs to thread v % 1024 in every pass (coalesced; wave w of round i holds tokens 1024 i + 64 w .. + 63 in lane order)
+//   scores  s = penalty(z) / T goes to `s` (scores_out, else the workspace); the block maximum and its LOWEST index are folded on the way
+//   top-k   the k-th largest value by a radix select over the order-preserving key bits of s, 4 bits a round: a thread adds 1.0 to ITS
+//           OWN fp64 bin of the digit (LDS [16][1024], no atomics), wave w folds bin w in thread order, every thread walks the 16 totals
+//   top-p   the same select with expf(s - max) as the weight, ascending: the smallest value x whose mass of values <= x exceeds
+//           (1 - top_p) Z; tokens below x are dropped.  Equal scores share a key, so they are kept or dropped together.
+//   pick    wave sums of the kept masses per 64 tokens (fp64, the butterfly), a block scan over them in token order, the first 64-token
+//           segment whose cumulative mass exceeds u Z, then a scan over its 64 lanes: the lowest kept index with C(v) > u Z
+// Every sum is fp64 in a fixed order; the only fp32 arithmetic is what transformers does in fp32 (the penalty, the division by T) and expf.
+constexpr int PICK_T = 1024, PICK_BINS = 16, PICK_MAX_V = 1 << 20;              // 16384 64-token segments fit the bins' 128 KB of LDS
+constexpr int PICK_LDS = PICK_BINS * PICK_T * (int)sizeof(double);
+constexpr int PICK_NONE = 0x7fffffff;
+
+__device__ __forceinline__ uint32_t pick_key(float f) {                          // a < b as floats  <=>  key(a) < key(b) (-0 below +0)
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float pick_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// A pass over the row: f(v, s[v]) for the thread's elements in ascending v, PICK_U loads issued before the first use (one block has to
+// cover the L2 latency by itself).  Measured at V = 152064: 0.38 to 0.49 ms per pick, i.e. 20 to 35 us per pass, and the loads are the
+// smaller part of it (batching them took 0.09 ms off a pick): ONE CU issues about a dozen instructions for each of 152064 elements per
+// pass.  Spreading a pass over many CUs (per-block bins in the workspace, folded by the next launch) is the next step, not taken here.
+constexpr int PICK_U = 16;
+template <typename F>
+__device__ __forceinline__ void pick_pass(const float* s, int V, F&& f) {
+    for (int v0 = threadIdx.x; v0 < V; v0 += PICK_T * PICK_U) {
+        float x[PICK_U];
+#pragma unroll
+        for (int u = 0; u < PICK_U; ++u) x[u] = v0 + u * PICK_T < V ? s[v0 + u * PICK_T] : 0.f;
+#pragma unroll
+        for (int u = 0; u < PICK_U; ++u)
+            if (v0 + u * PICK_T < V) f(v0 + u * PICK_T, x[u]);
+    }
+}
+
+// One radix select over the elements with s >= lo.  MASS = false: the value of the k-th largest element (target = k, weights 1, digits
+// walked from the top).  MASS = true: the smallest value x with sum_{s <= x} expf(s - smax) > target * Z, Z the mass of all of them
+// (digits walked from the bottom).  Every thread returns the same value.
+template <bool MASS>
+__device__ float pick_select(const float* s, int V, double* bins, double* tot, float lo, float smax, double target) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t prefix = 0;
+    double passed = 0.0;                                                         // the weight of the buckets already walked past
+    for (int r = 0; r < 8; ++r) {
+#pragma unroll
+        for (int b = 0; b < PICK_BINS; ++b) bins[b * PICK_T + tid] = 0.0;
+        const int shift = 28 - 4 * r;
+        pick_pass(s, V, [&](int, float x) {
+            if (x >= lo) {
+                const uint32_t key = pick_key(x);
+                if (r == 0 || (key >> (shift + 4)) == prefix) {
+                    double* bin = bins + ((key >> shift) & 15u) * PICK_T + tid;
+                    *bin += MASS ? (double)expf(x - smax) : 1.0;
+                }
+            }
+        });
+        __syncthreads();
+        double acc = 0.0;                                                        // wave w folds bin w: threads ascending, then the butterfly
+#pragma unroll
+        for (int j = 0; j < PICK_T / 64; ++j) acc += bins[wave * PICK_T + j * 64 + lane];
+        acc = wave_sum_f64(acc);
+        if (lane == 0) tot[wave] = acc;
+        __syncthreads();
+        int d;
+        if constexpr (MASS) {
+            if (r == 0) {
+                double Z = 0.0;
+                for (int b = 0; b < PICK_BINS; ++b) Z += tot[b];
+                target *= Z;
+            }
+            d = PICK_BINS - 1;
+            for (int b = 0; b < PICK_BINS - 1; ++b) {
+                if (passed + tot[b] > target) { d = b; break; }
+                passed += tot[b];
+            }
+        } else {
+            d = 0;
+            for (int b = PICK_BINS - 1; b > 0; --b) {
+                if (passed + tot[b] >= target) { d = b; break; }
+                passed += tot[b];
+            }
+        }
+        prefix = (prefix << 4) | (uint32_t)d;
+        __syncthreads();                                                         // the totals are read before the next round's fold writes them
+    }
+    return pick_unkey(prefix);
+}
+
+__global__ __launch_bounds__(PICK_T) void lm_pick_kernel(const float* __restrict__ z, int V, uint8_t* __restrict__ seen, float penalty,
+                                                          int sample, float temperature, int top_k, double top_p,
+                                                          const float* __restrict__ uniform, int64_t* __restrict__ token_out, float* s) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    double* bins = (double*)smem;
+    __shared__ double tot[PICK_BINS];
+    __shared__ float rv[PICK_T / 64];
+    __shared__ int ri[PICK_T / 64];
+    __shared__ double sh_prev;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // scores, and their maximum with its lowest index
+    float best = -INFINITY;
+    int at = PICK_NONE;
+    const bool pen = penalty != 1.f;
+    for (int v0 = tid; v0 < V; v0 += PICK_T * PICK_U) {
+        float x[PICK_U];
+        uint8_t m[PICK_U];
+#pragma unroll
+        for (int u = 0; u < PICK_U; ++u) {
+            const int v = v0 + u * PICK_T;
+            x[u] = v < V ? z[v] : 0.f;
+            m[u] = pen && v < V ? seen[v] : (uint8_t)0;
+        }
+#pragma unroll
+        for (int u = 0; u < PICK_U; ++u) {
+            const int v = v0 + u * PICK_T;
+            if (v < V) {
+                float y = x[u];
+                if (m[u]) y = y < 0.f ? y * penalty : y / penalty;
+                if (sample) y = y / temperature;
+                s[v] = y;
+                if (at == PICK_NONE || y > best) { best = y; at = v; }           // ascending v per thread, strict >: the first maximum
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float v2 = __shfl_xor(best, o, 64);
+        const int i2 = __shfl_xor(at, o, 64);
+        if (i2 != PICK_NONE && (at == PICK_NONE || v2 > best || (v2 == best && i2 < at))) { best = v2; at = i2; }
+    }
+    if (lane == 0) { rv[wave] = best; ri[wave] = at; }
+    __syncthreads();                                                             // also: every s[v] is written before another thread reads it
+    best = rv[0];
+    at = ri[0];
+    for (int w = 1; w < PICK_T / 64; ++w)
+        if (ri[w] != PICK_NONE && (at == PICK_NONE || rv[w] > best || (rv[w] == best && ri[w] < at))) { best = rv[w]; at = ri[w]; }
+    if (at == PICK_NONE) at = 0;
+    __syncthreads();
+    if (!sample) {                                                               // greedy: the argmax of the penalised scores
+        if (tid == 0) { token_out[0] = (int64_t)at; seen[at] = 1; }
+        return;
+    }
+    const float smax = best;
+    float lo = -INFINITY;                                                        // kept: s >= lo
+    if (top_k > 0 && top_k < V) lo = pick_select<false>(s, V, bins, tot, lo, smax, (double)top_k);
+    if (top_p < 1.0) lo = fmaxf(lo, pick_select<true>(s, V, bins, tot, lo, smax, 1.0 - top_p));
+    lo = fminf(lo, smax);                                                        // the largest is never dropped
+    // kept masses per 64-token segment, in token order
+    const int niter = (V + PICK_T - 1) / PICK_T, nseg = niter * (PICK_T / 64);
+    double* seg = bins;
+    int last = -1;
+    for (int i0 = 0; i0 < niter; i0 += PICK_U) {
+        float x[PICK_U];
+#pragma unroll
+        for (int u = 0; u < PICK_U; ++u) x[u] = (i0 + u) * PICK_T + tid < V ? s[(i0 + u) * PICK_T + tid] : -INFINITY;
+#pragma unroll
+        for (int u = 0; u < PICK_U; ++u) {
+            if (i0 + u < niter) {                                                // block-uniform
+                const int v = (i0 + u) * PICK_T + tid;
+                double e = 0.0;
+                if (v < V && x[u] >= lo) { e = (double)expf(x[u] - smax); last = v; }
+                e = wave_sum_f64(e);
+                if (lane == 0) seg[(i0 + u) * (PICK_T / 64) + wave] = e;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+    if (lane == 0) ri[wave] = last;
+    __syncthreads();
+    last = ri[0];
+    for (int w = 1; w < PICK_T / 64; ++w) last = max(last, ri[w]);
+    // block scan: thread t owns segments [t c, t c + c)
+    const int c = (nseg + PICK_T - 1) / PICK_T;
+    double local = 0.0;
+    for (int j = 0; j < c; ++j)
+        if (tid * c + j < nseg) local += seg[tid * c + j];
+    double inc = local;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double y = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += y;
+    }
+    double excl = __shfl_up(inc, 1, 64);
+    if (lane == 0) excl = 0.0;
+    if (lane == 63) tot[wave] = inc;
+    __syncthreads();                                                             // also: ri (the last kept index) is read by every thread
+    double Z = 0.0;
+    for (int w = 0; w < PICK_T / 64; ++w) {
+        if (w == wave) excl += Z;
+        Z += tot[w];
+    }
+    const double target = (double)uniform[0] * Z;
+    int cand = PICK_NONE;
+    double prev = 0.0, run = excl;
+    for (int j = 0; j < c; ++j) {
+        const int g = tid * c + j;
+        if (g < nseg) {
+            const double nx = run + seg[g];
+            if (cand == PICK_NONE && nx > target) { cand = g; prev = run; }
+            run = nx;
+        }
+    }
+    int first = cand;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+    if (lane == 0) ri[wave] = first;
+    __syncthreads();
+    first = ri[0];
+    for (int w = 1; w < PICK_T / 64; ++w) first = min(first, ri[w]);
+    if (cand != PICK_NONE && cand == first) sh_prev = prev;                      // segments are partitioned: one thread owns `first`
+    __syncthreads();
+    if (wave == 0) {
+        int tok = last >= 0 ? last : at;                                         // rounding left no crossing: the last kept token
+        if (first != PICK_NONE) {
+            const int v = (first / (PICK_T / 64)) * PICK_T + (first % (PICK_T / 64)) * 64 + lane;
+            double e = 0.0;
+            bool kept = false;
+            if (v < V) {
+                const float x = s[v];
+                if (x >= lo) { e = (double)expf(x - smax); kept = true; }
+            }
+            double ci = e;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const double y = __shfl_up(ci, o, 64);
+                if (lane >= o) ci += y;
+            }
+            const unsigned long long hit = __ballot(kept && sh_prev + ci > target), any = __ballot(kept);
+            const int base = v - lane;
+            if (hit) tok = base + (int)__ffsll((long long)hit) - 1;
+            else if (any) tok = base + 63 - (int)__clzll((long long)any);
+        }
+        if (lane == 0) { token_out[0] = (int64_t)tok; seen[tok] = 1; }
+    }
+    __syncthreads();
+    if (lo > -INFINITY)                                                          // the processed scores: -inf where filtered
+        pick_pass(s, V, [&](int v, float x) {
+            if (!(x >= lo)) s[v] = -INFINITY;
+        });
+}
+
 }  // namespace rgn
 
 using namespace rgn;
@@ -419,6 +681,42 @@ int rgn_lm_decode_attention_bf16(const void* q, const void* cache, void* O, int 
                        (float*)workspace, ns);
     hipLaunchKernelGGL(lm_decode_merge_kernel, dim3(Hq), dim3(128), 0, st, (const float*)workspace, ns, (uint16_t*)O);
     return check_launch("lm_decode_attention");
+}
+
+int rgn_lm_seen_mark(const void* ids, int n, void* seen, int V, void* stream) {
+    if (n == 0) return 0;
+    if (!ids || !seen || n < 0 || V < 1) return fail(RGN_E_BADARG, "lm_seen_mark: bad argument (ids, seen non-null; n >= 0; V >= 1)");
+    if ((uintptr_t)ids & 7u) return fail(RGN_E_BADARG, "lm_seen_mark: ids must be 8-byte aligned");
+    const int g = (n + 255) / 256;
+    hipLaunchKernelGGL(lm_seen_mark_kernel, dim3(g > 256 ? 256 : g), dim3(256), 0, (hipStream_t)stream, (const int64_t*)ids, n, (uint8_t*)seen, V);
+    return check_launch("lm_seen_mark_kernel");
+}
+
+size_t rgn_lm_pick_workspace_bytes(int V) { return V < 1 ? 0 : (size_t)V * sizeof(float); }
+
+int rgn_lm_pick(const float* logits, int V, void* seen, float penalty, int sample, float temperature, int top_k, double top_p,
+                const float* uniform, void* token_out, float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!logits || !seen || !token_out || !workspace || V < 1 || V > PICK_MAX_V)
+        return fail(RGN_E_BADARG, "lm_pick: bad argument (logits, seen, token_out, workspace non-null; 1 <= V <= 1048576)");
+    if (!(penalty > 0.f) || !(penalty < INFINITY)) return fail(RGN_E_BADARG, "lm_pick: the repetition penalty must be in (0, inf)");
+    if (!(temperature > 0.f) || !(temperature < INFINITY)) return fail(RGN_E_BADARG, "lm_pick: the temperature must be in (0, inf)");
+    if (top_k < 0) return fail(RGN_E_BADARG, "lm_pick: top_k must be >= 0 (0 = off)");
+    if (!(top_p > 0.0) || !(top_p <= 1.0)) return fail(RGN_E_BADARG, "lm_pick: top_p must be in (0, 1] (1 = off)");
+    if (sample && !uniform) return fail(RGN_E_BADARG, "lm_pick: sampling reads its uniform from device memory (uniform non-null)");
+    if (((uintptr_t)token_out & 7u) || (((uintptr_t)logits | (uintptr_t)scores_out | (uintptr_t)workspace | (uintptr_t)uniform) & 3u))
+        return fail(RGN_E_BADARG, "lm_pick: token_out must be 8-byte, logits, scores_out, workspace and uniform 4-byte aligned");
+    if (scores_out == logits) return fail(RGN_E_BADARG, "lm_pick: scores_out may not be the logits");
+    if (workspace_bytes < rgn_lm_pick_workspace_bytes(V)) return fail(RGN_E_BADARG, "lm_pick: workspace smaller than rgn_lm_pick_workspace_bytes(V)");
+    static bool attr[64] = {};          // per device (one process may drive several GPUs)
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !attr[dev]) {
+        (void)hipFuncSetAttribute((const void*)lm_pick_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PICK_LDS);
+        if (dev >= 0 && dev < 64) attr[dev] = true;
+    }
+    hipLaunchKernelGGL(lm_pick_kernel, dim3(1), dim3(PICK_T), PICK_LDS, (hipStream_t)stream, logits, V, (uint8_t*)seen, penalty, sample ? 1 : 0,
+                       temperature, top_k, top_p, uniform, (int64_t*)token_out, scores_out ? scores_out : (float*)workspace);
+    return check_launch("lm_pick_kernel");
 }
 
 }  // extern "C"

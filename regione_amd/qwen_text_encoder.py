@@ -33,6 +33,13 @@ quantisation of the concatenation), layer by layer on the device; norms, the q|k
 is unchanged (ops.gemm takes the scale from the weight tensor, rgn_gemm_group converts exactly and scales the accumulator); the decode loop
 calls rgn_lm_gemv_w8 instead of rgn_lm_gemv_bf16: half the bytes per token for those matrices.  Opt-in: the default "bf16" is the path above.
 
+`sampling=True` (opt-in; the default refuses what it refused before) lets `generate` honour a decoding configuration: `do_sample`,
+`temperature`, `top_k`, `top_p` and `repetition_penalty`, each taken from the module's generation_config when the argument is None, as
+transformers does.  The pick is then rgn_lm_head_argmax for the fp32 logits followed by ONE rgn_lm_pick on the same stream (penalty over
+a byte map of the ids so far, temperature, top-k, top-p, argmax or the inverse CDF at a uniform read from a device buffer filled before
+the loop), which overwrites the id slot: still no token visits the host inside a step.  The uniforms come from `generator=` /
+`uniforms=`, not from torch.multinomial: a seed gives transformers' distribution, not transformers' tokens.
+
 There is no eager fallback inside: what the kernels do not implement raises RegionEHipError before any launch, and the adapter
 (regione_amd/adapters.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
 only; every call returns freshly allocated outputs.
@@ -148,10 +155,11 @@ def decode_position_ids(prompt_position_ids: torch.Tensor, n_new: int) -> torch.
 
 class QwenGenerateOutput:
     """`generate(..., return_dict_in_generate=True)`: `.sequences` [1, L + n_new] int64 and, with `output_logits=True`, `.logits`, a tuple
-    of n_new fp32 [1, V] tensors (the raw lm_head outputs the tokens were picked from); None otherwise."""
+    of n_new fp32 [1, V] tensors (the raw lm_head outputs the tokens were picked from); None otherwise.  Under `sampling=True`,
+    `output_scores=True` adds `.scores`, the same shape: the processed scores of rgn_lm_pick (-inf where top-k / top-p filtered)."""
 
-    def __init__(self, sequences, logits=None):
-        self.sequences, self.logits = sequences, logits
+    def __init__(self, sequences, logits=None, scores=None):
+        self.sequences, self.logits, self.scores = sequences, logits, scores
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -163,6 +171,32 @@ SAMPLING_ARGS = ("temperature", "top_k", "top_p", "min_p", "typical_p", "epsilon
                  "num_beam_groups", "num_return_sequences", "bad_words_ids", "force_words_ids", "suppress_tokens", "begin_suppress_tokens",
                  "sequence_bias", "logits_processor", "stopping_criteria", "min_new_tokens", "min_length", "guidance_scale",
                  "exponential_decay_length_penalty", "renormalize_logits", "constraints", "prefix_allowed_tokens_fn", "assistant_model")
+
+# what a `sampling=True` adoption implements of them (rgn_lm_pick), and what its generate takes besides
+PICK_ARGS = ("temperature", "top_k", "top_p", "repetition_penalty")
+PICK_EXTRA = ("generator", "uniforms", "output_scores")
+# the generation_config fields such an adoption still refuses, with the value (besides None) that switches each off
+CONFIG_OFF = dict(min_p=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, encoder_repetition_penalty=1.0, no_repeat_ngram_size=0,
+                  length_penalty=1.0, diversity_penalty=0.0, penalty_alpha=None, num_beam_groups=1, num_return_sequences=1,
+                  bad_words_ids=None, force_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, sequence_bias=None,
+                  min_new_tokens=0, min_length=0, guidance_scale=1.0, exponential_decay_length_penalty=None, renormalize_logits=False,
+                  constraints=None)
+
+
+class PickPlan:
+    """The resolved decoding configuration of one generate under `sampling=True` (the arguments of rgn_lm_pick)."""
+
+    def __init__(self, sample, penalty, temperature, top_k, top_p, uniforms, generator, output_scores):
+        self.sample, self.penalty, self.temperature, self.top_k, self.top_p = sample, penalty, temperature, top_k, top_p
+        self.uniforms, self.generator, self.output_scores = uniforms, generator, output_scores
+
+    @property
+    def greedy_as_before(self):                                                  # nothing rgn_lm_head_argmax does not already do
+        return not self.sample and self.penalty == 1.0 and not self.output_scores
+
+
+def _number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
 
 
 def valid_lengths(attention_mask: Optional[torch.Tensor], B: int, L: int, what: str = "HipQwen25VLTextEncoder"):
@@ -206,10 +240,13 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
     states) are absent.  Padded positions are zero rows."""
     what = "HipQwen25VLTextEncoder"
 
-    def __init__(self, module_or_state_dict, device=None, config=None, max_length: int = 4096, vision=None, weights: str = "bf16"):
+    def __init__(self, module_or_state_dict, device=None, config=None, max_length: int = 4096, vision=None, weights: str = "bf16",
+                 sampling: bool = False):
         if weights not in WEIGHT_FORMATS:
             _refuse(self.what, f"weights={weights!r} (the layer matrices are kept as one of {WEIGHT_FORMATS})")
-        self.weights = weights
+        if not isinstance(sampling, bool):
+            _refuse(self.what, f"sampling={sampling!r} (True or False)")
+        self.weights, self.sampling = weights, sampling
         sd, cfg, dev, mod = _source(module_or_state_dict, config, device, self.what)
         self.vision = vision                               # a HipQwen25VLVisionTower, or None: the adopted module's eager tower
         why = qwen25vl_refusal(cfg)
@@ -431,6 +468,51 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             _refuse(self.what, "eos_token_id must be an int or a list of ints")
         return eos
 
+    def _pick_plan(self, do_sample, max_new_tokens, kw):
+        """`sampling=True`: the decoding configuration of this call - an argument, else the module's generation_config field, else off -
+        and every refusal that goes with it, before any launch.  `kw` holds the PICK_ARGS / PICK_EXTRA arguments of the call."""
+        gc = getattr(self.module, "generation_config", None)
+        if self.tok.shape[0] > 1 << 20:
+            _refuse(self.what, f"a vocabulary of {self.tok.shape[0]} under sampling=True (rgn_lm_pick takes V <= 1048576)")
+        for k, off in CONFIG_OFF.items():
+            v = getattr(gc, k, None)
+            if v is not None and v != off:
+                _refuse(self.what, f"generation_config.{k} = {v!r} of the adopted module is not implemented (only None"
+                        + (f" or {off!r}" if off is not None else "") + " would not change the tokens)")
+
+        def take(k):
+            v = kw.get(k)
+            return getattr(gc, k, None) if v is None else v
+        if do_sample is None:
+            do_sample = bool(getattr(gc, "do_sample", False))
+        if not isinstance(do_sample, bool):
+            _refuse(self.what, f"do_sample={do_sample!r} (True, False or None)")
+        penalty, temperature, top_k, top_p = take("repetition_penalty"), take("temperature"), take("top_k"), take("top_p")
+        if penalty is not None and not (_number(penalty) and 0 < penalty < float("inf")):
+            _refuse(self.what, f"repetition_penalty={penalty!r} (a number > 0)")
+        if temperature is not None and not (_number(temperature) and 0 < temperature < float("inf")):
+            _refuse(self.what, f"temperature={temperature!r} (a number > 0)")
+        if top_k is not None and not (isinstance(top_k, int) and not isinstance(top_k, bool) and 1 <= top_k < 2 ** 31):
+            _refuse(self.what, f"top_k={top_k!r} (an int >= 1)")
+        if top_p is not None and not (_number(top_p) and 0 < top_p <= 1):
+            _refuse(self.what, f"top_p={top_p!r} (a number in (0, 1])")
+        generator, uniforms, scores = kw.get("generator"), kw.get("uniforms"), kw.get("output_scores")
+        if generator is not None and uniforms is not None:
+            _refuse(self.what, "generator= and uniforms= together (one source of the uniforms)")
+        if generator is not None and not isinstance(generator, torch.Generator):
+            _refuse(self.what, f"generator={type(generator).__name__} (a torch.Generator)")
+        if uniforms is not None:
+            here = torch.device(self.device)
+            there = uniforms.device if isinstance(uniforms, torch.Tensor) else None
+            if there is None or tuple(uniforms.shape) != (max_new_tokens,) or uniforms.dtype != torch.float32 or not uniforms.is_contiguous() \
+                    or there.type != here.type or (here.index is not None and there.index not in (None, here.index)):
+                _refuse(self.what, f"uniforms must be a contiguous float32 tensor of shape ({max_new_tokens},) on {torch.device(self.device)} "
+                                   "(one uniform in [0, 1) per new token)")
+        if scores is not None and not isinstance(scores, bool):
+            _refuse(self.what, f"output_scores={scores!r} (True or False)")
+        return PickPlan(do_sample, float(penalty or 1.0), float(temperature or 1.0), int(top_k or 0), float(top_p or 1.0), uniforms, generator,
+                        bool(scores))
+
     def _adopt_lm_head(self):
         """`lm_head.weight` [V, d] bf16 on the device, adopted at the first generate; the token embedding under tie_word_embeddings."""
         if self.lm_head is not None:
@@ -455,8 +537,19 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         layer appended to a cache; each further token is one row through rgn_lm_gemv_bf16 (rgn_lm_gemv_w8 under weights="fp8") /
         rgn_lm_decode_attention_bf16, picked by
         rgn_lm_head_argmax INTO the device id buffer the next rgn_text_embed reads: no token visits the host inside a step.  The host reads
-        the ids back every `sync_every` tokens to look for EOS (never without one); the result does not depend on `sync_every`."""
-        eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
+        the ids back every `sync_every` tokens to look for EOS (never without one); the result does not depend on `sync_every`.
+        Under `sampling=True` the call also takes do_sample, temperature, top_k, top_p, repetition_penalty (None: the module's
+        generation_config value, else off), generator= or uniforms= (fp32 [max_new_tokens] on the device) and output_scores=True; the pick
+        is then rgn_lm_head_argmax for the logits and one rgn_lm_pick per token, still without a host read inside a step."""
+        plan = None
+        if self.sampling:                                                         # opt-in: without it every refusal below is what it was
+            mine = {k: kw.pop(k) for k in PICK_ARGS + PICK_EXTRA if k in kw}
+            eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, False, sync_every, kw)
+            plan = self._pick_plan(do_sample, max_new_tokens, mine)
+            if plan.greedy_as_before:
+                plan = None
+        else:
+            eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
         ids_cpu, lengths, tables, pos = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids,
                                                       mm_token_type_ids, image_embeds, {})
         L, T = ids_cpu.shape[1], int(max_new_tokens)
@@ -481,9 +574,32 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         st = _stream()
         ck = _lib.check
 
-        def pick(k):                                                              # token k from the normalised row in c["n"]
-            ck(lib.rgn_lm_head_argmax(_p(head), _p(c["n"]), V, d, ids.data_ptr() + 8 * (L + k), None if logits is None else _p(logits[k]),
-                                      _p(c["ws_h"]), ws_h, st), "rgn_lm_head_argmax")
+        if plan is None:
+            def pick(k):                                                          # token k from the normalised row in c["n"]
+                ck(lib.rgn_lm_head_argmax(_p(head), _p(c["n"]), V, d, ids.data_ptr() + 8 * (L + k), None if logits is None else _p(logits[k]),
+                                          _p(c["ws_h"]), ws_h, st), "rgn_lm_head_argmax")
+        else:
+            # the pick of this generate, chosen once: lm_head writes the fp32 row, ONE rgn_lm_pick turns it into the token in the id slot
+            ws_p = lib.rgn_lm_pick_workspace_bytes(V)
+            seen = torch.empty(V, dtype=torch.uint8, device=dev)
+            zrow = torch.empty(V, dtype=torch.float32, device=dev) if logits is None else None
+            pick_ws = torch.empty((ws_p + 3) // 4, dtype=torch.float32, device=dev)
+            scores = torch.empty(T, V, dtype=torch.float32, device=dev) if plan.output_scores else None
+            uni = plan.uniforms
+            if plan.sample and uni is None:                                       # filled before the loop; the kernel has no generator
+                g = plan.generator
+                uni = torch.rand(T, dtype=torch.float32, generator=g, device=dev if g is None else g.device).to(dev)
+            ck(lib.rgn_fill_zero(_p(seen), V, st), "rgn_fill_zero")
+            ck(lib.rgn_lm_seen_mark(_p(ids), L, _p(seen), V, st), "rgn_lm_seen_mark")
+            pen, smp, tmp, tk, tp = plan.penalty, int(plan.sample), plan.temperature, plan.top_k, plan.top_p
+            pu = uni.data_ptr() if plan.sample else None
+
+            def pick(k):
+                z = logits[k] if logits is not None else zrow
+                ck(lib.rgn_lm_head_argmax(_p(head), _p(c["n"]), V, d, ids.data_ptr() + 8 * (L + k), _p(z), _p(c["ws_h"]), ws_h, st),
+                   "rgn_lm_head_argmax")
+                ck(lib.rgn_lm_pick(_p(z), V, _p(seen), pen, smp, tmp, tk, tp, None if pu is None else pu + 4 * k, ids.data_ptr() + 8 * (L + k),
+                                   None if scores is None else _p(scores[k]), _p(pick_ws), ws_p, st), "rgn_lm_pick")
 
         h, _ = self._prefill_row(t, ids[:L], L, tab[0, 0], tab[1, 0], emb if emb is not None and emb.shape[0] else None, idx, cache=c["cache"])
         self._rms(h[L - 1:L], self.final_ln, c["n"])                              # the final norm on the last row only
@@ -534,4 +650,5 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         seq = ids[:L + n_new].to(input_ids.device)[None]
         if not return_dict_in_generate:
             return seq
-        return QwenGenerateOutput(seq, tuple(logits[k][None] for k in range(n_new)) if logits is not None else None)
+        return QwenGenerateOutput(seq, tuple(logits[k][None] for k in range(n_new)) if logits is not None else None,
+                                  tuple(scores[k][None] for k in range(n_new)) if plan is not None and scores is not None else None)

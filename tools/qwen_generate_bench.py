@@ -16,9 +16,15 @@ with `both` the bf16 and the fp8 encoder are built from the one synthetic state 
 the encoder call (`__call__`, the prefill alone) is timed for both, and every ratio is taken against the format's OWN streaming floor.  The
 GEMV A/B leg is then rgn_lm_gemv_w8 against rgn_lm_gemv_bf16 on the four layer shapes, each format walking its own ring of weight copies.
 
+`--sampling` adopts with `sampling=True` and adds two sampled legs per encoder, alternating with the greedy leg in the one process (a
+sampling adoption asked for plain greedy search takes the default path, launch for launch): `*_s20` = (repetition_penalty 1.05, temperature
+0.7, top_k 20, top_p 0.8) and `*_s0` = (1.1, 1.0, top_k off, 0.9), uniforms from a seeded generator filled before the loop; each step then
+runs one rgn_lm_pick after lm_head.  `*_ms_per_new_token` of a sampled leg against the greedy leg's is the cost of the pick.
+
     python tools/qwen_generate_bench.py [--iters 5] [--out profiles/r14_qwen_generate_bench.json] [--ab-out profiles/r14_lm_gemv_ab.txt]
     python tools/qwen_generate_bench.py --weights both --out profiles/r17_qwen_fp8_generate_bench.json --ab-out profiles/r17_lm_gemv_w8_ab.txt
     rocprofv3 --kernel-trace --stats -d DIR -o kt -- python tools/qwen_generate_bench.py --hip-only --no-ab --iters 2    # the kernel listing
+    python tools/qwen_generate_bench.py --weights both --sampling --hip-only --no-ab --out profiles/r19_qwen_sampling_bench.json
 """
 import argparse
 import json
@@ -41,6 +47,8 @@ NEW = 64
 AB_SHAPES = ((4608, 3584), (3584, 3584), (37888, 3584), (3584, 18944), (152064, 3584))
 LAYER_SHAPES = AB_SHAPES[:4]      # q|k|v, o, gate|up, down: the matrices `weights="fp8"` quantises (lm_head stays bf16)
 RING_BYTES = 1 << 30              # weight copies walked per timed pass: four times the 256 MB last-level cache
+SAMPLED = {"s20": dict(do_sample=True, repetition_penalty=1.05, temperature=0.7, top_k=20, top_p=0.8),
+           "s0": dict(do_sample=True, repetition_penalty=1.1, temperature=1.0, top_p=0.9)}
 
 
 def _ms(fn):
@@ -182,6 +190,7 @@ def main():
     ap.add_argument("--no-ab", action="store_true", help="skip the GEMV A/B")
     ap.add_argument("--no-generate", action="store_true", help="only the GEMV A/B")
     ap.add_argument("--weights", choices=("bf16", "fp8", "both"), default="bf16", help="format of the layers' projection matrices")
+    ap.add_argument("--sampling", action="store_true", help="adopt with sampling=True and time two sampled legs beside the greedy one")
     a = ap.parse_args()
     from regione_amd import build
     sha = build.csrc_hash()
@@ -231,9 +240,12 @@ def main():
         # the encoders by key prefix: "hip" is the bf16 adoption (today's keys), "hip_fp8" the fp8 one; both read the one module
         encs = {}
         if a.weights in ("bf16", "both"):
-            encs["hip"] = QT.HipQwen25VLTextEncoder(mod)
+            encs["hip"] = QT.HipQwen25VLTextEncoder(mod, sampling=a.sampling)
         if a.weights in ("fp8", "both"):
-            encs["hip_fp8"] = QT.HipQwen25VLTextEncoder(mod, weights="fp8")
+            encs["hip_fp8"] = QT.HipQwen25VLTextEncoder(mod, weights="fp8", sampling=a.sampling)
+        uni = {n: torch.rand(n, generator=torch.Generator().manual_seed(2)).cuda() for n in (1, NEW)}
+        if a.sampling:
+            res["sampled_legs"] = SAMPLED
         fmt = {"hip": "bf16", "hip_fp8": "fp8"}
         res["weights"] = a.weights
         hip = next(iter(encs.values()))
@@ -247,6 +259,10 @@ def main():
                 arms[f"{name}_64"] = lambda enc=enc: enc.generate(**kw, max_new_tokens=NEW, eos_token_id=[])
                 if a.weights != "bf16":
                     arms[f"{name}_call"] = lambda enc=enc: enc(**kw)             # the encoder call: the prefill alone
+                for leg, skw in (SAMPLED.items() if a.sampling else ()):
+                    for n in (1, NEW):
+                        arms[f"{name}_{leg}_{n}"] = lambda enc=enc, skw=skw, n=n: enc.generate(**kw, max_new_tokens=n, eos_token_id=[], uniforms=uni[n],
+                                                                                           **skw)
             if not a.hip_only:
                 ek = dict(do_sample=False, eos_token_id=None, pad_token_id=0)
                 arms["eager_1"] = lambda: mod.generate(**kw, max_new_tokens=1, min_new_tokens=1, **ek)
@@ -282,6 +298,11 @@ def main():
                     if a.weights != "bf16":
                         r[f"{side}_step_bytes"], r[f"{side}_streaming_floor_ms"] = sb, sb / HBM_BYTES_PER_S * 1e3
                         r[f"{side}_ms_per_new_token_over_its_floor"] = per / (sb / HBM_BYTES_PER_S * 1e3)
+            for name in encs:
+                for leg in (SAMPLED if a.sampling else ()):
+                    per = (r[f"{name}_{leg}_{NEW}"]["median_ms"] - r[f"{name}_{leg}_1"]["median_ms"]) / (NEW - 1)
+                    r[f"{name}_{leg}_ms_per_new_token"] = per
+                    r[f"{name}_{leg}_over_greedy_ms_per_new_token"] = per / r[f"{name}_ms_per_new_token"]
             if len(encs) == 2:
                 r["fp8_over_bf16_ms_per_new_token"] = r["hip_fp8_ms_per_new_token"] / r["hip_ms_per_new_token"]
                 r["fp8_over_bf16_call"] = r["hip_fp8_call"]["median_ms"] / r["hip_call"]["median_ms"]
