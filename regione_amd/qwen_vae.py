@@ -31,8 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .vae import (EncoderOutput, PaddedImage, UpConvWeights, _KLBase, check_image_size, conv, conv_s2, conv_up2, downsample_rows,
-                  upsample_rows)
+from .vae import EncoderOutput, PaddedImage, UpConvWeights, _KLBase, _levels_flops, _mid_flops, _wrote, check_image_size
 
 _p, _stream = ops._p, ops._stream
 
@@ -112,6 +111,7 @@ def rms_norm_silu(x: PaddedImage, gamma: torch.Tensor, c_valid: int, out: Padded
     """out = [silu](RMS_norm(x)) over the first c_valid channels (rgn_rms_norm_silu); gamma [x.C] bf16, zero past c_valid."""
     if gamma.numel() != x.C or out.C != x.C or out.rows != x.rows:
         raise _lib.RegionEHipError(f"rms_norm_silu: gamma of {gamma.numel()} channels on images of {x.C} -> {out.C} channels")
+    _wrote(out, True)
     _lib.check(_lib.lib().rgn_rms_norm_silu(x.ptr(), out.ptr(), x.Hp, x.Wp, int(c_valid), x.C, _p(gamma), int(silu), _stream()),
                "rgn_rms_norm_silu")
     return out
@@ -163,9 +163,9 @@ class _QwenBase(_KLBase):
         b = F.pad(self._raw.pop(name + ".bias").to(self.device, torch.float32), (0, co_p - co))
         return w, b
 
-    def _conv_q(self, name, ci_p, co_p, ldy=None, weights=None):
+    def _conv_q(self, name, ci_p, co_p, ldy=None, weights=None, groups=True):
         self._sd[name + ".weight"], self._sd[name + ".bias"] = self._w(name, ci_p, co_p) if weights is None else weights
-        self._conv(name, ldy=ldy)
+        self._conv(name, ldy=ldy, groups=groups)
 
     def _gamma(self, name):
         g = self._raw.pop(name + ".gamma").reshape(-1).to(self.device, torch.float32)
@@ -201,19 +201,12 @@ class _QwenBase(_KLBase):
     def _norm(self, x, name, out, silu=True):
         return rms_norm_silu(x, self.p[name + ".gamma"], self.nc[name], out, silu)
 
-    def _to_host(self, y: PaddedImage, c: int, clamp: bool) -> torch.Tensor:
+    def _to_host(self, y: PaddedImage, c: int, clamp: bool = False) -> torch.Tensor:
         out = torch.empty((1, c, 1, y.H, y.W), dtype=self.out_dtype, device=self.device)
         _lib.check(_lib.lib().rgn_padded_to_nchw_cvt(y.ptr(), y.C, _p(out), c, y.H, y.W, int(clamp), int(self.out_dtype == torch.float32),
                                                      _stream()), "rgn_padded_to_nchw_cvt")
+        self.pool.put(y)
         return out
-
-
-def _res_flops(p, ci, co):
-    return 2.0 * p * (9 * ci * co + 9 * co * co + (ci * co if ci != co else 0))
-
-
-def _mid_flops(p, c):
-    return 2 * _res_flops(p, c, c) + 2.0 * p * c * c * 4 + 4.0 * p * p * c
 
 
 class HipQwenVaeDecoder(_QwenBase):
@@ -231,12 +224,10 @@ class HipQwenVaeDecoder(_QwenBase):
         self._conv_q("post_quant_conv", 64, 64)
         self._conv_q("conv_in", 64, cs(self.top))
         self._mid_q(self.top)
-        self.u: Dict[str, UpConvWeights] = {}
-        self._up_rows = {}
         self.levels = []
         for i, (ci, co) in enumerate(zip(dims[:-1], dims[1:])):
             ci = ci // 2 if i > 0 else ci
-            for j in range(c["num_res_blocks"] + 1):
+            for j in range(self.nres):
                 self._resnet_q(f"up_blocks.{i}.resnets.{j}", ci if j == 0 else co, co)
             up = i != len(dm) - 1
             if up:
@@ -254,45 +245,21 @@ class HipQwenVaeDecoder(_QwenBase):
             raise _lib.RegionEHipError(f"HipQwenVaeDecoder.decode: one latent frame [1, {self.zc}, 1, h, w] on the GPU, got {tuple(z.shape)} on {z.device}")
         h, w = z.shape[3], z.shape[4]
         check_image_size(8 * h, 8 * w, "HipQwenVaeDecoder.decode")
-        z = z[:, :, 0].to(torch.bfloat16).contiguous()
-        Cv, pool, L = self.c, self.pool, _lib.lib()
-        zin = pool.get(h, w, 64)
-        _lib.check(L.rgn_nchw_to_padded(_p(z), zin.ptr(), self.zc, h, w, 64, _stream()), "rgn_nchw_to_padded")
-        zq = conv(zin, Cv["post_quant_conv"], pool.get(h, w, 64))
-        pool.put(zin)
-        x = conv(zq, Cv["conv_in"], pool.get(h, w, cs(self.top)))
-        pool.put(zq)
-        x = self._run_resnet(x, "mid_block.resnets.0", cs(self.top))
-        x = self._run_attention(x)
-        x = self._run_resnet(x, "mid_block.resnets.1", cs(self.top))
+        top = cs(self.top)
+        zq = self._conv_to(self._load(z[:, :, 0].to(torch.bfloat16).contiguous(), self.zc, h, w), "post_quant_conv", 64)
+        x = self._run_mid(self._conv_to(zq, "conv_in", top), top)
         for i, (ci, co, up) in enumerate(self.levels):
             for j in range(self.nres):
                 x = self._run_resnet(x, f"up_blocks.{i}.resnets.{j}", cs(co))
             if up:
-                key = (x.H, x.W)
-                if key not in self._up_rows:
-                    self._up_rows[key] = upsample_rows(x.H, x.W, self.device)
-                y = conv_up2(x, self.u[f"up_blocks.{i}.upsamplers.0.resample.1"], pool.get(2 * x.H, 2 * x.W, cs(co // 2)), self._up_rows[key])
-                pool.put(x)
-                x = y
-        n = self._norm(x, "norm_out", pool.get(x.H, x.W, x.C))
-        pool.put(x)
-        y = conv(n, Cv["conv_out"], pool.get(n.H, n.W, 8))
-        pool.put(n)
-        img = self._to_host(y, 3, clamp=True)
-        pool.put(y)
-        return img
+                x = self._up(x, f"up_blocks.{i}.upsamplers.0.resample.1", cs(co // 2))
+        return self._to_host(self._head(x, "norm_out", 8), 3, clamp=True)
 
     def flops(self, h: int, w: int) -> float:
         """Algorithmic FLOPs of one decode of an h x w latent frame as the 2-D network (valid channels; no padding, no time taps)."""
         px = h * w
-        f = 2.0 * px * self.zc * self.zc + 2.0 * px * 9 * self.zc * self.top + _mid_flops(px, self.top)
-        for ci, co, up in self.levels:
-            f += _res_flops(px, ci, co) + QWEN_VAE_CONFIG["num_res_blocks"] * _res_flops(px, co, co)
-            if up:
-                px *= 4
-                f += 2.0 * px * 9 * co * (co // 2)
-        return f + 2.0 * px * 9 * self.levels[-1][1] * 3
+        f, full = _levels_flops(px, self.levels, self.nres, 4, lambda p, co: 2.0 * p * 9 * co * (co // 2))
+        return 2.0 * px * self.zc * self.zc + 2.0 * px * 9 * self.zc * self.top + _mid_flops(px, self.top) + f + 2.0 * full * 9 * self.levels[-1][1] * 3
 
 
 class HipQwenVaeEncoder(_QwenBase):
@@ -319,9 +286,7 @@ class HipQwenVaeEncoder(_QwenBase):
             down = None
             if i != len(c["dim_mult"]) - 1:
                 down = f"down_blocks.{k}.resample.1"
-                pg, self.pixel_groups = self.pixel_groups, False          # the stride-2 launch stores through a row table: no pixel groups
-                self._conv_q(down, cs(co), cs(co))
-                self.pixel_groups = pg
+                self._conv_q(down, cs(co), cs(co), groups=False)
                 k += 1
             self.levels.append((res, down, cs(co), ci))
         self._mid_q(self.top)
@@ -331,7 +296,6 @@ class HipQwenVaeEncoder(_QwenBase):
         wq = wq[:, :, 0, 0]
         self._conv_q("conv_out", cs(self.top), 2 * self.zc, weights=(torch.einsum("oc,cikl->oikl", wq, wo), wq @ bo + bq))
         self._finish()
-        self._rows = {}
 
     @torch.no_grad()
     def encode(self, x: torch.Tensor) -> torch.Tensor:
@@ -339,45 +303,21 @@ class HipQwenVaeEncoder(_QwenBase):
             raise _lib.RegionEHipError(f"HipQwenVaeEncoder.encode: one frame [1, 3, 1, H, W] on the GPU, H and W multiples of 8; got {tuple(x.shape)} on {x.device}")
         H, W = x.shape[3], x.shape[4]
         check_image_size(H, W, "HipQwenVaeEncoder.encode")
-        x = x[:, :, 0].to(torch.bfloat16).contiguous()
-        Cv, pool, L = self.c, self.pool, _lib.lib()
-        xin = pool.get(H, W, 64)
-        _lib.check(L.rgn_nchw_to_padded(_p(x), xin.ptr(), 3, H, W, 64, _stream()), "rgn_nchw_to_padded")
-        h = conv(xin, Cv["conv_in"], pool.get(H, W, cs(self.c0)))
-        pool.put(xin)
+        h = self._conv_to(self._load(x[:, :, 0].to(torch.bfloat16).contiguous(), 3, H, W), "conv_in", cs(self.c0))
         for res, down, co, _ in self.levels:
             for r in res:
                 h = self._run_resnet(h, r, co)
             if down is not None:
-                key = (h.H, h.W)
-                if key not in self._rows:
-                    self._rows[key] = downsample_rows(h.H, h.W, self.device)
-                d = conv_s2(h, Cv[down], pool.get(h.H // 2, h.W // 2, co), self._rows[key])
-                pool.put(h)
-                h = d
-        h = self._run_resnet(h, "mid_block.resnets.0", self.top)
-        h = self._run_attention(h)
-        h = self._run_resnet(h, "mid_block.resnets.1", self.top)
-        n = self._norm(h, "norm_out", pool.get(h.H, h.W, h.C))
-        pool.put(h)
-        y = conv(n, Cv["conv_out"], pool.get(n.H, n.W, 2 * self.zc))
-        pool.put(n)
-        out = self._to_host(y, 2 * self.zc, clamp=False)
-        pool.put(y)
-        return out
+                h = self._down(h, down)
+        h = self._run_mid(h, self.top)
+        return self._to_host(self._head(h, "norm_out", 2 * self.zc), 2 * self.zc)
 
     def encode_dist(self, x: torch.Tensor) -> EncoderOutput:
         return EncoderOutput(self.encode(x))
 
     def flops(self, H: int, W: int) -> float:
-        px = H * W
-        c = QWEN_VAE_CONFIG
+        px, c, z2 = H * W, QWEN_VAE_CONFIG, 2 * self.zc
         dims = [c["base_dim"] * u for u in (1,) + tuple(c["dim_mult"])]
-        f = 2.0 * px * 9 * 3 * dims[0]
-        for i, (ci, co) in enumerate(zip(dims[:-1], dims[1:])):
-            f += _res_flops(px, ci, co) + (c["num_res_blocks"] - 1) * _res_flops(px, co, co)
-            if i != len(c["dim_mult"]) - 1:
-                px //= 4
-                f += 2.0 * px * 9 * co * co
-        z2 = 2 * self.zc
-        return f + _mid_flops(px, self.top) + 2.0 * px * 9 * self.top * z2 + 2.0 * px * z2 * z2
+        levels = [(ci, co, i != len(dims) - 2) for i, (ci, co) in enumerate(zip(dims[:-1], dims[1:]))]
+        f, low = _levels_flops(px, levels, c["num_res_blocks"], 0.25, lambda p, co: 2.0 * p * 9 * co * co)
+        return 2.0 * px * 9 * 3 * dims[0] + f + _mid_flops(low, self.top) + 2.0 * low * 9 * self.top * z2 + 2.0 * low * z2 * z2

@@ -22,6 +22,7 @@ No CPU / eager fallback: a missing library raises RegionEHipError like every oth
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Dict, List, Optional, Tuple
 
@@ -59,7 +60,8 @@ def attention_path(mode: str, rows: int) -> str:
 
 
 class PaddedImage:
-    """A zero-bordered pixel-major activation image [Hp * Wp, C] bf16 inside a storage tensor with guard rows on both sides."""
+    """A zero-bordered pixel-major activation image [Hp * Wp, C] bf16 inside a storage tensor with guard rows on both sides.
+    `border_zero`: the border rows are known to be zero - true from creation, then whatever the last writer left (`_wrote`)."""
 
     def __init__(self, H: int, W: int, C: int, device):
         self.H, self.W, self.C = H, W, C
@@ -68,6 +70,7 @@ class PaddedImage:
         g = self.Wp + 72                     # guard rows: a window reads up to Wp + 1 + group rows outside the image, pixel groups write group - 1
         self.storage = torch.zeros((self.rows + 2 * g, C), dtype=torch.bfloat16, device=device)
         self.t = self.storage[g:g + self.rows]
+        self.border_zero = True
 
     def ptr(self) -> int:
         return self.t.data_ptr()
@@ -114,19 +117,58 @@ class ConvWeights:
             self.b = b.reshape(-1).to(torch.bfloat16).contiguous()
 
 
-_gn_ws: Dict[Tuple[int, int], torch.Tensor] = {}
-_gn_owner: Dict[Tuple[int, int], Tuple[Optional["PaddedImage"], int]] = {}      # whose statistics the workspace's partial sums hold, tile count
+class GnHandoff:
+    """One stream's GroupNorm hand-off: the workspace of per-tile partial sums every image on the stream shares, and whose statistics it
+    holds right now (`owner`, in `nblk` tiles; None: nobody's).  A convolution with gn = True is the producer, the next groupnorm_silu of
+    that image the consumer; any other write to the owner in between makes the sums stale and drops them."""
+
+    def __init__(self):
+        self.ws, self.owner, self.nblk = None, None, 0
+
+    def workspace(self, device) -> torch.Tensor:
+        if self.ws is None:
+            self.ws = torch.empty(_lib.lib().rgn_groupnorm_workspace_bytes() // 4, dtype=torch.float32, device=device)
+        return self.ws
+
+    def set(self, img: Optional[PaddedImage], nblk: int = 0):
+        self.owner, self.nblk = img, nblk
+
+    def wrote(self, img: PaddedImage):
+        if self.owner is img:
+            self.set(None)
+
+    def take(self, img: PaddedImage) -> int:
+        """The tile count of `img`'s sums (0: the workspace does not hold them); consumed either way."""
+        nblk = self.nblk if self.owner is img else 0
+        self.set(None)
+        return nblk
 
 
-def _gn_key(device):
-    return (device.index if device.index is not None else torch.cuda.current_device(), _stream())
+_gn_lanes: Dict[Tuple[str, int], GnHandoff] = {}
 
 
-def _gn_workspace(device) -> torch.Tensor:
-    key = _gn_key(device)
-    if key not in _gn_ws:
-        _gn_ws[key] = torch.empty(_lib.lib().rgn_groupnorm_workspace_bytes() // 4, dtype=torch.float32, device=device)
-    return _gn_ws[key]
+def _handoff(device) -> GnHandoff:
+    return ops._ws_lane(_gn_lanes, device, GnHandoff)        # per (device, stream), bounded like the GEMM and attention scratch
+
+
+def gn_handoff(device) -> Tuple[Optional[PaddedImage], int]:
+    """(owner, tile count) of the current stream's GroupNorm hand-off."""
+    lane = _handoff(device)
+    return lane.owner, lane.nblk
+
+
+def _wrote(img: PaddedImage, border_zero: bool):
+    """Every writer of a PaddedImage reports here: what it leaves on the border, and that statistics handed off for `img` - on whichever
+    stream: the few lanes are walked, no stream is looked up - are stale."""
+    img.border_zero = border_zero
+    for lane in _gn_lanes.values():
+        lane.wrote(img)
+
+
+def _need_zero_border(img: PaddedImage, what: str):
+    if not img.border_zero:
+        raise _lib.RegionEHipError(f"{what}: the border of the {img.H} x {img.W} x {img.C} image is not known to be zero (its last writer - the "
+                                   "attention's P V GEMM - wrote it; a convolution or a norm has to rewrite the image first)")
 
 
 def conv(x: PaddedImage, cw: ConvWeights, out: PaddedImage, resid: Optional[PaddedImage] = None, gn: bool = False):
@@ -134,25 +176,27 @@ def conv(x: PaddedImage, cw: ConvWeights, out: PaddedImage, resid: Optional[Padd
     in the stream's groupnorm workspace (the next `groupnorm_silu(out, ...)` then skips its statistics pass)."""
     if cw.cin != x.C or out.C != cw.ldy or (resid is not None and (resid.C != out.C or resid.rows != out.rows)) or out.rows != x.rows:
         raise _lib.RegionEHipError(f"conv: weights for {cw.cin} -> {cw.cout} (row stride {cw.ldy}) on images with {x.C} -> {out.C} channels")
-    import ctypes
-    dev = x.t.device
-    nblk = ctypes.c_int(0)
-    ws = _gn_workspace(dev) if gn else None
-    _gn_owner[_gn_key(dev)] = (None, 0)                  # whatever the workspace held is about to be overwritten (or is left stale: same answer)
+    nblk, ws = ctypes.c_int(0), None
+    _wrote(out, True)
+    if gn:
+        lane = _handoff(x.t.device)
+        lane.set(None)                                   # whatever the workspace held is about to be overwritten
+        ws = lane.workspace(x.t.device)
     rc = _lib.lib().rgn_conv_bf16(x.ptr(), x.C, _p(cw.w), _p(cw.b), None if resid is None else resid.ptr(), out.ptr(), out.C, x.Hp, x.Wp,
                                   x.C, cw.cout, cw.taps, cw.group, _p(ws), ctypes.byref(nblk) if gn else None, _stream())
     _lib.check(rc, "rgn_conv_bf16")
     if gn:
-        _gn_owner[_gn_key(dev)] = (out, nblk.value)
+        lane.set(out, nblk.value)
     return out
 
 
 def groupnorm_silu(x: PaddedImage, gamma: torch.Tensor, beta: torch.Tensor, out: PaddedImage, silu: bool = True, eps: float = 1e-6):
-    dev = x.t.device
-    ws = _gn_workspace(dev)
-    owner, nblk = _gn_owner.get(_gn_key(dev), (None, 0))
-    pre = nblk if owner is x else 0                      # the convolution that wrote x left its tiles' sums in the workspace
-    _gn_owner[_gn_key(dev)] = (None, 0)                  # consumed
+    lane = _handoff(x.t.device)
+    pre = lane.take(x)                                   # > 0: the convolution that wrote x left its tiles' sums in the workspace
+    if pre == 0:
+        _need_zero_border(x, "groupnorm_silu")           # the statistics pass sums the border rows too
+    ws = lane.workspace(x.t.device)
+    _wrote(out, True)
     rc = _lib.lib().rgn_groupnorm_silu(x.ptr(), out.ptr(), x.Hp, x.Wp, x.C, _p(gamma), _p(beta), float(eps), int(silu), _p(ws), pre, _stream())
     _lib.check(rc, "rgn_groupnorm_silu")
     return out
@@ -160,8 +204,39 @@ def groupnorm_silu(x: PaddedImage, gamma: torch.Tensor, beta: torch.Tensor, out:
 
 def upsample2x(x: PaddedImage, out: PaddedImage):
     assert out.H == 2 * x.H and out.W == 2 * x.W and out.C == x.C
+    _wrote(out, True)
     _lib.check(_lib.lib().rgn_upsample2x(x.ptr(), out.ptr(), x.Hp, x.Wp, x.C, _stream()), "rgn_upsample2x")
     return out
+
+
+def gemm_into(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], out: PaddedImage) -> PaddedImage:
+    """out = A W^T + bias over every row of the image, border rows included (ops.gemm): they are not zero afterwards."""
+    _wrote(out, False)
+    ops.gemm(A, W, bias, out.t)
+    return out
+
+
+def _conv_shapes(s, n, co, ci, k):
+    s[n + ".weight"], s[n + ".bias"] = (co, ci, k, k), (co,)
+
+
+def _norm_shapes(s, n, c):
+    s[n + ".weight"], s[n + ".bias"] = (c,), (c,)
+
+
+def _res_shapes(s, n, ci, co):
+    _norm_shapes(s, n + ".norm1", ci); _conv_shapes(s, n + ".conv1", co, ci, 3)
+    _norm_shapes(s, n + ".norm2", co); _conv_shapes(s, n + ".conv2", co, co, 3)
+    if ci != co:
+        _conv_shapes(s, n + ".conv_shortcut", co, ci, 1)
+
+
+def _mid_shapes(s, c):
+    _res_shapes(s, "mid_block.resnets.0", c, c); _res_shapes(s, "mid_block.resnets.1", c, c)
+    a = "mid_block.attentions.0."
+    _norm_shapes(s, a + "group_norm", c)
+    for n in ("to_q", "to_k", "to_v", "to_out.0"):
+        s[a + n + ".weight"], s[a + n + ".bias"] = (c, c), (c,)
 
 
 def decoder_param_shapes(block_out_channels=(128, 256, 512, 512), latent_channels: int = 16, layers_per_block: int = 2):
@@ -169,33 +244,17 @@ def decoder_param_shapes(block_out_channels=(128, 256, 512, 512), latent_channel
     tools): a real checkpoint's `vae.decoder.state_dict()` has exactly these entries."""
     ch = list(reversed(block_out_channels))
     s: Dict[str, Tuple[int, ...]] = {}
-
-    def conv_(n, co, ci, k):
-        s[n + ".weight"], s[n + ".bias"] = (co, ci, k, k), (co,)
-
-    def norm_(n, c):
-        s[n + ".weight"], s[n + ".bias"] = (c,), (c,)
-
-    def res_(n, ci, co):
-        norm_(n + ".norm1", ci); conv_(n + ".conv1", co, ci, 3); norm_(n + ".norm2", co); conv_(n + ".conv2", co, co, 3)
-        if ci != co:
-            conv_(n + ".conv_shortcut", co, ci, 1)
-    top = ch[0]
-    conv_("conv_in", top, latent_channels, 3)
-    res_("mid_block.resnets.0", top, top); res_("mid_block.resnets.1", top, top)
-    a = "mid_block.attentions.0."
-    norm_(a + "group_norm", top)
-    for n in ("to_q", "to_k", "to_v", "to_out.0"):
-        s[a + n + ".weight"], s[a + n + ".bias"] = (top, top), (top,)
-    cin = top
+    _conv_shapes(s, "conv_in", ch[0], latent_channels, 3)
+    _mid_shapes(s, ch[0])
+    cin = ch[0]
     for i, co in enumerate(ch):
         for j in range(layers_per_block + 1):
-            res_(f"up_blocks.{i}.resnets.{j}", cin if j == 0 else co, co)
+            _res_shapes(s, f"up_blocks.{i}.resnets.{j}", cin if j == 0 else co, co)
         if i < len(ch) - 1:
-            conv_(f"up_blocks.{i}.upsamplers.0.conv", co, co, 3)
+            _conv_shapes(s, f"up_blocks.{i}.upsamplers.0.conv", co, co, 3)
         cin = co
-    norm_("conv_norm_out", cin)
-    conv_("conv_out", 3, cin, 3)
+    _norm_shapes(s, "conv_norm_out", cin)
+    _conv_shapes(s, "conv_out", 3, cin, 3)
     return s
 
 
@@ -203,32 +262,17 @@ def encoder_param_shapes(block_out_channels=(128, 256, 512, 512), latent_channel
     """The same for the encoder (`vae.encoder.state_dict()`)."""
     ch = list(block_out_channels)
     s: Dict[str, Tuple[int, ...]] = {}
-
-    def conv_(n, co, ci, k):
-        s[n + ".weight"], s[n + ".bias"] = (co, ci, k, k), (co,)
-
-    def norm_(n, c):
-        s[n + ".weight"], s[n + ".bias"] = (c,), (c,)
-
-    def res_(n, ci, co):
-        norm_(n + ".norm1", ci); conv_(n + ".conv1", co, ci, 3); norm_(n + ".norm2", co); conv_(n + ".conv2", co, co, 3)
-        if ci != co:
-            conv_(n + ".conv_shortcut", co, ci, 1)
-    conv_("conv_in", ch[0], 3, 3)
+    _conv_shapes(s, "conv_in", ch[0], 3, 3)
     cin = ch[0]
     for i, co in enumerate(ch):
         for j in range(layers_per_block):
-            res_(f"down_blocks.{i}.resnets.{j}", cin if j == 0 else co, co)
+            _res_shapes(s, f"down_blocks.{i}.resnets.{j}", cin if j == 0 else co, co)
         if i < len(ch) - 1:
-            conv_(f"down_blocks.{i}.downsamplers.0.conv", co, co, 3)
+            _conv_shapes(s, f"down_blocks.{i}.downsamplers.0.conv", co, co, 3)
         cin = co
-    res_("mid_block.resnets.0", cin, cin); res_("mid_block.resnets.1", cin, cin)
-    a = "mid_block.attentions.0."
-    norm_(a + "group_norm", cin)
-    for n in ("to_q", "to_k", "to_v", "to_out.0"):
-        s[a + n + ".weight"], s[a + n + ".bias"] = (cin, cin), (cin,)
-    norm_("conv_norm_out", cin)
-    conv_("conv_out", 2 * latent_channels, cin, 3)
+    _mid_shapes(s, cin)
+    _norm_shapes(s, "conv_norm_out", cin)
+    _conv_shapes(s, "conv_out", 2 * latent_channels, cin, 3)
     return s
 
 
@@ -254,6 +298,8 @@ def conv_s2(x: PaddedImage, cw: "ConvWeights", out: PaddedImage, rows_table: tor
     """The encoder's downsampler: 3 x 3, stride 2, F.pad (0, 1, 0, 1) (rgn_conv_s2_bf16); `rows_table` = downsample_rows(x, out)."""
     if cw.cin != x.C or out.C != cw.ldy or cw.group != 1 or cw.taps != 9 or out.H * 2 != x.H or out.W * 2 != x.W:
         raise _lib.RegionEHipError(f"conv_s2: weights for {cw.cin} -> {cw.cout} on {x.H} x {x.W} x {x.C} -> {out.H} x {out.W} x {out.C}")
+    _need_zero_border(out, "conv_s2")                    # the launch does not write its output's border rows
+    _wrote(out, True)
     rc = _lib.lib().rgn_conv_s2_bf16(x.ptr(), _p(cw.w), _p(cw.b), out.ptr(), out.C, x.Hp, x.Wp, x.C, cw.cout, _p(rows_table), _stream())
     _lib.check(rc, "rgn_conv_s2_bf16")
     return out
@@ -303,16 +349,18 @@ def conv_up2(x: PaddedImage, uw: UpConvWeights, out: PaddedImage, rows_table: to
     """out = conv3x3(upsample2x(x)) + bias without the upsampled image (rgn_conv_up2_bf16); `rows_table` = upsample_rows(x.H, x.W)."""
     if uw.cin != x.C or out.C != uw.cout or out.H != 2 * x.H or out.W != 2 * x.W:
         raise _lib.RegionEHipError(f"conv_up2: weights for {uw.cin} -> {uw.cout} on {x.H} x {x.W} x {x.C} -> {out.H} x {out.W} x {out.C}")
-    import ctypes
-    dev = x.t.device
-    nblk = ctypes.c_int(0)
-    ws = _gn_workspace(dev) if gn else None
-    _gn_owner[_gn_key(dev)] = (None, 0)
+    _need_zero_border(out, "conv_up2")                   # the launch does not write its output's border rows
+    nblk, ws = ctypes.c_int(0), None
+    _wrote(out, True)
+    if gn:
+        lane = _handoff(x.t.device)
+        lane.set(None)
+        ws = lane.workspace(x.t.device)
     rc = _lib.lib().rgn_conv_up2_bf16(x.ptr(), _p(uw.w), _p(uw.b), out.ptr(), out.C, x.Hp, x.Wp, x.C, uw.cout, _p(rows_table), _p(ws),
                                       ctypes.byref(nblk) if gn else None, _stream())
     _lib.check(rc, "rgn_conv_up2_bf16")
     if gn:
-        _gn_owner[_gn_key(dev)] = (out, nblk.value)
+        lane.set(out, nblk.value)
     return out
 
 
@@ -327,27 +375,51 @@ def downsample_rows(H: int, W: int, device) -> torch.Tensor:
     return torch.where(xo < Wo, row, torch.full_like(row, (Ho + 2) * (Wo + 2))).contiguous()
 
 
+def _res_flops(p, ci, co):
+    """Algorithmic FLOPs of one ResNet block over p pixels: 2 * pixels * Cout * taps * Cin per convolution (the shortcut where ci != co)."""
+    return 2.0 * p * (9 * ci * co + 9 * co * co + (ci * co if ci != co else 0))
+
+
+def _mid_flops(p, c):
+    """The mid block: two ResNets, the four attention projections, Q K^T and P V."""
+    return 2 * _res_flops(p, c, c) + 2.0 * p * c * c * 4 + 4.0 * p * p * c
+
+
+def _levels_flops(p, levels, nres, scale, up_flops):
+    """(FLOPs, pixels behind the last level) of levels [(cin, cout, resample)] of nres ResNets each from p pixels; a resampling level
+    multiplies the pixels by `scale` and adds up_flops(pixels behind it, cout)."""
+    f = 0.0
+    for cin, co, resample in levels:
+        f += _res_flops(p, cin, co) + (nres - 1) * _res_flops(p, co, co)
+        if resample:
+            p = int(p * scale)
+            f += up_flops(p, co)
+    return f, p
+
+
 class _KLBase:
-    """Parameter adoption shared by the decoder and the encoder."""
+    """Parameter adoption and the forward steps shared by the decoders and the encoders of both VAE families (qwen_vae.py derives from it)."""
 
     def _init_params(self, state_dict, device, prefix, pixel_groups):
         self.device = torch.device(device)
         self._sd = {(k[len(prefix):] if k.startswith(prefix) else k): v for k, v in state_dict.items()}
         self.p: Dict[str, torch.Tensor] = {}
         self.c: Dict[str, ConvWeights] = {}
+        self.u: Dict[str, UpConvWeights] = {}
         self.pixel_groups = pixel_groups
         self.fuse_gn = True              # GroupNorm statistics in the producing convolution's epilogue (False: the standalone statistics pass)
+        self.fuse_upsample = True        # nearest 2 x upsample folded into its convolution (rgn_conv_up2_bf16); False: upsample pass + 3 x 3
         self.attention = "auto"          # mid-block attention: "auto" | "fused" | "materialized" (attention_path)
         self._v_conv = None              # to_v as a 1 x 1 convolution (bias-free: b_v is added by the fused kernel), built at first use
         self.pool = _Pool(self.device)
         self._attn_buf = {}
+        self._rows = {}                  # (kind, H, W) -> row table of the resampling convolutions, built at first use
 
     def _done(self, what, ignore=()):
         unused = [k for k in self._sd if not k.startswith(tuple(ignore))]
         if unused:
             raise _lib.RegionEHipError(f"{what}: state dict entries it does not know: {unused[:6]}")
         del self._sd
-
 
     def _attention(self, a, top):
         self._vec(a + "group_norm.weight"); self._vec(a + "group_norm.bias")
@@ -365,7 +437,8 @@ class _KLBase:
     def _vec(self, name):
         self.p[name] = self._take(name).to(self.device, torch.bfloat16).contiguous()
 
-    def _conv(self, prefix, pad_in: Optional[int] = None, ldy: Optional[int] = None):
+    def _conv(self, prefix, pad_in: Optional[int] = None, ldy: Optional[int] = None, groups: bool = True):
+        """groups = False: a convolution that stores through a row table (the stride-2 launch) takes no pixel groups."""
         w = self._take(prefix + ".weight").to(self.device, torch.float32)          # [Cout, Cin, kh, kw] (or [Cout, Cin]: a Linear)
         if w.dim() == 2:
             w = w[:, :, None, None]
@@ -375,7 +448,7 @@ class _KLBase:
             w = torch.nn.functional.pad(w, (0, pad_in - ci))
         # narrow outputs fill the 256-wide MFMA tile through pixel groups: 128 channels -> 2 pixels per GEMM row, the RGB head -> 8
         group = 2 if co == 128 else (8 if co <= 8 else 1)
-        self.c[prefix] = ConvWeights(w, self._take(prefix + ".bias"), group=group if self.pixel_groups else 1, ldy=ldy)
+        self.c[prefix] = ConvWeights(w, self._take(prefix + ".bias"), group=group if self.pixel_groups and groups else 1, ldy=ldy)
 
     def _resnet(self, prefix):
         for n in ("norm1", "norm2"):
@@ -384,8 +457,32 @@ class _KLBase:
         if prefix + ".conv_shortcut.weight" in self._sd:
             self._conv(prefix + ".conv_shortcut")
 
-    # -- blocks -------------------------------------------------------------------------------------------------------------------
+    def _kl_widths(self, block_out_channels):
+        self.ch = tuple(block_out_channels)
+        for c in self.ch:
+            if c not in (128, 256, 512):
+                raise _lib.RegionEHipError(f"{type(self).__name__}: block width {c} (the kernels cover 128 / 256 / 512 channels)")
+
+    def _kl_mid(self):
+        for r in (0, 1):
+            self._resnet(f"mid_block.resnets.{r}")
+        self._attention("mid_block.attentions.0.", self.ch[-1])
+
+    # -- forward steps ------------------------------------------------------------------------------------------------------------
     _attn_norm = "group_norm"
+
+    def _load(self, x: torch.Tensor, C: int, H: int, W: int) -> PaddedImage:
+        """NCHW bf16 [1, C, H, W] -> a pooled 64-channel padded image (channels past C and the border zero)."""
+        img = self.pool.get(H, W, 64)
+        _wrote(img, True)
+        _lib.check(_lib.lib().rgn_nchw_to_padded(_p(x), img.ptr(), C, H, W, 64, _stream()), "rgn_nchw_to_padded")
+        return img
+
+    def _conv_to(self, x: PaddedImage, name: str, cout: int, gn: bool = False) -> PaddedImage:
+        """conv `name` of x into a pooled image of cout channels; x goes back to the pool."""
+        y = conv(x, self.c[name], self.pool.get(x.H, x.W, cout), gn=gn)
+        self.pool.put(x)
+        return y
 
     def _norm(self, x: PaddedImage, name: str, out: PaddedImage, silu: bool = True) -> PaddedImage:
         return groupnorm_silu(x, self.p[name + ".weight"], self.p[name + ".bias"], out, silu=silu, eps=self.eps)
@@ -407,46 +504,77 @@ class _KLBase:
         return h
 
     def _run_attention(self, x: PaddedImage) -> PaddedImage:
-        """One head of width C over every pixel (diffusers `Attention`, residual_connection=True): three GEMMs + a row softmax.  The border
-        pixels of the padded image are masked out as keys by the softmax pass and zeroed as outputs by the last projection's epilogue."""
+        """One head of width C over every pixel (diffusers `Attention`, residual_connection=True): three GEMMs + a row softmax, or - with Q, K,
+        V as 1 x 1 convolutions - one rgn_vae_attention_bf16 launch and no score matrix in memory (attention_path).  The border pixels of the
+        padded image are masked out as keys; as outputs the P V GEMM writes them (`o.border_zero` turns false: o must be rewritten before
+        anything relies on its border) and the last projection's epilogue zeroes them in `out`."""
         P, Cv, pool, a = self.p, self.c, self.pool, "mid_block.attentions.0."
         C, rows = x.C, x.rows
-        if attention_path(self.attention, rows) == "fused":
-            return self._run_attention_fused(x)
-        ldp = ops.padded(rows, 64)
-        key = (rows, C)
-        if key not in self._attn_buf:
-            self._attn_buf[key] = (torch.zeros((rows, ldp), dtype=torch.bfloat16, device=self.device),       # S / P
-                                   torch.zeros((C, ldp), dtype=torch.bfloat16, device=self.device))          # V^T (padding columns stay 0)
-        S, vt = self._attn_buf[key]
+        fused = attention_path(self.attention, rows) == "fused"
+        if fused and self._v_conv is None:
+            self._v_conv = ConvWeights(P[a + "to_v.weight"].float().reshape(C, 1, 1, C), torch.zeros(C, device=self.device))
+        if not fused:
+            ldp = ops.padded(rows, 64)
+            if (rows, C) not in self._attn_buf:
+                self._attn_buf[(rows, C)] = (torch.zeros((rows, ldp), dtype=torch.bfloat16, device=self.device),       # S / P
+                                             torch.zeros((C, ldp), dtype=torch.bfloat16, device=self.device))          # V^T (padding columns stay 0)
+            S, vt = self._attn_buf[(rows, C)]
         n = self._norm(x, a + self._attn_norm, pool.get(x.H, x.W, C), silu=False)
         q = conv(n, Cv[a + "to_q"], pool.get(x.H, x.W, C))
         k = conv(n, Cv[a + "to_k"], pool.get(x.H, x.W, C))
-        ops.gemm(P[a + "to_v.weight"], n.t, None, vt[:, :rows])                  # V^T = W_v X^T; b_v is added behind P V (rows of P sum to 1)
-        ops.gemm(q.t, k.t, None, S[:, :rows])                                     # S = Q K^T
-        _lib.check(_lib.lib().rgn_softmax_rows(_p(S), ldp, x.Hp, x.Wp, 1.0 / math.sqrt(C), _stream()), "rgn_softmax_rows")
-        o = q                                                                     # q is dead: O = P V + b_v
-        ops.gemm(S, vt, P[a + "to_v.bias"], o.t)
-        out = conv(o, Cv[a + "to_out.0"], k, resid=x, gn=self.fuse_gn)       # k is dead
-        pool.put(n); pool.put(o); pool.put(x)
+        o, v = q, None                                                            # q is dead once read: O = P V + b_v overwrites it
+        if fused:
+            v = conv(n, self._v_conv, pool.get(x.H, x.W, C))
+            _wrote(o, o.border_zero)                                              # the launch does not write O's border rows: q's stay
+            _lib.check(_lib.lib().rgn_vae_attention_bf16(q.ptr(), k.ptr(), v.ptr(), _p(P[a + "to_v.bias"]), o.ptr(), x.Hp, x.Wp, C,
+                                                         1.0 / math.sqrt(C), _stream()), "rgn_vae_attention_bf16")
+        else:
+            ops.gemm(P[a + "to_v.weight"], n.t, None, vt[:, :rows])              # V^T = W_v X^T; b_v is added behind P V (rows of P sum to 1)
+            ops.gemm(q.t, k.t, None, S[:, :rows])                                 # S = Q K^T
+            _lib.check(_lib.lib().rgn_softmax_rows(_p(S), ldp, x.Hp, x.Wp, 1.0 / math.sqrt(C), _stream()), "rgn_softmax_rows")
+            gemm_into(S, vt, P[a + "to_v.bias"], o)
+        out = conv(o, Cv[a + "to_out.0"], k, resid=x, gn=self.fuse_gn)           # k is dead; a 1 x 1 convolution: o's border rows meet nobody
+        pool.put(n); pool.put(o)
+        if v is not None:
+            pool.put(v)
+        pool.put(x)
         return out
 
-    def _run_attention_fused(self, x: PaddedImage) -> PaddedImage:
-        """The same block with Q, K, V as 1 x 1 convolutions and one rgn_vae_attention_bf16 launch: no score matrix in memory."""
-        P, Cv, pool, a = self.p, self.c, self.pool, "mid_block.attentions.0."
-        C = x.C
-        if self._v_conv is None:
-            wv = P[a + "to_v.weight"]
-            self._v_conv = ConvWeights(wv.float().reshape(C, 1, 1, C), torch.zeros(C, device=self.device))
-        n = self._norm(x, a + self._attn_norm, pool.get(x.H, x.W, C), silu=False)
-        q = conv(n, Cv[a + "to_q"], pool.get(x.H, x.W, C))
-        k = conv(n, Cv[a + "to_k"], pool.get(x.H, x.W, C))
-        v = conv(n, self._v_conv, pool.get(x.H, x.W, C))
-        o = q                                                                     # O overwrites Q (include/regione_hip.h allows it)
-        _lib.check(_lib.lib().rgn_vae_attention_bf16(q.ptr(), k.ptr(), v.ptr(), _p(P[a + "to_v.bias"]), o.ptr(), x.Hp, x.Wp, C,
-                                                     1.0 / math.sqrt(C), _stream()), "rgn_vae_attention_bf16")
-        out = conv(o, Cv[a + "to_out.0"], k, resid=x, gn=self.fuse_gn)           # k is dead; border rows of o are zeroed here
-        pool.put(n); pool.put(o); pool.put(v); pool.put(x)
+    def _run_mid(self, x: PaddedImage, c: int) -> PaddedImage:
+        x = self._run_resnet(x, "mid_block.resnets.0", c)
+        x = self._run_attention(x)
+        return self._run_resnet(x, "mid_block.resnets.1", c)
+
+    def _row_table(self, kind: str, H: int, W: int) -> torch.Tensor:
+        key = (kind, H, W)
+        if key not in self._rows:
+            self._rows[key] = (upsample_rows if kind == "up" else downsample_rows)(H, W, self.device)
+        return self._rows[key]
+
+    def _up(self, x: PaddedImage, name: str, cout: int) -> PaddedImage:
+        """Nearest 2 x upsample + the 3 x 3 convolution `name`: one launch (weights self.u), or the two passes (weights self.c)."""
+        if self.fuse_upsample:
+            y = conv_up2(x, self.u[name], self.pool.get(2 * x.H, 2 * x.W, cout), self._row_table("up", x.H, x.W), gn=self.fuse_gn)
+            self.pool.put(x)
+            return y
+        u = upsample2x(x, self.pool.get(2 * x.H, 2 * x.W, x.C))
+        self.pool.put(x)
+        return self._conv_to(u, name, cout, gn=self.fuse_gn)
+
+    def _down(self, x: PaddedImage, name: str) -> PaddedImage:
+        d = conv_s2(x, self.c[name], self.pool.get(x.H // 2, x.W // 2, x.C), self._row_table("down", x.H, x.W))
+        self.pool.put(x)
+        return d
+
+    def _head(self, x: PaddedImage, norm: str, cout: int) -> PaddedImage:
+        n = self._norm(x, norm, self.pool.get(x.H, x.W, x.C))
+        self.pool.put(x)
+        return self._conv_to(n, "conv_out", cout)
+
+    def _to_host(self, y: PaddedImage, c: int) -> torch.Tensor:
+        out = torch.empty((1, c, y.H, y.W), dtype=torch.bfloat16, device=self.device)
+        _lib.check(_lib.lib().rgn_padded_to_nchw(y.ptr(), y.C, _p(out), c, y.H, y.W, _stream()), "rgn_padded_to_nchw")
+        self.pool.put(y)
         return out
 
 
@@ -455,21 +583,12 @@ class HipVaeDecoder(_KLBase):
 
     def __init__(self, state_dict, device, block_out_channels=(128, 256, 512, 512), latent_channels: int = 16, layers_per_block: int = 2,
                  norm_eps: float = 1e-6, pixel_groups: bool = True):
-        self.ch = tuple(block_out_channels)
+        self._kl_widths(block_out_channels)
         self.zc, self.nres, self.eps = latent_channels, layers_per_block + 1, norm_eps
         self._init_params(state_dict, device, "decoder.", pixel_groups)
-        self.u: Dict[str, UpConvWeights] = {}
-        self.fuse_upsample = True        # nearest 2 x upsample folded into its convolution (rgn_conv_up2_bf16); False: upsample pass + 3 x 3
-        self._up_rows = {}
-        top = self.ch[-1]
-        for c in self.ch:
-            if c not in (128, 256, 512):
-                raise _lib.RegionEHipError(f"HipVaeDecoder: block width {c} (the kernels cover 128 / 256 / 512 channels)")
         self._conv("conv_in", pad_in=64)
-        for r in (0, 1):
-            self._resnet(f"mid_block.resnets.{r}")
-        self._attention("mid_block.attentions.0.", top)
-        cin = top
+        self._kl_mid()
+        cin = self.ch[-1]
         self.levels = []
         for i, co in enumerate(reversed(self.ch)):
             for j in range(self.nres):
@@ -488,62 +607,27 @@ class HipVaeDecoder(_KLBase):
             raise _lib.RegionEHipError("HipVaeDecoder: post_quant_conv is not part of the FLUX.1 / Step1X-Edit VAE (use_post_quant_conv = False)")
         self._done("HipVaeDecoder", ignore=("encoder.", "quant_conv"))
 
-    # -- decode -------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         if not z.is_cuda or z.dim() != 4 or z.shape[0] != 1 or z.shape[1] != self.zc:
             raise _lib.RegionEHipError(f"HipVaeDecoder.decode: one latent image [1, {self.zc}, h, w] on the GPU, got {tuple(z.shape)} on {z.device}")
         h, w = z.shape[2], z.shape[3]
         check_image_size(8 * h, 8 * w, "HipVaeDecoder.decode")
-        z = z.to(torch.bfloat16).contiguous()
-        P, Cv, pool, L = self.p, self.c, self.pool, _lib.lib()
-        zin = pool.get(h, w, 64)
-        _lib.check(L.rgn_nchw_to_padded(_p(z), zin.ptr(), self.zc, h, w, 64, _stream()), "rgn_nchw_to_padded")
         top = self.ch[-1]
-        x = conv(zin, Cv["conv_in"], pool.get(h, w, top), gn=self.fuse_gn)
-        pool.put(zin)
-        x = self._run_resnet(x, "mid_block.resnets.0", top)
-        x = self._run_attention(x)
-        x = self._run_resnet(x, "mid_block.resnets.1", top)
+        x = self._conv_to(self._load(z.to(torch.bfloat16).contiguous(), self.zc, h, w), "conv_in", top, gn=self.fuse_gn)
+        x = self._run_mid(x, top)
         for i, (cin, co, up) in enumerate(self.levels):
             for j in range(self.nres):
                 x = self._run_resnet(x, f"up_blocks.{i}.resnets.{j}", co)
             if up:
-                name = f"up_blocks.{i}.upsamplers.0.conv"
-                if self.fuse_upsample:
-                    key = (x.H, x.W)
-                    if key not in self._up_rows:
-                        self._up_rows[key] = upsample_rows(x.H, x.W, self.device)
-                    y = conv_up2(x, self.u[name], pool.get(2 * x.H, 2 * x.W, x.C), self._up_rows[key], gn=self.fuse_gn)
-                    pool.put(x)
-                    x = y
-                else:
-                    u = upsample2x(x, pool.get(2 * x.H, 2 * x.W, x.C))
-                    pool.put(x)
-                    x = conv(u, Cv[name], pool.get(u.H, u.W, u.C), gn=self.fuse_gn)
-                    pool.put(u)
-        n = groupnorm_silu(x, P["conv_norm_out.weight"], P["conv_norm_out.bias"], pool.get(x.H, x.W, x.C), eps=self.eps)
-        pool.put(x)
-        y = conv(n, Cv["conv_out"], pool.get(n.H, n.W, 8))
-        pool.put(n)
-        img = torch.empty((1, 3, y.H, y.W), dtype=torch.bfloat16, device=self.device)
-        _lib.check(L.rgn_padded_to_nchw(y.ptr(), 8, _p(img), 3, y.H, y.W, _stream()), "rgn_padded_to_nchw")
-        pool.put(y)
-        return img
+                x = self._up(x, f"up_blocks.{i}.upsamplers.0.conv", co)
+        return self._to_host(self._head(x, "conv_norm_out", 8), 3)
 
     def flops(self, h: int, w: int) -> float:
         """Algorithmic FLOPs of one decode of an h x w latent (2 * valid pixels * Cout * taps * Cin per convolution + the attention GEMMs)."""
-        top = self.ch[-1]
-        px = h * w
-        f = 2.0 * px * top * 9 * self.zc
-        res = lambda p, ci, co: 2.0 * p * (9 * ci * co + 9 * co * co + (ci * co if ci != co else 0))
-        f += 2 * res(px, top, top) + 2.0 * px * top * top * 4 + 4.0 * px * px * top
-        for cin, co, up in self.levels:
-            f += res(px, cin, co) + (self.nres - 1) * res(px, co, co)
-            if up:
-                px *= 4
-                f += 2.0 * px * 9 * co * co
-        return f + 2.0 * px * 9 * self.ch[0] * 3
+        top, px = self.ch[-1], h * w
+        f, full = _levels_flops(px, self.levels, self.nres, 4, lambda p, co: 2.0 * p * 9 * co * co)
+        return 2.0 * px * top * 9 * self.zc + _mid_flops(px, top) + f + 2.0 * full * 9 * self.ch[0] * 3
 
 
 class LatentDist:
@@ -578,12 +662,9 @@ class HipVaeEncoder(_KLBase):
 
     def __init__(self, state_dict, device, block_out_channels=(128, 256, 512, 512), latent_channels: int = 16, layers_per_block: int = 2,
                  norm_eps: float = 1e-6, pixel_groups: bool = True):
-        self.ch = tuple(block_out_channels)
+        self._kl_widths(block_out_channels)
         self.zc, self.nres, self.eps = latent_channels, layers_per_block, norm_eps
         self._init_params(state_dict, device, "encoder.", pixel_groups)
-        for c in self.ch:
-            if c not in (128, 256, 512):
-                raise _lib.RegionEHipError(f"HipVaeEncoder: block width {c} (the kernels cover 128 / 256 / 512 channels)")
         self._conv("conv_in", pad_in=64)
         cin = self.ch[0]
         self.levels = []
@@ -592,21 +673,15 @@ class HipVaeEncoder(_KLBase):
                 self._resnet(f"down_blocks.{i}.resnets.{j}")
             down = i < len(self.ch) - 1
             if down:
-                pg, self.pixel_groups = self.pixel_groups, False         # the stride-2 launch stores through a row table: no pixel groups
-                self._conv(f"down_blocks.{i}.downsamplers.0.conv")
-                self.pixel_groups = pg
+                self._conv(f"down_blocks.{i}.downsamplers.0.conv", groups=False)
             self.levels.append((cin, co, down))
             cin = co
-        top = self.ch[-1]
-        for r in (0, 1):
-            self._resnet(f"mid_block.resnets.{r}")
-        self._attention("mid_block.attentions.0.", top)
+        self._kl_mid()
         self._vec("conv_norm_out.weight"); self._vec("conv_norm_out.bias")
         self._conv("conv_out")
         if any(k.startswith("quant_conv") for k in self._sd):
             raise _lib.RegionEHipError("HipVaeEncoder: quant_conv is not part of the FLUX.1 / Step1X-Edit VAE (use_quant_conv = False)")
         self._done("HipVaeEncoder", ignore=("decoder.", "post_quant_conv"))
-        self._rows = {}
 
     @torch.no_grad()
     def encode(self, x: torch.Tensor) -> torch.Tensor:
@@ -614,46 +689,19 @@ class HipVaeEncoder(_KLBase):
             raise _lib.RegionEHipError(f"HipVaeEncoder.encode: one image [1, 3, H, W] on the GPU, H and W multiples of 8; got {tuple(x.shape)} on {x.device}")
         H, W = x.shape[2], x.shape[3]
         check_image_size(H, W, "HipVaeEncoder.encode")
-        x = x.to(torch.bfloat16).contiguous()
-        P, Cv, pool, L = self.p, self.c, self.pool, _lib.lib()
-        xin = pool.get(H, W, 64)
-        _lib.check(L.rgn_nchw_to_padded(_p(x), xin.ptr(), 3, H, W, 64, _stream()), "rgn_nchw_to_padded")
-        h = conv(xin, Cv["conv_in"], pool.get(H, W, self.ch[0]), gn=self.fuse_gn)
-        pool.put(xin)
+        h = self._conv_to(self._load(x.to(torch.bfloat16).contiguous(), 3, H, W), "conv_in", self.ch[0], gn=self.fuse_gn)
         for i, (cin, co, down) in enumerate(self.levels):
             for j in range(self.nres):
                 h = self._run_resnet(h, f"down_blocks.{i}.resnets.{j}", co)
             if down:
-                key = (h.H, h.W)
-                if key not in self._rows:
-                    self._rows[key] = downsample_rows(h.H, h.W, self.device)
-                d = conv_s2(h, Cv[f"down_blocks.{i}.downsamplers.0.conv"], pool.get(h.H // 2, h.W // 2, h.C), self._rows[key])
-                pool.put(h)
-                h = d
-        top = self.ch[-1]
-        h = self._run_resnet(h, "mid_block.resnets.0", top)
-        h = self._run_attention(h)
-        h = self._run_resnet(h, "mid_block.resnets.1", top)
-        n = groupnorm_silu(h, P["conv_norm_out.weight"], P["conv_norm_out.bias"], pool.get(h.H, h.W, h.C), eps=self.eps)
-        pool.put(h)
-        y = conv(n, Cv["conv_out"], pool.get(n.H, n.W, 2 * self.zc))
-        pool.put(n)
-        out = torch.empty((1, 2 * self.zc, y.H, y.W), dtype=torch.bfloat16, device=self.device)
-        _lib.check(L.rgn_padded_to_nchw(y.ptr(), y.C, _p(out), 2 * self.zc, y.H, y.W, _stream()), "rgn_padded_to_nchw")
-        pool.put(y)
-        return out
+                h = self._down(h, f"down_blocks.{i}.downsamplers.0.conv")
+        h = self._run_mid(h, self.ch[-1])
+        return self._to_host(self._head(h, "conv_norm_out", 2 * self.zc), 2 * self.zc)
 
     def encode_dist(self, x: torch.Tensor) -> EncoderOutput:
         return EncoderOutput(self.encode(x))
 
     def flops(self, H: int, W: int) -> float:
-        px = H * W
-        f = 2.0 * px * self.ch[0] * 9 * 3
-        res = lambda p, ci, co: 2.0 * p * (9 * ci * co + 9 * co * co + (ci * co if ci != co else 0))
-        for cin, co, down in self.levels:
-            f += res(px, cin, co) + (self.nres - 1) * res(px, co, co)
-            if down:
-                px //= 4
-                f += 2.0 * px * 9 * co * co
-        top = self.ch[-1]
-        return f + 2 * res(px, top, top) + 2.0 * px * top * top * 4 + 4.0 * px * px * top + 2.0 * px * 9 * top * 2 * self.zc
+        top, px = self.ch[-1], H * W
+        f, low = _levels_flops(px, self.levels, self.nres, 0.25, lambda p, co: 2.0 * p * 9 * co * co)
+        return 2.0 * px * self.ch[0] * 9 * 3 + f + _mid_flops(low, top) + 2.0 * low * 9 * top * 2 * self.zc

@@ -141,10 +141,10 @@ def test_groupnorm_statistics_from_the_convolution_epilogue(H, W, cin, cout, gro
         y, n = V.PaddedImage(H, W, cout, "cuda"), V.PaddedImage(H, W, cout, "cuda")
         with _lib.plan_override(gemm_geometry=geometry):
             V.conv(xi, cw, y, resid=ri, gn=fused)
-        owner, nblk = V._gn_owner[V._gn_key(y.t.device)]
+        owner, nblk = V.gn_handoff(y.t.device)
         assert (owner is y and nblk > 0) if fused else owner is None
         V.groupnorm_silu(y, gamma, beta, n)
-        assert V._gn_owner[V._gn_key(y.t.device)][0] is None           # consumed
+        assert V.gn_handoff(y.t.device)[0] is None                     # consumed
         torch.cuda.synchronize()
         outs.append((_unpadded(y), _unpadded(n)))
     assert torch.equal(outs[0][0], outs[1][0])                           # the convolution's output does not depend on the statistics option

@@ -1,8 +1,8 @@
 """-m gpu: one VAE object called again and again at changing sizes, as the hosted pipelines call theirs (one decoder and one encoder per pipe
-for the life of the pipe, at whatever resolution each edit resizes to).  Two invariants of regione_amd/vae.py hold only through call order:
-  * every buffer in a `_Pool` has an all-zero border (rgn_conv_s2_bf16 and rgn_conv_up2_bf16 do not write their outputs' borders, and the
-    standalone GroupNorm statistics pass sums the border rows too);
-  * `_gn_owner` - whose GroupNorm partial sums the stream's shared workspace holds - is shared by every VAE object on the stream.
+for the life of the pipe, at whatever resolution each edit resizes to).  Two invariants of regione_amd/vae.py, kept by `_wrote`:
+  * every buffer in a `_Pool` has an all-zero border once a call is over (rgn_conv_s2_bf16 and rgn_conv_up2_bf16 do not write their
+    outputs' borders, and the standalone GroupNorm statistics pass sums the border rows too); `PaddedImage.border_zero` says so;
+  * the GroupNorm hand-off - whose partial sums the stream's shared workspace holds - is shared by every VAE object on the stream.
 Latents h x w, 2h x 2w, h x w, h x 2w with h = 8: at 2h the mid-block attention runs at the size a later h x w call's first upsampling
 convolution writes (and the encoder's last stride-2 convolution always writes the mid-block size); the same family's decoder and encoder
 interleaved on one stream.  Each output must equal, bit for bit, the first call of a freshly built object at that size; after every call,

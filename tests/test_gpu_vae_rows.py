@@ -323,7 +323,7 @@ def test_groupnorm_epilogue_statistics_large_mean(H, W, cin, cout, group, ratio)
     cw = V.ConvWeights(w.permute(0, 2, 3, 1).cuda(), b.cuda(), group=group)
     y, n = V.PaddedImage(H, W, cout, "cuda"), V.PaddedImage(H, W, cout, "cuda")
     V.conv(xi, cw, y, resid=ri, gn=True)
-    owner, nblk = V._gn_owner[V._gn_key(y.t.device)]
+    owner, nblk = V.gn_handoff(y.t.device)
     assert owner is y and nblk > 0
     yv = _unpadded(y).double().cpu()
     t = y.t.view(y.Hp, y.Wp, cout)
