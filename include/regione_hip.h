@@ -54,7 +54,8 @@ int rgn_plan_override(const char* key, int value);
 int rgn_plan_override_get(const char* key, int* value);
 /* The launch plan the GEMM planner chose for the last rgn_gemm_group call on this thread (introspection for tests and traces; the
  * reference has no counterpart): bits 0-7 = K pieces of the remainder (1 = none), bit 8 = quarter-tile remainder, bit 10 =
- * 256 x 256 tile geometry, bit 11 = launched as two row bands (rgn_rowband_fork). */
+ * 256 x 256 tile geometry, bit 11 = launched as two row bands (rgn_rowband_fork), bits 12-15 = K pieces of the remainder on the
+ * 128 x 128 geometry (0 = not cut; only ever set with bit 10 clear). */
 int rgn_gemm_last_plan(void);
 /* The plan the planner WOULD choose for a group of `nprob` (<= 4) problems with M = Ms[i] rows, N output channels, depth K, `distinct_w`
  * different weight matrices (problems of one stream share W), bf16 (w8 = 0) or fp8 (w8 = 1) weights and a workspace of
