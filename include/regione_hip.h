@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 116
+#define RGN_ABI_VERSION 117
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -647,6 +647,27 @@ typedef struct rgn_mmdit_block {
 int rgn_mmdit_double_block(const rgn_mmdit_block* b, void* stream);
 int rgn_mmdit_single_block(const rgn_mmdit_block* b, void* stream);
 size_t rgn_mmdit_block_bytes(void);
+
+/* ------------------------------------------------------------------------------------------
+ * a11  LoRA merge into a bf16 weight (csrc/lora.hip; no reference counterpart: the reference runs whatever modules the host pipeline
+ * holds, PEFT side paths included).  Adoption-time work, never on the per-step path:
+ *   dst[n, k] = bf16_rne(t),   t = f32(W[n, k]);   for each term in order:  acc = 0;  for r ascending: acc = fmaf(B[n, r], A[r, k], acc);
+ *                                                                           t = fmaf(scale, acc, t)
+ * One rounding to bf16 per element; the delta is never rounded on its own; fixed order, no atomics: a repeated call is bit-identical.
+ * dst, W [N, K] bf16 with row strides ldd, ldw in elements (>= K, multiples of 8): a destination may be a row range of a packed tensor.
+ * dst == W with ldd == ldw is the in-place form (every element is read once and written once by the same lane); any other overlap
+ * of dst with W is undefined.  `terms` is a HOST array of n_terms descriptors read at call time; A [r, K] and B [N, r] are dense
+ * row-major fp32 DEVICE tensors (A 16-byte aligned).  1 <= n_terms <= RGN_LORA_MAX_TERMS, 1 <= r <= RGN_LORA_MAX_RANK, K % 8 == 0,
+ * dst and W 16-byte aligned; N == 0 returns 0 without looking further.  Every refusal is RGN_E_BADARG before any launch. */
+#define RGN_LORA_MAX_TERMS 8
+#define RGN_LORA_MAX_RANK 1024
+typedef struct rgn_lora_term {
+    const float* A;            /* [r, K] */
+    const float* B;            /* [N, r] */
+    int r;
+    float scale;
+} rgn_lora_term;
+int rgn_lora_merge_bf16(void* dst, int ldd, const void* W, int ldw, int N, int K, const rgn_lora_term* terms, int n_terms, void* stream);
 
 /* Device properties the host side needs for roofline reporting (no torch types). */
 int rgn_device_info(int* cu_count, int* clock_khz, size_t* hbm_bytes);

@@ -63,6 +63,14 @@ class MmditBlock(C.Structure):
 
 _block_p = C.POINTER(MmditBlock)
 
+
+class LoraTerm(C.Structure):
+    """struct rgn_lora_term (include/regione_hip.h): one `scale * B A` term of rgn_lora_merge_bf16 (A [r, K], B [N, r] fp32 on the device)."""
+    _fields_ = [("A", _c_void_p), ("B", _c_void_p), ("r", _c_int), ("scale", _c_float)]
+
+
+_term_p = C.POINTER(LoraTerm)
+
 # name -> argtypes (restype is always int unless listed in _RESTYPE)
 SIGNATURES = {
     "rgn_version": [],
@@ -162,6 +170,8 @@ SIGNATURES = {
     "rgn_mmdit_double_block": [_block_p, _c_void_p],
     "rgn_mmdit_single_block": [_block_p, _c_void_p],
     "rgn_mmdit_block_bytes": [],
+    # a11: LoRA merge into a bf16 weight at adoption (csrc/lora.hip)
+    "rgn_lora_merge_bf16": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _term_p, _c_int, _c_void_p],
 }
 _RESTYPE = {"rgn_last_error": C.c_char_p, "rgn_abi_struct_bytes": C.c_size_t, "rgn_attention_workspace_bytes": C.c_size_t,
             "rgn_gemm_workspace_bytes": C.c_size_t, "rgn_groupnorm_workspace_bytes": C.c_size_t,

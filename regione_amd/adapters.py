@@ -20,6 +20,9 @@ the host's own methods in the order the reference's patched `__call__` does (Reg
 diffusers is not installed in the build image: the call sequence follows the reference's copy of the diffusers
 `__call__`, and is exercised in tests/test_adapters.py against host-pipeline stand-ins with the same method surface
 (tests/host_trunks.py module trees, whose own vanilla forward the adopted engine is compared with).  Treat the first run against a real checkpoint as the remaining validation step.
+
+LoRA adapters loaded into the host transformer (PEFT layers: `load_lora_weights` without `fuse_lora`) are merged into the engine's weights
+on the device at adoption and re-merged when the adapter state changes (`lora_sync`, the LoRA section below): no per-step side path.
 """
 from __future__ import annotations
 
@@ -92,9 +95,196 @@ def _axes_dim(transformer):
     return tuple(pe.axes_dim) if pe is not None and hasattr(pe, "axes_dim") else None
 
 
-def _stream(sd, family: str, device) -> Iterator[Tuple[str, torch.Tensor]]:
-    for k, v in sd.items():
-        yield map_key(k, family), v.detach().to(device=device, dtype=torch.bfloat16)
+# ---------------------------------------------------------------------------------------------------------------------
+# LoRA on the trunk (PEFT layout): merged on the device at adoption, re-merged when the adapter state changes
+# ---------------------------------------------------------------------------------------------------------------------
+# `pipe.load_lora_weights(...)` without `fuse_lora()` leaves PEFT layers in pipe.transformer: a wrapped Linear X holds `X.base_layer`,
+# `X.lora_A[adapter]` ([r, in]) and `X.lora_B[adapter]` ([out, r]) Linears, `X.scaling[adapter]` (alpha / r times the set_adapters weight),
+# `X.active_adapters`, `X.disable_adapters`, `X.merged_adapters`.  The engine has no per-step side path: it holds
+# W_eff = W_base + sum over the active, not disabled adapters of scaling[a] * B_a A_a, built by rgn_lora_merge_bf16 (ops.lora_merge: fp32
+# fma in adapter order, ONE rounding to bf16) in the engine's packed layouts.  `lora_dropout` is training-only and ignored.
+_PEFT_OTHER_TUNERS = ("lokr_", "hada_", "ia3_")
+
+
+def _lora_decline(what: str):
+    raise NotImplementedError(f"host transformer carries {what}: the HIP engine merges plain LoRA on the trunk's Linear layers only "
+                              "(fuse or unload it on the host first)")
+
+
+def lora_layers(transformer) -> Dict[str, object]:
+    """{module path: PEFT LoRA wrapper} of a host transformer ({} for a module tree without any, or an object without named_modules)."""
+    if not hasattr(transformer, "named_modules"):
+        return {}
+    return {n: m for n, m in transformer.named_modules() if hasattr(m, "base_layer") and hasattr(m, "lora_A")}
+
+
+def _lora_active(m):
+    """The adapters a wrapped module applies in its forward, in `active_adapters` order: none when the adapters are disabled or when the
+    module is merged (PEFT merge_adapter / fuse_lora already added them to base_layer.weight: they are not applied a second time)."""
+    if getattr(m, "disable_adapters", False) or list(getattr(m, "merged_adapters", None) or ()):
+        return []
+    act = getattr(m, "active_adapters", None)
+    if act is None:
+        act = getattr(m, "active_adapter", ())
+    if isinstance(act, str):
+        act = [act]
+    return [a for a in act if a in m.lora_A]
+
+
+def _lora_checked(transformer, sd, ignore_prefixes) -> Dict[str, object]:
+    """lora_layers() of the trunk (layers under an ignored prefix stay the host's business) after every by-name refusal - host-side
+    attribute and shape reads only, nothing allocated, nothing launched."""
+    for k in sd:
+        for t in _PEFT_OTHER_TUNERS:
+            if t in k:
+                _lora_decline(f"a non-LoRA PEFT tuner ({t}* in {k!r})")
+        if "lora_embedding_" in k:
+            _lora_decline(f"a LoRA embedding layer (lora_embedding_* in {k!r})")
+        if "lora_magnitude_vector" in k:
+            _lora_decline(f"DoRA (lora_magnitude_vector in {k!r})")
+    layers = {n: m for n, m in lora_layers(transformer).items() if not n.startswith(tuple(ignore_prefixes))}
+    for n, m in layers.items():
+        if any(dict(getattr(m, "use_dora", None) or {}).values()) or len(getattr(m, "lora_magnitude_vector", None) or ()):
+            _lora_decline(f"DoRA (use_dora / lora_magnitude_vector on {n})")
+        if len(getattr(m, "lora_embedding_A", None) or ()) or len(getattr(m, "lora_embedding_B", None) or ()):
+            _lora_decline(f"a LoRA embedding layer (lora_embedding_* on {n})")
+        if any(dict(getattr(m, "lora_bias", None) or {}).values()) or any(getattr(b, "bias", None) is not None for b in m.lora_B.values()):
+            _lora_decline(f"lora_bias=True on {n}")
+        base = m.base_layer
+        if hasattr(base, "lora_A") or not isinstance(base, torch.nn.Linear):
+            _lora_decline(f"LoRA on {n}, a {type(base).__name__}, not a Linear the trunk layout knows")
+        act = _lora_active(m)
+        if len(act) > ops.LORA_MAX_TERMS:
+            _lora_decline(f"{len(act)} active adapters on {n} (at most {ops.LORA_MAX_TERMS} are merged)")
+        out_f, in_f = base.weight.shape
+        for a in act:
+            A, B = m.lora_A[a].weight, m.lora_B[a].weight
+            if A.dim() != 2 or B.dim() != 2 or A.shape[1] != in_f or B.shape[0] != out_f or A.shape[0] != B.shape[1]:
+                _lora_decline(f"adapter {a!r} on {n} with A {tuple(A.shape)} / B {tuple(B.shape)} that do not fit the base weight {(out_f, in_f)}")
+            if A.shape[0] > ops.LORA_MAX_RANK:
+                _lora_decline(f"adapter {a!r} on {n} of rank {A.shape[0]} > {ops.LORA_MAX_RANK}")
+    return layers
+
+
+def _peft_names(sd, layers) -> Dict[str, str]:
+    """host state-dict key -> the name it has without the PEFT wrapper levels (`X.base_layer.weight` -> `X.weight`); the adapters' own
+    tensors (`X.lora_A.<adapter>.weight`, `X.lora_B.<adapter>.weight`) are left out.  The identity for a host without LoRA layers."""
+    if not layers:
+        return {k: k for k in sd}
+    own = tuple(n + s for n in layers for s in (".lora_A.", ".lora_B."))
+    return {k: k.replace(".base_layer.", ".") for k in sd if not k.startswith(own)}
+
+
+def _ver(t):
+    return None if t.is_inference() else t._version
+
+
+def _lora_fingerprint(layers, scale: float) -> Dict[str, tuple]:
+    """Per wrapped module, everything its effective weight depends on - host-side reads only (no device reads): the active adapters, their
+    `scaling` times the call-time scale, disable_adapters, merged_adapters, (data_ptr, _version) of the base weight and of each A / B."""
+    fp = {}
+    for n, m in layers.items():
+        act = _lora_active(m)
+        w = m.base_layer.weight
+        fp[n] = (tuple(act), tuple(float(m.scaling[a]) * scale for a in act), bool(getattr(m, "disable_adapters", False)),
+                 tuple(getattr(m, "merged_adapters", None) or ()), (w.data_ptr(), _ver(w)),
+                 tuple((t.data_ptr(), _ver(t)) for a in act for t in (m.lora_A[a].weight, m.lora_B[a].weight)))
+    return fp
+
+
+def _lora_terms(m, device, scale: float):
+    """[(A [r, in] fp32, B [out, r] fp32, scaling * scale)] on the device for the module's active adapters (real LoRA files are bf16, fp16
+    or fp32 and tiny: converted once per merge)."""
+    return [(m.lora_A[a].weight.detach().to(device, torch.float32).contiguous(),
+             m.lora_B[a].weight.detach().to(device, torch.float32).contiguous(), float(m.scaling[a]) * scale) for a in _lora_active(m)]
+
+
+def _staged(host_w, device):
+    return host_w.detach().to(device=device, dtype=torch.bfloat16).contiguous()
+
+
+def _stream(sd, names, family: str, device, lora=None, scale: float = 1.0) -> Iterator[Tuple[str, torch.Tensor]]:
+    """(engine name, bf16 device tensor) of every host tensor; a LoRA-carrying weight is merged here, in place on its staged copy, before
+    load_state_dict_stream packs it (the engine never writes to a host tensor: a host already on the device in bf16 gets a new one)."""
+    for k, stripped in names.items():
+        name, v = map_key(stripped, family), sd[k]
+        m = lora.get(name) if lora else None
+        terms = _lora_terms(m, device, scale) if m is not None else None
+        if not terms:
+            yield name, v.detach().to(device=device, dtype=torch.bfloat16)
+            continue
+        w = _staged(v, device)
+        yield name, ops.lora_merge(w if w.data_ptr() != v.data_ptr() else torch.empty_like(w), w, terms)
+
+
+def _lora_plan(pipe, family, ignore_prefixes):
+    """(state dict, key -> stripped name, {engine weight name: wrapped module}) of the host transformer, refusals raised."""
+    sd = pipe.transformer.state_dict()
+    layers = _lora_checked(pipe.transformer, sd, ignore_prefixes)
+    return sd, _peft_names(sd, layers), {map_key(n + ".weight", family): m for n, m in layers.items()}
+
+
+def lora_sync(pipe, engine, scale: float = 1.0, ignore_prefixes: Tuple[str, ...] = ("connector.",)) -> bool:
+    """Bring the engine's weights to the host transformer's CURRENT adapter state (set_adapters, disable_lora, unload_lora_weights, a
+    second load_lora_weights, fuse_lora, a call-time scale): compare the host-side fingerprint with the one the weights were built
+    from and, when it differs, re-stage the base rows of every engine weight whose module changed and re-apply its terms into the
+    recorded slot (FluxTransformer2DModel.weight_slots); an fp8 trunk rebuilds and re-quantises the touched packed tensors.  False: the
+    fingerprint is unchanged, nothing was launched."""
+    tr = engine.transformer
+    rec = tr.__dict__.get("_lora")
+    if rec is None:
+        return False                                             # an engine that was not adopted from a host pipeline
+    layers = {n: m for n, m in lora_layers(pipe.transformer).items() if not n.startswith(tuple(ignore_prefixes))}
+    if not layers and not rec["fp"]:
+        return False                                             # a pipeline that never saw a LoRA
+    family = rec["family"]
+    scale = float(scale) if layers else 1.0
+    fp = {map_key(n + ".weight", family): v for n, v in _lora_fingerprint(layers, scale).items()}
+    if fp == rec["fp"]:
+        return False
+    sd, names, lora = _lora_plan(pipe, family, ignore_prefixes)
+    slots, dev = tr.weight_slots(), tr.device
+    bad = [k for k in lora if k not in slots]
+    if bad:
+        _lora_decline(f"LoRA on {bad[0][:-len('.weight')]}, not a Linear the trunk layout knows")
+    host_key = {map_key(s, family): k for k, s in names.items()}
+    touched = sorted(k for k in set(fp) | set(rec["fp"]) if fp.get(k) != rec["fp"].get(k))
+
+    def fill(rows, name):
+        """rows <- the host's base weight with the module's current terms."""
+        w = _staged(sd[host_key[name]], dev)
+        m = lora.get(name)
+        terms = _lora_terms(m, dev, scale) if m is not None else []
+        if terms:
+            ops.lora_merge(rows, w, terms)
+        elif rows.data_ptr() != w.data_ptr():
+            rows.copy_(w)
+
+    done = set()
+    for name in touched:
+        obj, attr, lo, hi = slots[name]
+        tgt = getattr(obj, attr)
+        if tgt.dtype == ops.FP8:                                 # rebuild the whole packed tensor in bf16, then quantise it as quantize_fp8_ does
+            if (id(obj), attr) in done:
+                continue
+            done.add((id(obj), attr))
+            full = torch.empty(tgt.shape, dtype=torch.bfloat16, device=dev)
+            for n, s in slots.items():
+                if s[0] is obj and s[1] == attr:
+                    fill(full[s[2]:s[3]] if s[3] is not None else full, n)
+            setattr(obj, attr, ops.quantize_w8(full))
+        elif hi is None and tgt.data_ptr() == sd[host_key[name]].data_ptr():
+            # adopted without a copy from a host that is already on the device in bf16: the engine never writes to a host tensor
+            full = torch.empty_like(tgt)
+            fill(full, name)
+            setattr(obj, attr, full)
+        else:
+            fill(tgt[lo:hi] if hi is not None else tgt, name)
+    if any(re.search(r"\.(to_[qkv]|add_[qkv]_proj)\.weight$", n) for n in touched):
+        tr.refresh_score_bounds()
+    tr.clear_modulations()                                       # AdaLN tables of earlier edits were built from the old mod_w / embedders
+    rec["fp"] = fp
+    return True
 
 
 def adopt_engine(pipe, device="cuda", family: Optional[str] = None, ignore_prefixes: Tuple[str, ...] = ("connector.",)):
@@ -106,11 +296,14 @@ def adopt_engine(pipe, device="cuda", family: Optional[str] = None, ignore_prefi
     family = family or _FAMILY_OF.get(name)
     if family is None:
         raise NotImplementedError(f"no RegionE patch set for pipeline class {name}")
-    sd = pipe.transformer.state_dict()
-    shapes = {map_key(k, family): tuple(v.shape) for k, v in sd.items()}
+    sd, names, lora = _lora_plan(pipe, family, ignore_prefixes)       # PEFT wrapper levels stripped; what is not plain LoRA is refused by name
+    shapes = {map_key(s, family): tuple(sd[k].shape) for k, s in names.items()}
     cfg = infer_config(shapes, _axes_dim(pipe.transformer))
     want = flux_param_shapes(cfg)
-    extra = [k for k in shapes if k not in want and not k.startswith(tuple(ignore_prefixes))]
+    for k in lora:
+        if k not in want or len(want[k]) != 2:
+            _lora_decline(f"LoRA on {k[:-len('.weight')]}, not a Linear the trunk layout knows")
+    extra =[k for k in shapes if k not in want and not k.startswith(tuple(ignore_prefixes))]
     missing = [k for k in want if k not in shapes]
     wrong = [k for k in want if k in shapes and tuple(shapes[k]) != tuple(want[k])]
     if extra or missing or wrong:
@@ -130,7 +323,9 @@ def adopt_engine(pipe, device="cuda", family: Optional[str] = None, ignore_prefi
             raise ValueError("Qwen-Image trunk expected: double-stream blocks only, timestep-only conditioning, txt_norm")
         tr = HQ.QwenImageTransformer2DModel(cfg, device)
         engine_cls = HQ.QwenImageEditPlusPipeline if "Plus" in name else HQ.QwenImageEditPipeline
-    tr.load_state_dict_stream((k, v) for k, v in _stream(sd, family, device) if k in want)
+    fp = _lora_fingerprint(lora, 1.0)
+    tr.load_state_dict_stream((k, v) for k, v in _stream(sd, names, family, device, lora) if k in want)
+    tr._lora = {"family": family, "fp": fp}          # the adapter state the weights were built from: lora_sync re-merges when it changes
     sched_cfg = dict(getattr(pipe.scheduler, "config", {}) or {}) if getattr(pipe, "scheduler", None) is not None else {}
     # every key travels: the engine's scheduler implements shift_terminal / time_shift_type / invert_sigmas and REFUSES
     # what it does not implement (karras / exponential / beta sigmas, stochastic sampling, unknown keys)
@@ -187,6 +382,19 @@ def _refuse_unused(fn_name: str, unused: dict):
         known = k in _IGNORABLE_DEFAULTS
         raise (NotImplementedError if known else TypeError)(
             f"{fn_name}: argument {k}={v!r} is {'not implemented by' if known else 'unknown to'} the hosted HIP loop")
+
+
+def _lora_call(host, eng, unused: dict, key: str) -> dict:
+    """The start of every hosted call: `{key: {"scale": s}}` (the stock pipelines' call-time LoRA scale) multiplies every term's scale
+    for THIS call - honoured by a re-merge, and the weights are restored by the next call that differs; then the engine's weights are
+    brought to the host's current adapter state (lora_sync: a no-op while the fingerprint is unchanged).  Any other content of `key`
+    stays in `unused` and is refused as before."""
+    kw, scale = unused.get(key), 1.0
+    if isinstance(kw, dict) and set(kw) == {"scale"} and isinstance(kw["scale"], (int, float)) and not isinstance(kw["scale"], bool):
+        scale = float(kw["scale"])
+        unused = {k: v for k, v in unused.items() if k != key}
+    lora_sync(host, eng, scale)
+    return unused
 
 
 def _loop_extras(kw: dict, sigmas, callback_on_step_end, callback_on_step_end_tensor_inputs):
@@ -552,6 +760,7 @@ def _hosted_flux(host, eng, image=None, prompt=None, prompt_2=None, negative_pro
                  preferred_resolutions=None, trace=None, sigmas=None, callback_on_step_end=None,
                  callback_on_step_end_tensor_inputs=("latents",), **unused):
     """FluxKontextPipeline.__call__ around the engine loop (RegionE/FluxKontext/inplace.py:112-240, :396-410)."""
+    unused = _lora_call(host, eng, unused, "joint_attention_kwargs")
     _refuse_unused("FluxKontextPipeline.__call__", unused)
     dev = eng.transformer.device
     clk = _Clock(dev)
@@ -783,6 +992,7 @@ def _hosted_step1x(host, eng, image=None, prompt=None, negative_prompt=None, tru
     accepted when they switch that loop OFF (the reference driver's own call, src/Step1X-Edit-v1p2/main.py:42-43,:69-77),
     True raises NotImplementedError; left unspecified the hosted call runs ONE attempt without reflection (the reference's
     signature default is reflection on: stated deviation)."""
+    unused = _lora_call(host, eng, unused, "joint_attention_kwargs")
     v1p2 = _host_name(host).endswith("V1P2")
     think = dict(enable_thinking_mode=enable_thinking_mode, enable_reflection_mode=enable_reflection_mode, max_try_cnt=max_try_cnt)
     if v1p2:
@@ -894,6 +1104,7 @@ def _hosted_qwen(host, eng, image=None, prompt=None, negative_prompt=None, true_
     """QwenImageEditPipeline / QwenImageEditPlusPipeline `__call__` around the engine loop (QwenImageEdit/inplace.py:180-330,
     :434-455; QwenImageEditPlus/inplace.py:189-300: a LIST of condition images, each resized twice - 384^2 area for the VLM,
     1024^2 area for the VAE - the last one fixing the output size)."""
+    unused = _lora_call(host, eng, unused, "attention_kwargs")
     _refuse_unused(_host_name(host) + ".__call__", unused)
     plus = "Plus" in _host_name(host)
     dev = eng.transformer.device
@@ -1007,6 +1218,8 @@ def adopt(pipe, device="cuda"):
 def attach(pipe, device="cuda"):
     """Adopt the host pipeline's transformer once and keep the engine ON the host object (`pipe._regione_engine`)."""
     eng = pipe.__dict__.get("_regione_engine") if hasattr(pipe, "__dict__") else None
+    if eng is not None:
+        lora_sync(pipe, eng)                                  # adapters loaded, switched or removed since the adoption
     if eng is None:
         eng = adopt_engine(pipe, device)
         pipe._regione_engine = eng

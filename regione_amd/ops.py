@@ -481,6 +481,31 @@ def gate_resid_rows(p: torch.Tensor, gate: torch.Tensor, resid: torch.Tensor, ou
     return out
 
 
+LORA_MAX_TERMS, LORA_MAX_RANK = 8, 1024          # RGN_LORA_MAX_TERMS / RGN_LORA_MAX_RANK
+
+
+def lora_merge(dst: torch.Tensor, W: torch.Tensor, terms) -> torch.Tensor:
+    """dst = bf16(W + sum_t scale_t * B_t A_t) (rgn_lora_merge_bf16: fp32 fma in term order, r ascending, ONE rounding to bf16).
+    dst, W [N, K] bf16 with unit column stride (row ranges of packed tensors are fine; `dst is W` is the in-place form); `terms` a
+    sequence of (A [r, K], B [N, r], scale) with A, B contiguous fp32 on W's device."""
+    _bf16_rows("lora_merge", dst=dst, W=W)
+    if dst.dim() != 2 or dst.shape != W.shape:
+        raise _lib.RegionEHipError(f"lora_merge: dst {tuple(dst.shape)} and W {tuple(W.shape)} must be the same [N, K]")
+    N, K = W.shape
+    terms = list(terms)
+    arr = (_lib.LoraTerm * max(len(terms), 1))()
+    for i, (A, B, scale) in enumerate(terms):
+        for name, t, shape in (("A", A, (A.shape[0], K)), ("B", B, (N, A.shape[0]))):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != W.device or tuple(t.shape) != shape:
+                raise _lib.RegionEHipError(f"lora_merge: term {i} {name} must be contiguous fp32 {shape} on {W.device} "
+                                           f"(got {t.dtype} {tuple(t.shape)} on {t.device})")
+        arr[i] = _lib.LoraTerm(_p(A), _p(B), A.shape[0], float(scale))
+    rc = _lib.lib().rgn_lora_merge_bf16(_p(dst), dst.stride(0) if N > 1 else max(dst.stride(0), K), _p(W),
+                                        W.stride(0) if N > 1 else max(W.stride(0), K), N, K, arr, len(terms), _stream())
+    _lib.check(rc, "rgn_lora_merge_bf16")
+    return dst
+
+
 def sel_rows(edited_ids: torch.Tensor, T: int) -> torch.Tensor:
     """int64 [T + K]: [0..T) then T + edited_ids - the cache rows of a region step (inplace.py:732-733)."""
     idv = edited_ids.reshape(-1)
