@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 117
+#define RGN_ABI_VERSION 118
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -58,8 +58,8 @@ int rgn_plan_override_get(const char* key, int* value);
  * 128 x 128 geometry (0 = not cut; only ever set with bit 10 clear). */
 int rgn_gemm_last_plan(void);
 /* The plan the planner WOULD choose for a group of `nprob` (<= 4) problems with M = Ms[i] rows, N output channels, depth K, `distinct_w`
- * different weight matrices (problems of one stream share W), bf16 (w8 = 0) or fp8 (w8 = 1) weights and a workspace of
- * `workspace_bytes` (0 = none): same bits as rgn_gemm_last_plan.  Pure host arithmetic on the launch cost model - no launch, no GPU
+ * different weight matrices (problems of one stream share W), bf16 (w8 = 0) or fp8 (w8 = 1) weights, or fp8 weights AND fp8 activations
+ * (w8 = 2: `ascale`, whole-K tiles only - never K pieces) and a workspace of `workspace_bytes` (0 = none): same bits as rgn_gemm_last_plan.  Pure host arithmetic on the launch cost model - no launch, no GPU
  * (CPU tests pin the planner's decisions for the region-step shapes with it); negative RGN_E_* on a bad argument. */
 int rgn_gemm_plan_query(const int* Ms, int nprob, int N, int K, int distinct_w, int w8, size_t workspace_bytes);
 
@@ -189,6 +189,14 @@ int rgn_cfg_combine(const void* pos, const void* neg, void* out, int dtype, floa
  * total the call first widens W8 to bf16 (exact) into the TAIL of the workspace (N x K x 2 bytes per distinct weight matrix, >= 64 MiB
  * left for the split remainders) and runs the bf16 K loop on it - same result bit for bit, weights stay fp8 in HBM.
  *
+ * fp8 activations (opt-in; no reference counterpart): `ascale` != NULL - then for every problem of the call - says A is stored as OCP
+ * e4m3fn bytes ([M, K], lda in BYTES, a multiple of 16) with one fp32 scale per ROW of A (`ascale[M]`, what rgn_quantize_rows_a8 /
+ * rgn_ln_modulate_a8 write): C = epilogue((A8 @ W8^T) * ascale[m] * wscale[n] + bias), the two multiplications in fp32 in that order.
+ * Both operands go to the matrix unit as bytes: one v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3 x e4m3, unit block scales) per 16 x 16 tile
+ * and K tile of 128, twice the bf16 rate per clock.  Needs `wscale` (fp8 weights), K % 128 == 0 and RGN_EPI_BIAS, RGN_EPI_GELU or
+ * RGN_EPI_QKV; RGN_EPI_GATE_RESID, `out_rows` and a call that mixes A formats return RGN_E_UNSUPPORTED before anything is written.
+ * Such a call runs whole-K tiles only (256 x 256 tiles plus the quarter-tile remainder, or 128 x 128 tiles): no K pieces, no workspace use.
+ *
  * `workspace` (optional, fp32 scratch, rgn_gemm_workspace_bytes()) enables the round-aware schedule: output tiles that do not fill a
  * whole round of the chip's workgroup slots are cut along K, spread over all CUs and finished by a reduce pass (8 workgroups per
  * tile, epilogue in registers; bit-identical to a reduce by the tile's own workgroup).  NULL = plain single launch.
@@ -229,7 +237,7 @@ typedef struct rgn_qkv_epilogue {
                                   (fused_kernels.py:80); 0: one rounding, like F.linear on store / plain steps */
 } rgn_qkv_epilogue;
 typedef struct rgn_gemm_problem {
-    const void* A;             /* [M, K] bf16, row stride lda */
+    const void* A;             /* [M, K] bf16, row stride lda (elements); with `ascale`: e4m3fn bytes, lda in bytes */
     const void* W;             /* [N, K], row stride ldw */
     const float* wscale;       /* per-output-channel fp32 scale: W is OCP e4m3fn bytes; NULL: W is bf16 */
     const void* bias;          /* [N] bf16 or NULL */
@@ -240,6 +248,7 @@ typedef struct rgn_gemm_problem {
     const int64_t* out_rows;   /* row scatter, NULL = identity */
     int lda, ldc, M;
     int ldw;                   /* 0 = W is dense: K elements (bf16) / K bytes (fp8) */
+    const float* ascale;       /* per-row fp32 scale of A: A is OCP e4m3fn bytes (needs wscale); NULL: A is bf16 */
 } rgn_gemm_problem;
 int rgn_gemm_group(const rgn_gemm_problem* probs, int nprob, int N, int K, int epilogue, int gelu_from_col, void* workspace,
                    size_t workspace_bytes, void* stream);
@@ -286,6 +295,20 @@ int rgn_ln_modulate(const void* x, int ldx, void* out, int ldo, int M, int d, fl
  * (reference: the B = 2 forward, Step1XEdit/inplace.py:381-399, where `temb` has one row per branch). */
 int rgn_ln_modulate_segs(const void* x, int ldx, void* out, int ldo, int M, int d, float eps, int nseg,
                          const int* seg_end_host, const void* const* shift_host, const void* const* scale_host, void* stream);
+
+/* fp8 activations for rgn_gemm_group's `ascale` (opt-in; no reference counterpart).  bf16 rows x [M, K] (row stride ldx elements) become
+ * OCP e4m3fn bytes q [M, K] (row stride ldq BYTES, a multiple of 8; q 8-byte aligned) plus one fp32 scale per row, the arithmetic of the
+ * per-channel weight quantiser restated per row:  scale[m] = max(amax_k |x[m,k]|, 1e-12) / 448,  q[m,k] = e4m3fn_rne(f32(x[m,k]) / scale[m])
+ * - IEEE fp32 divisions, round to nearest even: bit-identical to the torch expression on the CPU.  One wave per row, the row stays in
+ * registers between the amax pass and the convert pass; K % 8 == 0, K <= 16384; no atomics. */
+int rgn_quantize_rows_a8(const void* x, int ldx, void* q, int ldq, float* scale, int M, int K, void* stream);
+/* rgn_ln_modulate / rgn_ln_modulate_segs whose output leaves as fp8 bytes + row scales: each row forms exactly the bf16 values the bf16
+ * entry would store and quantises them as rgn_quantize_rows_a8 does, in one pass over HBM - bit-identical to
+ * rgn_quantize_rows_a8(rgn_ln_modulate(x)).  Row bands cut these launches like the bf16 ones. */
+int rgn_ln_modulate_a8(const void* x, int ldx, void* q, int ldq, float* scale, int M, int d, float eps, int split_row,
+                       const void* shift0, const void* scale0, const void* shift1, const void* scale1, void* stream);
+int rgn_ln_modulate_segs_a8(const void* x, int ldx, void* q, int ldq, float* scale, int M, int d, float eps, int nseg,
+                            const int* seg_end_host, const void* const* shift_host, const void* const* scale_host, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Region-Instruction KV-cache write (RegoionEFluxAttnProcessor2_0, inplace.py:717-763,792-794):

@@ -38,7 +38,7 @@ class GemmProblem(C.Structure):
     """struct rgn_gemm_problem (include/regione_hip.h): one problem of rgn_gemm_group, the one GEMM entry point."""
     _fields_ = [("A", _c_void_p), ("W", _c_void_p), ("wscale", _c_void_p), ("bias", _c_void_p), ("C", _c_void_p),
                 ("gate", _c_void_p), ("resid", _c_void_p), ("qkv", _qkv_p), ("out_rows", _c_void_p), ("lda", _c_int), ("ldc", _c_int),
-                ("M", _c_int), ("ldw", _c_int)]
+                ("M", _c_int), ("ldw", _c_int), ("ascale", _c_void_p)]
 
 
 _prob_p = C.POINTER(GemmProblem)
@@ -110,6 +110,12 @@ SIGNATURES = {
                         _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "rgn_ln_modulate_segs": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_int, C.POINTER(_c_int),
                              C.POINTER(_c_void_p), C.POINTER(_c_void_p), _c_void_p],
+    # fp8 activations: row quantiser and the LN-modulate forms that write fp8 rows + row scales (csrc/norm.hip)
+    "rgn_quantize_rows_a8": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p],
+    "rgn_ln_modulate_a8": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_float, _c_int, _c_void_p,
+                           _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "rgn_ln_modulate_segs_a8": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_float, _c_int, C.POINTER(_c_int),
+                                C.POINTER(_c_void_p), C.POINTER(_c_void_p), _c_void_p],
     "rgn_qk_norm_rope_store": [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p,
                                _c_void_p, _c_void_p, _c_void_p, _c_float, _c_void_p, _c_void_p, _c_void_p,
                                _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p],

@@ -60,7 +60,7 @@ rgn_gemm_problem problem(const void* A, int lda, const rgn_block_weight& w, void
                          const void* resid = nullptr, const rgn_qkv_epilogue* e = nullptr) {
     rgn_gemm_problem p;
     p.A = A; p.W = w.W; p.wscale = w.wscale; p.bias = w.bias; p.C = C; p.gate = gate; p.resid = resid; p.qkv = e; p.out_rows = nullptr;
-    p.lda = lda; p.ldc = ldc; p.M = M; p.ldw = 0;
+    p.lda = lda; p.ldc = ldc; p.M = M; p.ldw = 0; p.ascale = nullptr;      // bf16 activations: the block entries have no fp8-activation form
     return p;
 }
 

@@ -18,6 +18,39 @@ struct LnSegs {
     const uint16_t* scale[LN_MAXSEG];
 };
 
+// fp8 activations (rgn_quantize_rows_a8, rgn_ln_modulate_a8): a bf16 row becomes OCP e4m3fn bytes plus ONE fp32 scale, the arithmetic of
+// ops.quantize_w8 per row: s = max(amax|y|, 1e-12) / 448, q = e4m3fn_rne(y / s) - IEEE fp32 divisions (hipcc's default), the hardware
+// convert (v_cvt_pk_fp8_f32: round to nearest even, subnormals kept; |y / s| <= 448 * (1 + 2^-23) never reaches the saturation point).
+struct A8Out {
+    uint8_t* q;          // [M, ldq] bytes
+    float* scale;        // [M]
+    int ldq;
+};
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float a8_row_scale(float amax) { return fmaxf(amax, 1e-12f) / 448.0f; }
+// 8 consecutive bf16 values (packed pairs) -> 8 fp8 bytes
+__device__ __forceinline__ uint2 a8_quant8(const uint32_t (&w)[4], float s) {
+    float y[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { y[2 * k] = __uint_as_float(w[k] << 16) / s; y[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u) / s; }
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
+    return make_uint2((uint32_t)lo, (uint32_t)hi);
+}
+__device__ __forceinline__ float a8_amax8(const uint32_t (&w)[4]) {
+    float a = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a = fmaxf(a, fmaxf(fabsf(__uint_as_float(w[k] << 16)), fabsf(__uint_as_float(w[k] & 0xffff0000u))));
+    return a;
+}
+
 __global__ __launch_bounds__(256) void ln_modulate_kernel(const uint16_t* __restrict__ x, int ldx,
                                                           uint16_t* __restrict__ out, int ldo, int d, float eps,
                                                           const LnSegs segs) {
@@ -78,6 +111,85 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const uint16_t* __rest
             }
             *(uint4*)(orow + vi * 8) = *(const uint4*)o;
         }
+    }
+}
+
+// rgn_ln_modulate_a8: ln_modulate_kernel's arithmetic restated statement for statement (same sums in the same order: keep the two in
+// step - tests/test_gpu_quantize_rows.py pins the identity); the bf16 row it would store stays in registers, is quantised as above and
+// leaves as fp8 bytes + its scale - bit-identical to rgn_quantize_rows_a8 of the bf16 output, in one pass over HBM.
+__global__ __launch_bounds__(256) void ln_modulate_a8_kernel(const uint16_t* __restrict__ x, int ldx, int d, float eps, const LnSegs segs,
+                                                             const A8Out a8) {
+    __shared__ float red[8];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint16_t* xr = x + (size_t)row * ldx;
+    int si = 0;
+#pragma unroll
+    for (int i = 0; i < LN_MAXSEG - 1; ++i) si += (row >= segs.end[i]) ? 1 : 0;
+    const uint16_t* sh = segs.shift[si];
+    const uint16_t* sc = segs.scale[si];
+    const int nvec = d >> 3;
+    constexpr int MAXV = 4;                       // d <= 8192
+    float v[MAXV][8];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int vi = tid + i * 256;
+        if (vi < nvec) {
+            uint16_t t[8];
+            *(uint4*)t = *(const uint4*)(xr + vi * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { v[i][e] = bf2f(t[e]); s += v[i][e]; }
+        }
+    }
+    s = wave_sum(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)d;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int vi = tid + i * 256;
+        if (vi < nvec) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { const float c = v[i][e] - mean; q += c * c; }
+        }
+    }
+    q = wave_sum(q);
+    if (lane == 0) red[4 + wave] = q;
+    __syncthreads();
+    const float var = (red[4] + red[5] + red[6] + red[7]) / (float)d;
+    const float rstd = 1.0f / sqrtf(var + eps);
+    uint32_t ow[MAXV][4];
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int vi = tid + i * 256;
+        if (vi < nvec) {
+            uint16_t a[8], b[8], o[8];
+            *(uint4*)a = *(const uint4*)(sc + vi * 8);
+            *(uint4*)b = *(const uint4*)(sh + vi * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float y0 = rbf((v[i][e] - mean) * rstd);          // LayerNorm output (bf16)
+                const float s1 = rbf(1.0f + bf2f(a[e]));                // (1 + scale) (bf16)
+                const float y1 = rbf(y0 * s1);
+                o[e] = f2bf(y1 + bf2f(b[e]));
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ow[i][k] = (uint32_t)o[2 * k] | ((uint32_t)o[2 * k + 1] << 16);
+            amax = fmaxf(amax, a8_amax8(ow[i]));
+        }
+    }
+    amax = wave_max(amax);
+    if (lane == 0) red[wave] = amax;          // red[0..3] were last read before the second barrier
+    __syncthreads();
+    const float sq = a8_row_scale(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
+    if (tid == 0) a8.scale[row] = sq;
+    uint8_t* qrow = a8.q + (size_t)row * a8.ldq;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int vi = tid + i * 256;
+        if (vi < nvec) *(uint2*)(qrow + vi * 8) = a8_quant8(ow[i], sq);
     }
 }
 
@@ -148,7 +260,128 @@ __global__ __launch_bounds__(256) void ln_modulate_wave_kernel(const uint16_t* _
     }
 }
 
-static int launch_ln_rows(const uint16_t* x, int ldx, uint16_t* out, int ldo, int M, int d, float eps, const LnSegs& segs, hipStream_t st) {
+// The wave-per-row kernel with fp8 output (ln_modulate_wave_kernel restated statement for statement, then the quantiser)
+template <int NV>
+__global__ __launch_bounds__(256) void ln_modulate_wave_a8_kernel(const uint16_t* __restrict__ x, int ldx, int M, float eps, const LnSegs segs,
+                                                                  const A8Out a8) {
+    constexpr int d = NV * 512;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    int si = 0;
+#pragma unroll
+    for (int i = 0; i < LN_MAXSEG - 1; ++i) si += (row >= segs.end[i]) ? 1 : 0;
+    const uint16_t* sh = segs.shift[si];
+    const uint16_t* sc = segs.scale[si];
+    const uint16_t* xr = x + (size_t)row * ldx + lane * 8;
+    uint4 xv[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) xv[i] = *(const uint4*)(xr + i * 512);
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const uint32_t w[4] = {xv[i].x, xv[i].y, xv[i].z, xv[i].w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { s += __uint_as_float(w[k] << 16); s += __uint_as_float(w[k] & 0xffff0000u); }
+    }
+    const float mean = wave_sum(s) / (float)d;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const uint32_t w[4] = {xv[i].x, xv[i].y, xv[i].z, xv[i].w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float c0 = __uint_as_float(w[k] << 16) - mean, c1 = __uint_as_float(w[k] & 0xffff0000u) - mean;
+            q += c0 * c0;
+            q += c1 * c1;
+        }
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + eps);
+    uint32_t ow[NV][4];
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const uint4 a4 = *(const uint4*)(sc + lane * 8 + i * 512), b4 = *(const uint4*)(sh + lane * 8 + i * 512);
+        const uint32_t w[4] = {xv[i].x, xv[i].y, xv[i].z, xv[i].w}, a[4] = {a4.x, a4.y, a4.z, a4.w}, b[4] = {b4.x, b4.y, b4.z, b4.w};
+        uint32_t o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float y[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float xe = __uint_as_float(h ? (w[k] & 0xffff0000u) : (w[k] << 16));
+                const float ae = __uint_as_float(h ? (a[k] & 0xffff0000u) : (a[k] << 16));
+                const float be = __uint_as_float(h ? (b[k] & 0xffff0000u) : (b[k] << 16));
+                const float y0 = rbf((xe - mean) * rstd);          // LayerNorm output (bf16)
+                const float s1 = rbf(1.0f + ae);                   // (1 + scale) (bf16)
+                y[h] = rbf(y0 * s1) + be;
+            }
+            o[k] = f2bf_pk(y[0], y[1]);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ow[i][k] = o[k];
+        amax = fmaxf(amax, a8_amax8(ow[i]));
+    }
+    const float sq = a8_row_scale(wave_max(amax));
+    if (lane == 0) a8.scale[row] = sq;
+    uint8_t* qrow = a8.q + (size_t)row * a8.ldq + lane * 8;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) *(uint2*)(qrow + i * 512) = a8_quant8(ow[i], sq);
+}
+
+
+// bf16 rows -> fp8 bytes + row scales (rgn_quantize_rows_a8): one wave per row, the row held in registers (NV 16-byte vectors per lane)
+// between the amax pass and the convert pass.
+template <int NV>
+__global__ __launch_bounds__(256) void quantize_rows_a8_kernel(const uint16_t* __restrict__ x, int ldx, int M, int K, const A8Out a8) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int nvec = K >> 3;
+    const uint16_t* xr = x + (size_t)row * ldx;
+    uint32_t w[NV][4];
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int vi = lane + i * 64;
+        uint4 t = make_uint4(0u, 0u, 0u, 0u);
+        if (vi < nvec) t = *(const uint4*)(xr + vi * 8);
+        w[i][0] = t.x; w[i][1] = t.y; w[i][2] = t.z; w[i][3] = t.w;
+        amax = fmaxf(amax, a8_amax8(w[i]));
+    }
+    const float sq = a8_row_scale(wave_max(amax));
+    if (lane == 0) a8.scale[row] = sq;
+    uint8_t* qrow = a8.q + (size_t)row * a8.ldq;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int vi = lane + i * 64;
+        if (vi < nvec) *(uint2*)(qrow + vi * 8) = a8_quant8(w[i], sq);
+    }
+}
+
+static int launch_ln_rows_a8(const uint16_t* x, int ldx, const A8Out& a8, int M, int d, float eps, const LnSegs& segs, hipStream_t st) {
+    if (d % 512 == 0) {          // the same kernel choice as the bf16 rows: the two kernels sum in different orders
+        const dim3 grid((M + 3) / 4), blk(256);
+        switch (d / 512) {
+            case 1: hipLaunchKernelGGL(ln_modulate_wave_a8_kernel<1>, grid, blk, 0, st, x, ldx, M, eps, segs, a8); return check_launch("ln_modulate_wave_a8_kernel");
+            case 2: hipLaunchKernelGGL(ln_modulate_wave_a8_kernel<2>, grid, blk, 0, st, x, ldx, M, eps, segs, a8); return check_launch("ln_modulate_wave_a8_kernel");
+            case 3: hipLaunchKernelGGL(ln_modulate_wave_a8_kernel<3>, grid, blk, 0, st, x, ldx, M, eps, segs, a8); return check_launch("ln_modulate_wave_a8_kernel");
+            case 4: hipLaunchKernelGGL(ln_modulate_wave_a8_kernel<4>, grid, blk, 0, st, x, ldx, M, eps, segs, a8); return check_launch("ln_modulate_wave_a8_kernel");
+            case 6: hipLaunchKernelGGL(ln_modulate_wave_a8_kernel<6>, grid, blk, 0, st, x, ldx, M, eps, segs, a8); return check_launch("ln_modulate_wave_a8_kernel");
+            case 8: hipLaunchKernelGGL(ln_modulate_wave_a8_kernel<8>, grid, blk, 0, st, x, ldx, M, eps, segs, a8); return check_launch("ln_modulate_wave_a8_kernel");
+            default: break;
+        }
+    }
+    hipLaunchKernelGGL(ln_modulate_a8_kernel, dim3(M), dim3(256), 0, st, x, ldx, d, eps, segs, a8);
+    return check_launch("ln_modulate_a8_kernel");
+}
+
+static int launch_ln_rows(const uint16_t* x, int ldx, uint16_t* out, int ldo, int M, int d, float eps, const LnSegs& segs, hipStream_t st,
+                          const A8Out* a8 = nullptr, int row0 = 0) {
+    if (a8 != nullptr) {          // fp8 rows: `out` is unused, the band's first row is row0 of the caller's buffers
+        const A8Out b{a8->q + (size_t)row0 * a8->ldq, a8->scale + row0, a8->ldq};
+        return launch_ln_rows_a8(x, ldx, b, M, d, eps, segs, st);
+    }
     if (d % 512 == 0) {          // the wave-per-row kernel; other widths (toy trunks, d = 256): the block-per-row kernel below
         const dim3 grid((M + 3) / 4), blk(256);
         switch (d / 512) {
@@ -167,15 +400,16 @@ static int launch_ln_rows(const uint16_t* x, int ldx, uint16_t* out, int ldo, in
 
 // Row bands (rgn_rowband_fork, region.hip): while `st` is forked the rows are cut where the GEMMs of the same chain cut theirs - the row
 // segments are the GEMM group's problems - and the rows behind the cut go to the side stream.  Per row nothing changes.
-static int launch_ln(const uint16_t* x, int ldx, uint16_t* out, int ldo, int M, int d, float eps, const LnSegs& segs, hipStream_t st) {
+static int launch_ln(const uint16_t* x, int ldx, uint16_t* out, int ldo, int M, int d, float eps, const LnSegs& segs, hipStream_t st,
+                     const A8Out* a8 = nullptr) {
     hipStream_t side = nullptr;
-    if (!rowband_active(st, &side)) return launch_ln_rows(x, ldx, out, ldo, M, d, eps, segs, st);
+    if (!rowband_active(st, &side)) return launch_ln_rows(x, ldx, out, ldo, M, d, eps, segs, st, a8);
     int Ms[LN_MAXSEG], n = 0, start[LN_MAXSEG], prev = 0, which = 0, row = 0;
     for (int i = 0; i < LN_MAXSEG; ++i) {
         const int end = segs.end[i] < M ? segs.end[i] : M;
         if (end > prev) { Ms[n] = end - prev; start[n] = prev; ++n; prev = end; }
     }
-    if (!rowband_cut(Ms, nullptr, n, &which, &row)) return launch_ln_rows(x, ldx, out, ldo, M, d, eps, segs, st);
+    if (!rowband_cut(Ms, nullptr, n, &which, &row)) return launch_ln_rows(x, ldx, out, ldo, M, d, eps, segs, st, a8);
     // band 1 = rows [c, e) of the cut segment; band 0 = everything else: rows [0, c) and, when the cut segment is not the last, [e, M)
     const int c = start[which] + row, e = start[which] + Ms[which];
     auto shifted = [&](int by) {
@@ -183,12 +417,12 @@ static int launch_ln(const uint16_t* x, int ldx, uint16_t* out, int ldo, int M, 
         for (int i = 0; i < LN_MAXSEG; ++i) t.end[i] = segs.end[i] < by ? 0 : segs.end[i] - by;
         return t;
     };
-    int rc = launch_ln_rows(x, ldx, out, ldo, c, d, eps, segs, st);
-    if (rc == 0 && e < M) rc = launch_ln_rows(x + (size_t)e * ldx, ldx, out + (size_t)e * ldo, ldo, M - e, d, eps, shifted(e), st);
+    int rc = launch_ln_rows(x, ldx, out, ldo, c, d, eps, segs, st, a8);
+    if (rc == 0 && e < M) rc = launch_ln_rows(x + (size_t)e * ldx, ldx, out + (size_t)e * ldo, ldo, M - e, d, eps, shifted(e), st, a8, e);
     if (rc) return rc;
     const LnSegs hi = shifted(c);
     rowband_count_side_launch();
-    return launch_ln_rows(x + (size_t)c * ldx, ldx, out + (size_t)c * ldo, ldo, e - c, d, eps, hi, side);
+    return launch_ln_rows(x + (size_t)c * ldx, ldx, out + (size_t)c * ldo, ldo, e - c, d, eps, hi, side, a8, c);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -337,8 +571,8 @@ int rgn_add_bf16(const void* a, const void* b, void* y, size_t n, void* stream) 
     return check_launch("add_bf16_kernel");
 }
 
-int rgn_ln_modulate(const void* x, int ldx, void* out, int ldo, int M, int d, float eps, int split_row,
-                    const void* shift0, const void* scale0, const void* shift1, const void* scale1, void* stream) {
+static int ln_modulate(const void* x, int ldx, void* out, int ldo, int M, int d, float eps, int split_row,
+                       const void* shift0, const void* scale0, const void* shift1, const void* scale1, void* stream, const A8Out* a8) {
     if (M == 0) return 0;
     if (!x || !out || M < 0 || d <= 0 || (d % 8) || d > 8192 || (ldx % 8) || (ldo % 8) || !shift1 || !scale1)
         return fail(RGN_E_BADARG, "ln_modulate: bad argument");
@@ -349,11 +583,51 @@ int rgn_ln_modulate(const void* x, int ldx, void* out, int ldo, int M, int d, fl
         segs.shift[i] = (const uint16_t*)(i == 0 && split_row > 0 ? shift0 : shift1);
         segs.scale[i] = (const uint16_t*)(i == 0 && split_row > 0 ? scale0 : scale1);
     }
-    return launch_ln((const uint16_t*)x, ldx, (uint16_t*)out, ldo, M, d, eps, segs, (hipStream_t)stream);
+    return launch_ln((const uint16_t*)x, ldx, (uint16_t*)out, ldo, M, d, eps, segs, (hipStream_t)stream, a8);
 }
 
-int rgn_ln_modulate_segs(const void* x, int ldx, void* out, int ldo, int M, int d, float eps, int nseg, const int* seg_end_host,
-                         const void* const* shift_host, const void* const* scale_host, void* stream) {
+int rgn_ln_modulate(const void* x, int ldx, void* out, int ldo, int M, int d, float eps, int split_row,
+                    const void* shift0, const void* scale0, const void* shift1, const void* scale1, void* stream) {
+    return ln_modulate(x, ldx, out, ldo, M, d, eps, split_row, shift0, scale0, shift1, scale1, stream, nullptr);
+}
+
+// fp8 rows + row scales: `q` rows of ldq BYTES (a multiple of 8), 8-byte aligned; `scale` [M] fp32
+static int a8_out(void* q, int ldq, float* scale, int d, A8Out* o) {
+    if (!q || !scale || ldq < d || (ldq % 8) || ((uintptr_t)q & 7)) return fail(RGN_E_BADARG, "a8: q rows must be 8-byte aligned with ldq >= the row width, scale non-null");
+    o->q = (uint8_t*)q; o->scale = scale; o->ldq = ldq;
+    return 0;
+}
+
+int rgn_ln_modulate_a8(const void* x, int ldx, void* q, int ldq, float* scale, int M, int d, float eps, int split_row,
+                       const void* shift0, const void* scale0, const void* shift1, const void* scale1, void* stream) {
+    if (M == 0) return 0;
+    A8Out o;
+    if (int rc = a8_out(q, ldq, scale, d, &o)) return rc;
+    return ln_modulate(x, ldx, q, 8, M, d, eps, split_row, shift0, scale0, shift1, scale1, stream, &o);
+}
+
+int rgn_quantize_rows_a8(const void* x, int ldx, void* q, int ldq, float* scale, int M, int K, void* stream) {
+    if (M == 0) return 0;
+    if (!x || M < 0 || K <= 0 || (K % 8) || K > 16384 || (ldx % 8) || ldx < K || ((uintptr_t)x & 15))
+        return fail(RGN_E_BADARG, "quantize_rows_a8: bad argument (K a multiple of 8 up to 16384, x rows 16-byte aligned)");
+    A8Out o;
+    if (int rc = a8_out(q, ldq, scale, K, &o)) return rc;
+    const dim3 grid((M + 3) / 4), blk(256);
+    const uint16_t* xx = (const uint16_t*)x;
+    hipStream_t st = (hipStream_t)stream;
+    const int nv = (K + 511) / 512;
+    if (nv <= 1) hipLaunchKernelGGL(quantize_rows_a8_kernel<1>, grid, blk, 0, st, xx, ldx, M, K, o);
+    else if (nv <= 2) hipLaunchKernelGGL(quantize_rows_a8_kernel<2>, grid, blk, 0, st, xx, ldx, M, K, o);
+    else if (nv <= 4) hipLaunchKernelGGL(quantize_rows_a8_kernel<4>, grid, blk, 0, st, xx, ldx, M, K, o);
+    else if (nv <= 6) hipLaunchKernelGGL(quantize_rows_a8_kernel<6>, grid, blk, 0, st, xx, ldx, M, K, o);
+    else if (nv <= 8) hipLaunchKernelGGL(quantize_rows_a8_kernel<8>, grid, blk, 0, st, xx, ldx, M, K, o);
+    else if (nv <= 16) hipLaunchKernelGGL(quantize_rows_a8_kernel<16>, grid, blk, 0, st, xx, ldx, M, K, o);
+    else hipLaunchKernelGGL(quantize_rows_a8_kernel<32>, grid, blk, 0, st, xx, ldx, M, K, o);
+    return check_launch("quantize_rows_a8_kernel");
+}
+
+static int ln_modulate_segs(const void* x, int ldx, void* out, int ldo, int M, int d, float eps, int nseg, const int* seg_end_host,
+                            const void* const* shift_host, const void* const* scale_host, void* stream, const A8Out* a8) {
     if (M == 0) return 0;
     if (!x || !out || M < 0 || d <= 0 || (d % 8) || d > 8192 || (ldx % 8) || (ldo % 8) || nseg < 1 || nseg > LN_MAXSEG ||
         !seg_end_host || !shift_host || !scale_host)
@@ -369,7 +643,20 @@ int rgn_ln_modulate_segs(const void* x, int ldx, void* out, int ldo, int M, int 
         prev = seg_end_host[j];
     }
     if (seg_end_host[nseg - 1] != M) return fail(RGN_E_BADARG, "ln_modulate_segs: the last segment must end at M");
-    return launch_ln((const uint16_t*)x, ldx, (uint16_t*)out, ldo, M, d, eps, segs, (hipStream_t)stream);
+    return launch_ln((const uint16_t*)x, ldx, (uint16_t*)out, ldo, M, d, eps, segs, (hipStream_t)stream, a8);
+}
+
+int rgn_ln_modulate_segs(const void* x, int ldx, void* out, int ldo, int M, int d, float eps, int nseg, const int* seg_end_host,
+                         const void* const* shift_host, const void* const* scale_host, void* stream) {
+    return ln_modulate_segs(x, ldx, out, ldo, M, d, eps, nseg, seg_end_host, shift_host, scale_host, stream, nullptr);
+}
+
+int rgn_ln_modulate_segs_a8(const void* x, int ldx, void* q, int ldq, float* scale, int M, int d, float eps, int nseg, const int* seg_end_host,
+                            const void* const* shift_host, const void* const* scale_host, void* stream) {
+    if (M == 0) return 0;
+    A8Out o;
+    if (int rc = a8_out(q, ldq, scale, d, &o)) return rc;
+    return ln_modulate_segs(x, ldx, q, 8, M, d, eps, nseg, seg_end_host, shift_host, scale_host, stream, &o);
 }
 
 int rgn_rms_norm_rows(const void* x, int ldx, const void* w, void* out, int ldo, int M, int d, float eps, void* stream) {

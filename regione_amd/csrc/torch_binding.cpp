@@ -263,6 +263,7 @@ rgn_gemm_problem problem(const Tensor& x, const Tensor& w, const OptTensor& w_sc
     p.A = ptr(x); p.W = ptr(w); p.wscale = (const float*)ptr(w_scale); p.bias = ptr(bias);
     p.C = out.data_ptr(); p.gate = nullptr; p.resid = nullptr; p.qkv = e; p.out_rows = nullptr;
     p.lda = (int)x.stride(0); p.ldc = (int)out.stride(0); p.M = (int)x.size(0); p.ldw = (int)w.stride(0);
+    p.ascale = nullptr;      // check_act: bf16 activations
     return p;
 }
 
@@ -362,6 +363,23 @@ Tensor masked_mean_rows(const Tensor& x, int64_t n_valid, double scale) {
     check_rc(rgn_masked_mean_rows(ptr(x), (int)x.stride(0), (int)x.size(0), (int)x.size(1), (int)n_valid, (float)scale, out.data_ptr(),
                                   stream_of(x)), "rgn_masked_mean_rows");
     return out;
+}
+
+// ---- fp8 activations: the row quantiser (csrc/norm.hip) ------------------------------------------------------------------------
+// x bf16 [M, K] -> (q fp8 e4m3fn [M, K], scale fp32 [M]): scale = max(amax|x|, 1e-12) / 448 per row, q = e4m3fn(x / scale)
+std::tuple<Tensor, Tensor> quantize_rows_a8(const Tensor& x) {
+    RGN_DEVICE_GUARD(x);
+    bf16_rows("quantize_rows_a8", {&x});
+    TORCH_CHECK(x.dim() == 2, "quantize_rows_a8: x [M, K]");
+    const int64_t M = x.size(0), K = x.size(1);
+    TORCH_CHECK(K >= 8 && K % 8 == 0 && K <= 16384, "quantize_rows_a8: K = ", K, " must be a multiple of 8 in [8, 16384]");
+    TORCH_CHECK(M == 0 || (x.stride(0) >= K && x.stride(0) % 8 == 0 && ((uintptr_t)x.data_ptr() & 15) == 0),
+                "quantize_rows_a8: rows of x must be 16-byte aligned (row stride ", x.stride(0), " elements)");
+    Tensor q = at::empty({M, K}, x.options().dtype(at::kFloat8_e4m3fn));
+    Tensor scale = at::empty({M}, x.options().dtype(at::kFloat));
+    check_rc(rgn_quantize_rows_a8(ptr(x), (int)x.stride(0), q.data_ptr(), (int)K, (float*)scale.data_ptr(), (int)M, (int)K, stream_of(x)),
+             "rgn_quantize_rows_a8");
+    return std::make_tuple(q, scale);
 }
 
 void head_rms_norm_(Tensor qkv, const Tensor& wq, const Tensor& wk, int64_t heads, double eps) {
@@ -540,6 +558,7 @@ TORCH_LIBRARY(regione_mi, m) {
           "float score_bound=0.0) -> ()");
     m.def("workspace(Tensor like, int kind) -> Tensor");
     // the connector's row kernels (regione_amd/torch_ops.py: ROW_SCHEMAS)
+    m.def("quantize_rows_a8(Tensor x) -> (Tensor, Tensor)");
     m.def("masked_mean_rows(Tensor x, int n_valid, float scale=1.0) -> Tensor");
     m.def("head_rms_norm_(Tensor(a!) qkv, Tensor wq, Tensor wk, int heads, float eps=1e-6) -> ()");
     m.def("gate_resid_rows_(Tensor p, Tensor gate, Tensor resid, Tensor(a!) out) -> ()");
@@ -565,6 +584,7 @@ TORCH_LIBRARY_IMPL(regione_mi, CUDA, m) {
     m.impl("kv_partial_update_group_", &kv_partial_update_group_);
     m.impl("region_attention", &region_attention);
     m.impl("workspace", &workspace_op);
+    m.impl("quantize_rows_a8", &quantize_rows_a8);
     m.impl("masked_mean_rows", &masked_mean_rows);
     m.impl("head_rms_norm_", &head_rms_norm_);
     m.impl("gate_resid_rows_", &gate_resid_rows_);

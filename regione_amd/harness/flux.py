@@ -267,6 +267,13 @@ class Workspace:
         self.cfg, self.device = cfg, device
         self.rows = 0
         self.skv_pad = 0
+        self.a8 = False                 # fp8 activations (quantize_fp8_(activations=True)): the block bodies' normed rows live in `nrm8`
+
+    def act(self, lo: int, hi: int):
+        """Rows [lo, hi) of the block bodies' LN-modulate output, in the format the trunk's projections read: the bf16 `nrm` rows, or -
+        fp8 activations - the e4m3fn rows of `nrm8` with their row scales (ops.arows).  ops.ln_modulate* writes it, the Q/K/V(+MLP)
+        and first feed-forward GEMMs read it; norm_out -> proj_out keeps the bf16 `nrm`."""
+        return ops.arows(self.nrm8, lo, hi) if self.a8 else self.nrm[lo:hi]
 
     def ensure(self, rows: int, skv: int, branches: int = 1):
         """`rows` activation rows in total; one plain-phase K / V^T scratch slab of `skv` rows per CFG branch of a batched
@@ -278,6 +285,9 @@ class Workspace:
             self.nrm = torch.empty(rows, d, **kw)
             self.wide = torch.empty(rows, 3 * d + ff, **kw)        # [k | v | q | mlp]
             self.rows = rows
+        if self.a8 and getattr(self, "nrm8", torch.empty(0)).shape[0] < self.rows:
+            self.nrm8 = torch.empty(self.rows, d, dtype=ops.FP8, device=self.device)
+            self.nrm8._rgn_scale = torch.empty(self.rows, dtype=torch.float32, device=self.device)
         pad = ops.padded(skv)
         if pad > self.skv_pad or branches > len(getattr(self, "k_scratch_b", ())):
             kw = dict(dtype=torch.bfloat16, device=self.device)
@@ -298,6 +308,10 @@ class WsView:
         self.cfg, self.device = ws.cfg, ws.device
         self.x, self.nrm, self.wide = ws.x[base:], ws.nrm[base:], ws.wide[base:]
         self.k_scratch, self.vt_scratch = ws.k_scratch_b[bi], ws.vt_scratch_b[bi]
+        self.a8 = ws.a8
+
+    def act(self, lo: int, hi: int):
+        return self.ws.act(self.base + lo, self.base + hi)
 
 
 class Modulation:
@@ -440,6 +454,8 @@ class FluxAttnProcessor:
         k_slab, vt_slab, kv_rows, skv, rope_k = self.kv_target(attn, ctx)
         rope_k = rope_k if rope_k is not None else image_rotary_emb
         fuse = FUSE_QKV and H % 2 == 0             # the fused epilogue works on 256-column (two-head) blocks
+        # fp8 activations: the fused projections go to rgn_gemm_group through the ctypes wrappers (the registered ops take bf16 rows)
+        PR = TO.Direct if ws.a8 else TO.R
         # partial K/V update (region step): the rows the reference sends through `_partially_linear` round fp32 -> fp16 ->
         # bf16 (fused_kernels.py:80, quirk A-3): every row of a single-stream block, the image rows of a double-stream one
         partial = kv_rows is not None
@@ -457,9 +473,9 @@ class FluxAttnProcessor:
                 # streams, but queries, attention and the output projection only for the image rows the caller reads; the
                 # text stream's output of this block feeds nothing
                 lo, hi = T, T + n_out
-                ops.gemm_pair(ws.nrm[T:R], ops.wrows(attn.w_kvq, None, 2 * d), attn.b_kvq[:2 * d], wide[T:R, :2 * d],
-                              ws.nrm[:T], ops.wrows(attn.w_add_kvq, None, 2 * d), attn.b_add_kvq[:2 * d], wide[:T, :2 * d])
-                ops.gemm(ws.nrm[lo:hi], ops.wrows(attn.w_kvq, 2 * d, None), attn.b_kvq[2 * d:], wide[lo:hi, 2 * d:3 * d])
+                ops.gemm_pair(ws.act(T, R), ops.wrows(attn.w_kvq, None, 2 * d), attn.b_kvq[:2 * d], wide[T:R, :2 * d],
+                              ws.act(0, T), ops.wrows(attn.w_add_kvq, None, 2 * d), attn.b_add_kvq[:2 * d], wide[:T, :2 * d])
+                ops.gemm(ws.act(lo, hi), ops.wrows(attn.w_kvq, 2 * d, None), attn.b_kvq[2 * d:], wide[lo:hi, 2 * d:3 * d])
                 ops.qk_norm_rope_store(wide, 0, d, 2 * d, H, attn.norm_q, attn.norm_k, image_rotary_emb, rope_k,
                                        k_slab, vt_slab, kv_rows, split_row=T, wq0=attn.norm_added_q, wk0=attn.norm_added_k)
                 q = wide[lo:hi, 2 * d:3 * d]
@@ -468,13 +484,13 @@ class FluxAttnProcessor:
                 ops.gemm(q, attn.w_out, attn.b_out, ws.x[lo:hi], epilogue=ops.EPI_GATE_RESID, gate=g_img, resid=ws.x[lo:hi])
                 return ws.x[T:R], ws.x[:T]
             if fuse:       # projections + RMSNorm + RoPE + K / V^T cache placement of both streams: ONE launch
-                TO.R.kv_partial_update_pair_(ws.nrm[T:R], attn.w_kvq, attn.b_kvq, wide[T:R, :3 * d], attn.norm_q, attn.norm_k,
-                                             ws.nrm[:T], attn.w_add_kvq, attn.b_add_kvq, wide[:T, :3 * d], attn.norm_added_q,
-                                             attn.norm_added_k, cos_q, sin_q, cos_k, sin_k, kv_rows, k_slab, vt_slab, H, T,
-                                             1e-6, partial)
+                PR.kv_partial_update_pair_(ws.act(T, R), attn.w_kvq, attn.b_kvq, wide[T:R, :3 * d], attn.norm_q, attn.norm_k,
+                                           ws.act(0, T), attn.w_add_kvq, attn.b_add_kvq, wide[:T, :3 * d], attn.norm_added_q,
+                                           attn.norm_added_k, cos_q, sin_q, cos_k, sin_k, kv_rows, k_slab, vt_slab, H, T,
+                                           1e-6, partial)
             else:
-                ops.gemm_pair(ws.nrm[T:R], attn.w_kvq, attn.b_kvq, wide[T:R, :3 * d],
-                              ws.nrm[:T], attn.w_add_kvq, attn.b_add_kvq, wide[:T, :3 * d])
+                ops.gemm_pair(ws.act(T, R), attn.w_kvq, attn.b_kvq, wide[T:R, :3 * d],
+                              ws.act(0, T), attn.w_add_kvq, attn.b_add_kvq, wide[:T, :3 * d])
                 ops.qk_norm_rope_store(wide, 0, d, 2 * d, H, attn.norm_q, attn.norm_k, image_rotary_emb, rope_k,
                                        k_slab, vt_slab, kv_rows, split_row=T, wq0=attn.norm_added_q, wk0=attn.norm_added_k)
             q = wide[:, 2 * d:3 * d]
@@ -489,8 +505,8 @@ class FluxAttnProcessor:
             # proj_out only for the rows the caller reads - the text and condition-image rows of this block's output feed
             # nothing.  (Region steps keep the one-launch path: their K/V rows carry the fp16 round trip of quirk A-3.)
             lo, hi = T, T + n_out
-            ops.gemm(ws.nrm[:R], ops.wrows(attn.w_kvqm, None, 2 * d), attn.b_kvqm[:2 * d], wide[:, :2 * d])
-            ops.gemm(ws.nrm[lo:hi], ops.wrows(attn.w_kvqm, 2 * d, None), attn.b_kvqm[2 * d:], wide[lo:hi, 2 * d:], epilogue=ops.EPI_GELU,
+            ops.gemm(ws.act(0, R), ops.wrows(attn.w_kvqm, None, 2 * d), attn.b_kvqm[:2 * d], wide[:, :2 * d])
+            ops.gemm(ws.act(lo, hi), ops.wrows(attn.w_kvqm, 2 * d, None), attn.b_kvqm[2 * d:], wide[lo:hi, 2 * d:], epilogue=ops.EPI_GELU,
                      gelu_from_col=d)
             ops.qk_norm_rope_store(wide, 0, d, 2 * d, H, attn.norm_q, attn.norm_k, image_rotary_emb, rope_k, k_slab,
                                    vt_slab, kv_rows)
@@ -498,10 +514,10 @@ class FluxAttnProcessor:
             TO.R.region_attention(q, k_slab, vt_slab, q, skv, H, -1.0, attn.score_bound())
             return wide[lo:hi, 2 * d:]
         if fuse:
-            TO.R.kv_partial_update_(ws.nrm[:R], attn.w_kvqm, attn.b_kvqm, wide, attn.norm_q, attn.norm_k, cos_q, sin_q, cos_k,
-                                    sin_k, kv_rows, k_slab, vt_slab, H, 0, 1e-6, partial, 3 * d)
+            PR.kv_partial_update_(ws.act(0, R), attn.w_kvqm, attn.b_kvqm, wide, attn.norm_q, attn.norm_k, cos_q, sin_q, cos_k,
+                                  sin_k, kv_rows, k_slab, vt_slab, H, 0, 1e-6, partial, 3 * d)
         else:
-            ops.gemm(ws.nrm[:R], attn.w_kvqm, attn.b_kvqm, wide, epilogue=ops.EPI_GELU, gelu_from_col=3 * d)
+            ops.gemm(ws.act(0, R), attn.w_kvqm, attn.b_kvqm, wide, epilogue=ops.EPI_GELU, gelu_from_col=3 * d)
             ops.qk_norm_rope_store(wide, 0, d, 2 * d, H, attn.norm_q, attn.norm_k, image_rotary_emb, rope_k, k_slab,
                                    vt_slab, kv_rows)
         q = wide[:, 2 * d:3 * d]
@@ -527,17 +543,17 @@ class FluxAttnProcessor:
             ctx.partial_kv = partial
             per.append((wsv, T, R, k_slab, vt_slab, skv))
             if self.single:
-                probs = ((wsv.nrm[:R], attn.w_kvqm, attn.b_kvqm, wsv.wide[:R], attn.norm_q, attn.norm_k, 0, partial),)
+                probs = ((wsv.act(0, R), attn.w_kvqm, attn.b_kvqm, wsv.wide[:R], attn.norm_q, attn.norm_k, 0, partial),)
             else:           # image rows sit behind the T text rows of the branch's joint sequence; only they are ever partial
-                probs = ((wsv.nrm[T:R], attn.w_kvq, attn.b_kvq, wsv.wide[T:R, :3 * d], attn.norm_q, attn.norm_k, T, partial),
-                         (wsv.nrm[:T], attn.w_add_kvq, attn.b_add_kvq, wsv.wide[:T, :3 * d], attn.norm_added_q,
+                probs = ((wsv.act(T, R), attn.w_kvq, attn.b_kvq, wsv.wide[T:R, :3 * d], attn.norm_q, attn.norm_k, T, partial),
+                         (wsv.act(0, T), attn.w_add_kvq, attn.b_add_kvq, wsv.wide[:T, :3 * d], attn.norm_added_q,
                           attn.norm_added_k, 0, False))
             for x, w, b, o, wq, wk, row_base, rtrip in probs:
                 xs.append(x); ws_.append(w); bs.append(b); outs.append(o); nq.append(wq); nk.append(wk)
                 cq.append(rope_q[0]); sq.append(rope_q[1]); ck.append(rope_k[0]); sk.append(rope_k[1])
                 rows.append(kv_rows); kc.append(k_slab); vc.append(vt_slab); rb.append(row_base); rt.append(rtrip)
-        TO.R.kv_partial_update_group_(xs, ws_, bs, outs, nq, nk, cq, sq, ck, sk, rows, kc, vc, H, rb, 1e-6, rt,
-                                      3 * d if self.single else -1)
+        (TO.Direct if ctxs[0].ws.a8 else TO.R).kv_partial_update_group_(xs, ws_, bs, outs, nq, nk, cq, sq, ck, sk, rows, kc, vc, H, rb, 1e-6, rt,
+                                                                        3 * d if self.single else -1)
         # the second branch's attention on a side stream (ATTN_BRANCH_STREAMS above): the same
         # launches with the same arguments - bit-identical - but its first workgroups fill the CUs the first branch's stream-K
         # tail and merge pass leave idle (Qwen 1024^2 region step 65.0 -> 63.7 ms; full steps unchanged)
@@ -575,6 +591,13 @@ def _block_op_target(block, ctx, image_rotary_emb):
     attn = block.attn
     proc = attn.processor
     last = getattr(block, "is_last", False)
+    if BLOCK_OPS and ctx.ws.a8:
+        # rgn_mmdit_*_block has no fp8-activation form: such a trunk runs the Python sequence (same launches, fp8 `nrm`), said once
+        if not _block_op_target.__dict__.get("said"):
+            _block_op_target.__dict__["said"] = True
+            import warnings
+            warnings.warn("BLOCK_OPS: a trunk with fp8 activations runs its blocks launch by launch (the block entries take bf16 rows)")
+        return None
     if not (BLOCK_OPS and getattr(ctx, "block_ops", False) and FUSE_QKV and attn.heads % 2 == 0 and isinstance(proc, FluxAttnProcessor)
             and type(proc).__call__ is FluxAttnProcessor.__call__ and not (last and ctx.out_rows is not None)):
         return None
@@ -640,23 +663,23 @@ class FluxTransformerBlock:
             ctx.forked = False
             ops.rowband_join()             # the last block may skip rows: not the bands' rows
         # norm1 / norm1_context: LN * (1 + scale_msa) + shift_msa   (chunks: shift, scale, gate, shift, scale, gate)
-        ops.ln_modulate(ws.x[:R], ws.nrm[:R], mods.chunk(self.mo_img, 0), mods.chunk(self.mo_img, 1), split_row=T,
+        ops.ln_modulate(ws.x[:R], ws.act(0, R), mods.chunk(self.mo_img, 0), mods.chunk(self.mo_img, 1), split_row=T,
                         shift0=mods.chunk(self.mo_ctx, 0), scale0=mods.chunk(self.mo_ctx, 1))
         self.attn.fwd_ctx, self.attn.block = ctx, self
-        self.attn(hidden_states=ws.nrm[T:R], encoder_hidden_states=ws.nrm[:T], image_rotary_emb=image_rotary_emb)
+        self.attn(hidden_states=ws.act(T, R), encoder_hidden_states=ws.act(0, T), image_rotary_emb=image_rotary_emb)
         if getattr(self, "is_last", False) and ctx.out_rows is not None and not getattr(ctx, "partial_kv", False):
             lo, hi = T, T + ctx.out_rows                      # only these rows of the trunk's output are read
-            ops.ln_modulate(ws.x[lo:hi], ws.nrm[lo:hi], mods.chunk(self.mo_img, 3), mods.chunk(self.mo_img, 4))
+            ops.ln_modulate(ws.x[lo:hi], ws.act(lo, hi), mods.chunk(self.mo_img, 3), mods.chunk(self.mo_img, 4))
             ffh = ws.wide[:R, 3 * d:]
-            ops.gemm(ws.nrm[lo:hi], self.ff_w1, self.ff_b1, ffh[lo:hi], epilogue=ops.EPI_GELU)
+            ops.gemm(ws.act(lo, hi), self.ff_w1, self.ff_b1, ffh[lo:hi], epilogue=ops.EPI_GELU)
             ops.gemm(ffh[lo:hi], self.ff_w2, self.ff_b2, ws.x[lo:hi], epilogue=ops.EPI_GATE_RESID,
                      gate=mods.chunk(self.mo_img, 5), resid=ws.x[lo:hi])
             return ws.x[:T], ws.x[T:R]
         # norm2 + FF with the gated residual fused into the second GEMM
-        ops.ln_modulate(ws.x[:R], ws.nrm[:R], mods.chunk(self.mo_img, 3), mods.chunk(self.mo_img, 4), split_row=T,
+        ops.ln_modulate(ws.x[:R], ws.act(0, R), mods.chunk(self.mo_img, 3), mods.chunk(self.mo_img, 4), split_row=T,
                         shift0=mods.chunk(self.mo_ctx, 3), scale0=mods.chunk(self.mo_ctx, 4))
         ffh = ws.wide[:R, 3 * d:]
-        ops.gemm_pair(ws.nrm[T:R], self.ff_w1, self.ff_b1, ffh[T:R], ws.nrm[:T], self.ffc_w1, self.ffc_b1, ffh[:T],
+        ops.gemm_pair(ws.act(T, R), self.ff_w1, self.ff_b1, ffh[T:R], ws.act(0, T), self.ffc_w1, self.ffc_b1, ffh[:T],
                       epilogue=ops.EPI_GELU)
         ops.gemm_pair(ffh[T:R], self.ff_w2, self.ff_b2, ws.x[T:R], ffh[:T], self.ffc_w2, self.ffc_b2, ws.x[:T],
                       epilogue=ops.EPI_GATE_RESID, gate0=mods.chunk(self.mo_img, 5), resid0=ws.x[T:R],
@@ -677,14 +700,14 @@ class FluxTransformerBlock:
                 out.append((b + c.T, c.mods.chunk(self.mo_ctx, i_shift), c.mods.chunk(self.mo_ctx, i_scale)))
                 out.append((b + c.T + c.M, c.mods.chunk(self.mo_img, i_shift), c.mods.chunk(self.mo_img, i_scale)))
             return out
-        ops.ln_modulate_segs(ws.x[:Rtot], ws.nrm[:Rtot], segs(0, 1))
+        ops.ln_modulate_segs(ws.x[:Rtot], ws.act(0, Rtot), segs(0, 1))
         self.attn.processor.multi(self.attn, self, ctxs, ropes)
-        ops.ln_modulate_segs(ws.x[:Rtot], ws.nrm[:Rtot], segs(3, 4))
+        ops.ln_modulate_segs(ws.x[:Rtot], ws.act(0, Rtot), segs(3, 4))
         up, down = [], []
         for c in ctxs:
             v, T, R = c.ws, c.T, c.T + c.M
             ffh = v.wide[:R, 3 * d:]
-            up += [ops.Problem(v.nrm[T:R], self.ff_w1, self.ff_b1, ffh[T:R]), ops.Problem(v.nrm[:T], self.ffc_w1, self.ffc_b1, ffh[:T])]
+            up += [ops.Problem(v.act(T, R), self.ff_w1, self.ff_b1, ffh[T:R]), ops.Problem(v.act(0, T), self.ffc_w1, self.ffc_b1, ffh[:T])]
             down += [ops.Problem(ffh[T:R], self.ff_w2, self.ff_b2, v.x[T:R], gate=c.mods.chunk(self.mo_img, 5), resid=v.x[T:R]),
                      ops.Problem(ffh[:T], self.ffc_w2, self.ffc_b2, v.x[:T], gate=c.mods.chunk(self.mo_ctx, 5), resid=v.x[:T])]
         ops.gemm_group(up, epilogue=ops.EPI_GELU)
@@ -716,9 +739,9 @@ class FluxSingleTransformerBlock:
         if getattr(self, "is_last", False):
             ctx.forked = False
             ops.rowband_join()             # the last block may skip rows: not the bands' rows
-        ops.ln_modulate(ws.x[:R], ws.nrm[:R], mods.chunk(self.mo, 0), mods.chunk(self.mo, 1))
+        ops.ln_modulate(ws.x[:R], ws.act(0, R), mods.chunk(self.mo, 0), mods.chunk(self.mo, 1))
         self.attn.fwd_ctx, self.attn.block = ctx, self
-        cat = self.attn(hidden_states=ws.nrm[:R], image_rotary_emb=image_rotary_emb)
+        cat = self.attn(hidden_states=ws.act(0, R), image_rotary_emb=image_rotary_emb)
         rows = ws.x[:R] if cat.shape[0] == R else ws.x[T:T + cat.shape[0]]      # last block: only the rows the caller reads
         ops.gemm(cat, self.w_po, self.b_po, rows, epilogue=ops.EPI_GATE_RESID, gate=mods.chunk(self.mo, 2), resid=rows)
         return ws.x[:T], ws.x[T:R]
@@ -727,7 +750,7 @@ class FluxSingleTransformerBlock:
     def multi(self, ctxs: List[FwdCtx], ropes):
         ws = ctxs[0].ws.ws
         Rtot = _branch_rows(ctxs)
-        ops.ln_modulate_segs(ws.x[:Rtot], ws.nrm[:Rtot],
+        ops.ln_modulate_segs(ws.x[:Rtot], ws.act(0, Rtot),
                              [(c.ws.base + c.T + c.M, c.mods.chunk(self.mo, 0), c.mods.chunk(self.mo, 1)) for c in ctxs])
         self.attn.processor.multi(self.attn, self, ctxs, ropes)
         d = ws.cfg.d
@@ -898,12 +921,18 @@ class FluxTransformer2DModel:
         return slots
 
     # -- fp8 weights (BASELINE configs[4]) ----------------------------------------------------------------
-    def quantize_fp8_(self):
+    def quantize_fp8_(self, activations: bool = False):
         """Store the trunk's block GEMM weights (QKV(+MLP), out, FeedForward, proj_out of every block: > 99 % of the
         parameters) as OCP e4m3fn with one fp32 scale per output channel (ops.quantize_w8).  Activations, biases, norms,
         embedders and the AdaLN table stay bf16.  The GEMMs then read half the weight bytes; arithmetic is bf16 MFMA on the
         exactly converted values, the scale multiplies the fp32 accumulator (rgn_gemm_group with wscale).  Row slices of a quantised
-        weight (the last block's row skipping) go through ops.wrows, which slices the scales with it."""
+        weight (the last block's row skipping) go through ops.wrows, which slices the scales with it.
+
+        activations=True (opt-in) also carries the block bodies' LN-modulate output as e4m3fn with one fp32 scale per row
+        (Workspace.act): ops.ln_modulate* quantises the bf16 row it would have stored, and the GEMMs that read it - the Q/K/V
+        projections w_kvq / w_add_kvq, the first feed-forward GEMMs ff_w1 / ffc_w1, the fused w_kvqm - run fp8 x fp8 on the
+        block-scaled MFMA (rgn_gemm_group with ascale).  Everything else - attention, w_out, ff_w2, w_po, norm_out -> proj_out -
+        is unchanged.  It needs every such weight quantised (one format per launch): a trunk with unquantisable slots refuses."""
         def q(obj, name):
             w = getattr(obj, name, None)
             if w is not None and w.dtype == torch.bfloat16:
@@ -917,6 +946,15 @@ class FluxTransformer2DModel:
             q(blk.attn, "w_kvqm")
             q(blk, "w_po")
         self._fp8 = True
+        if activations:
+            names = [(b.attn, n) for b in self.transformer_blocks for n in ("w_kvq", "w_add_kvq")]
+            names += [(b, n) for b in self.transformer_blocks for n in ("ff_w1", "ffc_w1")] + [(b.attn, "w_kvqm") for b in self.single_transformer_blocks]
+            if any(getattr(o, n, None) is not None and getattr(o, n).dtype != ops.FP8 for o, n in names):
+                raise ops._lib.RegionEHipError("quantize_fp8_(activations=True): a projection that reads the normed rows is not fp8")
+            self._a8 = True
+            self.ws.a8 = True
+            for lane in self.__dict__.get("_ws_lanes", {}).values():
+                lane.a8 = True
         torch.cuda.empty_cache()
         return self
 
@@ -1008,6 +1046,7 @@ class FluxTransformer2DModel:
             while len(side) >= self.MAX_SIDE_LANES:
                 del lanes[side.pop(0)]
             lanes[sid] = Workspace(self.cfg_model, self.device)
+            lanes[sid].a8 = bool(getattr(self, "_a8", False))
         else:
             lanes[sid] = lanes.pop(sid) if lanes[sid] is not self.ws else lanes[sid]      # most recently used last
         return lanes[sid]

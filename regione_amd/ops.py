@@ -234,6 +234,53 @@ def _wscale(W: torch.Tensor) -> Optional[torch.Tensor]:
     return s
 
 
+def quantize_rows_a8(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 activations [M, K] -> fp8 e4m3fn [M, K] with one fp32 scale per ROW (rgn_quantize_rows_a8): the arithmetic of quantize_w8 per
+    row - scale = max(amax|x|, 1e-12) / 448, q = e4m3fn(x / scale) - on the device, bit-identical to that torch expression on the CPU.
+    The scales travel ON the result (`._rgn_scale`, fp32 [M]); `out` may be given (fp8 [M, K] with `._rgn_scale` [M] already attached)."""
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or x.stride(1) != 1:
+        raise _lib.RegionEHipError(f"quantize_rows_a8: x must be bf16 [M, K] with unit column stride (got {x.dtype} {tuple(x.shape)})")
+    M, K = x.shape
+    if out is None:
+        out = torch.empty((M, K), dtype=FP8, device=x.device)
+        out._rgn_scale = torch.empty(M, dtype=torch.float32, device=x.device)
+    sc = _a8_out(out, M, K, x.device, "quantize_rows_a8")
+    rc = _lib.lib().rgn_quantize_rows_a8(_p(x), x.stride(0), _p(out), out.stride(0), _p(sc), M, K, _stream())
+    _lib.check(rc, "rgn_quantize_rows_a8")
+    return out
+
+
+def _a8_out(out: torch.Tensor, M: int, K: int, dev, what: str) -> torch.Tensor:
+    """The row-scale vector of an fp8 activation buffer the kernels are about to WRITE (extents checked here: the C ABI cannot)."""
+    sc = getattr(out, "_rgn_scale", None)
+    if out.dtype != FP8 or tuple(out.shape) != (M, K) or out.stride(1) != 1 or out.device != dev:
+        raise _lib.RegionEHipError(f"{what}: out must be fp8 e4m3fn [{M}, {K}] on {dev} (got {out.dtype} {tuple(out.shape)} on {out.device})")
+    if sc is None or sc.dtype != torch.float32 or sc.dim() != 1 or sc.numel() != M or not sc.is_contiguous() or sc.device != dev:
+        raise _lib.RegionEHipError(f"{what}: an fp8 out carries its row scales as `._rgn_scale`, fp32 [{M}], contiguous, on {dev}")
+    return sc
+
+
+def arows(A: torch.Tensor, lo: Optional[int] = None, hi: Optional[int] = None) -> torch.Tensor:
+    """A[lo:hi] (rows) of an activation matrix; for fp8 activations the row scales are sliced with it, as wrows does for weights."""
+    v = A[lo:hi]
+    s = getattr(A, "_rgn_scale", None)
+    if s is not None:
+        v._rgn_scale = s[lo:hi]
+    return v
+
+
+def _ascale(A: torch.Tensor) -> Optional[torch.Tensor]:
+    if A.dtype != FP8:
+        return None
+    s = getattr(A, "_rgn_scale", None)
+    if s is None:
+        raise _lib.RegionEHipError("fp8 activations without their per-row scales (use ops.quantize_rows_a8 / an fp8 `out` of ops.ln_modulate; "
+                                   "slice rows with ops.arows - a plain slice loses the attribute)")
+    if s.dtype != torch.float32 or s.numel() != A.shape[0] or not s.is_contiguous() or s.device != A.device:
+        raise _lib.RegionEHipError(f"fp8 activations [{A.shape[0]} rows]: `_rgn_scale` must be fp32 [{A.shape[0]}], contiguous, on {A.device}")
+    return s
+
+
 class Problem:
     """One problem of a GEMM launch: out[r] = epilogue(A @ W^T + bias) with its own gate / residual, Q/K/V epilogue or row scatter."""
     __slots__ = ("A", "W", "bias", "out", "gate", "resid", "epi", "out_rows")
@@ -253,14 +300,14 @@ def _launch(problems, epilogue: int, gelu_from_col: int):
     arr = (_lib.GemmProblem * len(probs))(*[
         _lib.GemmProblem(_p(p.A), _p(p.W), _p(_wscale(p.W)), _p(p.bias), _p(p.out), _p(p.gate), _p(p.resid),
                          ctypes.pointer(p.epi) if p.epi is not None else None, _p(p.out_rows), p.A.stride(0), p.out.stride(0),
-                         p.A.shape[0], p.W.stride(0)) for p in probs])
+                         p.A.shape[0], p.W.stride(0), _p(_ascale(p.A))) for p in probs])
     ws = gemm_workspace(probs[0].A.device)
     rc = _lib.lib().rgn_gemm_group(arr, len(probs), N, K, epilogue, gelu_from_col, _p(ws), ws.numel() * 4, _stream())
     _lib.check(rc, "rgn_gemm_group")
 
 
 def _check_single(A, W, out):
-    assert A.dtype == out.dtype == torch.bfloat16 and W.dtype in (torch.bfloat16, FP8)
+    assert A.dtype in (torch.bfloat16, FP8) and out.dtype == torch.bfloat16 and W.dtype in (torch.bfloat16, FP8)
     K, N = A.shape[1], W.shape[0]
     assert A.stride(1) == 1 and W.stride(1) == 1 and out.stride(1) == 1 and W.shape[1] == K and out.shape[1] == N
 
@@ -270,7 +317,7 @@ def _check_pair(A0, W0, out0, A1, W1, out1):
     assert W1.shape == (N, K) and W0.is_contiguous() and W1.is_contiguous()
     assert A0.shape[1] == K and A1.shape[1] == K and out0.shape[1] == N and out1.shape[1] == N
     for t in (A0, A1, out0, out1):
-        assert t.stride(1) == 1 and t.dtype == torch.bfloat16
+        assert t.stride(1) == 1 and t.dtype in ((torch.bfloat16, FP8) if t is A0 or t is A1 else (torch.bfloat16,))
 
 
 def gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, *, epilogue: int = EPI_BIAS,
@@ -365,7 +412,7 @@ def gemm_group(problems, *, epilogue: int = EPI_BIAS, gelu_from_col: int = 0):
     for p in probs:
         assert p.W.shape == (N, K) and p.W.is_contiguous() and p.A.shape[1] == K and p.out.shape == (p.A.shape[0], N)
         for t in (p.A, p.out):
-            assert t.stride(1) == 1 and t.dtype == torch.bfloat16
+            assert t.stride(1) == 1 and t.dtype in ((torch.bfloat16, FP8) if t is p.A else (torch.bfloat16,))
         if p.resid is not None:
             assert p.resid.stride(0) == p.out.stride(0) and p.resid.stride(1) == 1
         _check_bias(p.bias, N, p.A.device, "gemm_group")
@@ -542,6 +589,12 @@ def cat_rows(parts, dim: int = 1) -> torch.Tensor:
 def ln_modulate(x: torch.Tensor, out: torch.Tensor, shift1, scale1, split_row: int = 0, shift0=None, scale0=None,
                 eps: float = 1e-6) -> torch.Tensor:
     M, d = x.shape
+    if out.dtype == FP8:          # fp8 rows + row scales (`out._rgn_scale`): bit-identical to quantize_rows_a8 of the bf16 result
+        sc = _a8_out(out, M, d, x.device, "ln_modulate")
+        rc = _lib.lib().rgn_ln_modulate_a8(_p(x), x.stride(0), _p(out), out.stride(0), _p(sc), M, d, eps, split_row, _p(shift0),
+                                           _p(scale0), _p(shift1), _p(scale1), _stream())
+        _lib.check(rc, "rgn_ln_modulate_a8")
+        return out
     rc = _lib.lib().rgn_ln_modulate(_p(x), x.stride(0), _p(out), out.stride(0), M, d, eps, split_row, _p(shift0),
                                     _p(scale0), _p(shift1), _p(scale1), _stream())
     _lib.check(rc, "rgn_ln_modulate")
@@ -558,6 +611,11 @@ def ln_modulate_segs(x: torch.Tensor, out: torch.Tensor, segs, eps: float = 1e-6
     ends = (C.c_int * n)(*[int(s[0]) for s in segs])
     sh = (C.c_void_p * n)(*[_p(s[1]) for s in segs])
     sc = (C.c_void_p * n)(*[_p(s[2]) for s in segs])
+    if out.dtype == FP8:
+        rs = _a8_out(out, M, d, x.device, "ln_modulate_segs")
+        rc = _lib.lib().rgn_ln_modulate_segs_a8(_p(x), x.stride(0), _p(out), out.stride(0), _p(rs), M, d, eps, n, ends, sh, sc, _stream())
+        _lib.check(rc, "rgn_ln_modulate_segs_a8")
+        return out
     rc = _lib.lib().rgn_ln_modulate_segs(_p(x), x.stride(0), _p(out), out.stride(0), M, d, eps, n, ends, sh, sc, _stream())
     _lib.check(rc, "rgn_ln_modulate_segs")
     return out

@@ -243,6 +243,21 @@ _define("gate_resid_rows_", "(Tensor p, Tensor gate, Tensor resid, Tensor(a!) ou
         lambda *a, **k: None, ROW_SCHEMAS, _row_defined)
 
 
+# ---- fp8 activations: the row quantiser (csrc/norm.hip) -----------------------------------------------
+A8_SCHEMAS = {}                 # listed apart like ROW_SCHEMAS: SCHEMAS stays the region-op surface
+_a8_defined = set()
+
+
+def _quantize_rows_a8(x):
+    q = ops.quantize_rows_a8(x)
+    return q, q._rgn_scale
+
+
+# x bf16 [M, K] -> (fp8 e4m3fn [M, K], fp32 row scales [M]); a caller attaches the scales (`q._rgn_scale = scale`) before ops.gemm
+_define("quantize_rows_a8", "(Tensor x) -> (Tensor, Tensor)", _quantize_rows_a8,
+        lambda x: (x.new_empty(x.shape, dtype=ops.FP8), x.new_empty((x.shape[0],), dtype=torch.float32)), A8_SCHEMAS, _a8_defined)
+
+
 # ---- one masked MMDiT block per call (csrc/block.hip) ------------------------------------------------
 BLOCK_SCHEMAS = {}              # listed apart like ROW_SCHEMAS: SCHEMAS stays the region-op surface
 _block_defined = set()
@@ -375,6 +390,10 @@ def registered_block_ops() -> Tuple[str, ...]:
     return tuple(sorted(_block_defined))
 
 
+def registered_a8_ops() -> Tuple[str, ...]:
+    return tuple(sorted(_a8_defined))
+
+
 def _sc(w):
     return ops._wscale(w)
 
@@ -449,3 +468,5 @@ class _Direct:
 
 
 R = _Direct if _mode == "0" else _Dispatched()
+Direct = _Direct        # the engine's fp8-activation trunks: their projections read fp8 rows + row scales, which the registered ops
+                        # (bf16 rows by schema) do not take - the same rgn_gemm_group launches through regione_amd.ops

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the dominant kernels at the FLUX 1024^2 shapes (GPU box only), sustained rate.
-    python tools/bench_kernels.py [gemm] [attn] [gemv]
+    python tools/bench_kernels.py [gemm] [attn] [gemv] [small] [region] [w8] [a8]
 Reports TFLOP/s (algorithmic) per shape, median of N interleaved rounds, uniform random [-1,1) data."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -152,6 +152,46 @@ def bench_w8():
         del W16, W8, A, out
 
 
+def bench_a8():
+    """fp8 activations x fp8 weights on the block-scaled MFMA (rgn_gemm_group with ascale) next to the fp8-weight path and the bf16 path, at
+    the trunk's projections fed by the LN-modulate output: full-step (M = 8704) and region-step (M = 1536) rows.  Alternating legs,
+    uniform random data, cold weights (every launch a different copy).  The A8 leg times the GEMM alone: its operand is quantised once,
+    outside the timed loop (in the engine the LN-modulate kernel writes it)."""
+    shapes = [("single kvq+mlp", 8704, 21504, 3072), ("double qkv", 8704, 9216, 3072), ("double ff up", 8704, 12288, 3072),
+              ("R single kvq+mlp", 1536, 21504, 3072), ("R double qkv", 1536, 9216, 3072), ("R double ff up", 1536, 12288, 3072)]
+    only = os.environ.get("GEMM_ONLY")
+    for name, M, N, K in shapes:
+        if only and only not in name:
+            continue
+        A, b = rnd(M, K), rnd(N)
+        A8 = ops.quantize_rows_a8(A)
+        out = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
+        ncopy = max(2, int(600e6 // (N * K)))
+        W16 = [rnd(N, K) * 0.05 for _ in range(max(2, ncopy // 2))]
+        W8 = [ops.quantize_w8(rnd(N, K) * 0.05) for _ in range(ncopy)]
+        st = {"i": 0}
+
+        def run(a, Ws):
+            st["i"] = (st["i"] + 1) % len(Ws)
+            ops.gemm(a, Ws[st["i"]], b, out)
+        fl = 2.0 * M * N * K
+        legs = [("bf16 A, bf16 W", A, W16, {}), ("bf16 A, fp8 W", A, W8, {}), ("fp8 A, fp8 W", A8, W8, {}),
+                ("fp8 A, fp8 W 256", A8, W8, dict(gemm_geometry=256)), ("fp8 A, fp8 W 128", A8, W8, dict(gemm_geometry=128))]
+        res = {label: [] for label, *_ in legs}
+        for _ in range(3):                       # alternating legs: every leg sees the same clock / power history
+            for label, a, Ws, env in legs:
+                force(env)
+                med, _ = timeit(lambda: run(a, Ws), iters=3, warm=1, inner=10)
+                res[label].append(med)
+        for label, *_ in legs:
+            med = sorted(res[label])[1]
+            print(f"a8 {name:<18} M={M:<6} N={N:<6} K={K:<6} {label:<18} {med*1e3:8.1f} us  {fl/med/1e9:7.1f} TF")
+        med, _ = timeit(lambda: ops.quantize_rows_a8(A, out=A8), iters=3, warm=1, inner=10)
+        print(f"a8 {name:<18} M={M:<6} K={K:<6} quantize_rows_a8 (not part of the legs above) {med*1e3:8.1f} us  {M*K*3/med/1e6:7.1f} GB/s")
+        del W16, W8, A, A8, out
+    force({})
+
+
 def bench_region():
     """The region-partition ops (O(L * 64) bytes -> launch-latency bound; achieved GB/s reported for
     honesty) next to the oracle's CPU time for the same call."""
@@ -227,5 +267,6 @@ if __name__ == "__main__":
     if "small" in which: bench_small()
     if "region" in which: bench_region()
     if "w8" in which: bench_w8()
+    if "a8" in which: bench_a8()
     if "attn" in which: bench_attn()
     if "gemv" in which: bench_gemv()

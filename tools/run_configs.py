@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Full-size runs of the BASELINE.json configurations that are NOT the bench line (GPU box only).
 
-    python tools/run_configs.py [flux_sweep] [flux_cfg] [step1x_512] [step1x_v1p2_2048] [step1x_v1p2_2048_50] [step1x_v1p2_2048_50_fp8] [qwen_1024] [--out FILE]
+    python tools/run_configs.py [flux_sweep] [flux_cfg] [step1x_512] [step1x_v1p2_2048] [step1x_v1p2_2048_50] [step1x_v1p2_2048_50_fp8] [qwen_1024] [--out FILE] [--fp8-activations]
 
 Each case builds the family's engine at its public dimensions with synthetic weights, enables RegionE
 through RegionEHelper exactly like a user would, fixes the edited region by construction (the same
@@ -81,8 +81,9 @@ def run_case(name, family, size, frac, device, cfg_scale=None, T=512, Tn=None, t
         pipe = HQ.QwenImageEditPipeline(HQ.QwenImageTransformer2DModel(cfg, device).load_state_dict_stream(weights_stream(cfg, device, 42)))
         defaults = {}
         fam_key = "qwen"
+    fp8 = fp8 or FP8_ACTIVATIONS
     if fp8:                                  # OCP e4m3fn block-GEMM weights, per-output-channel scales
-        pipe.transformer.quantize_fp8_()
+        pipe.transformer.quantize_fp8_(activations=FP8_ACTIVATIONS)      # --fp8-activations: + fp8 rows into the Q/K/V(+MLP) / FF-up GEMMs
     torch.cuda.synchronize()
     Tn = Tn or T
     lat, img, prompt, pooled = synth.make_edit_inputs(h_tok, w_tok, T, cfg, seed=110, dtype=torch.bfloat16)
@@ -140,7 +141,8 @@ def run_case(name, family, size, frac, device, cfg_scale=None, T=512, Tn=None, t
                finite=bool(torch.isfinite(out.float()).all()), steps=steps, regione_edit_s=tr_s, regione_steps_per_s=steps / tr_s,
                full_token_edit_s=tv, full_token_steps_per_s=steps / tv, speedup=tv / tr_s,
                latent_psnr_vs_full_token_random_weights_db=float(O.psnr(out.cpu(), van.cpu())), cfg_scale=cfg_scale,
-               peak_mem_gb=torch.cuda.max_memory_allocated() / 2 ** 30, weights="fp8 e4m3fn + per-channel scale" if fp8 else "bf16")
+               peak_mem_gb=torch.cuda.max_memory_allocated() / 2 ** 30, weights="fp8 e4m3fn + per-channel scale" if fp8 else "bf16",
+               activations="fp8 e4m3fn + per-row scale into the Q/K/V(+MLP) and FF-up GEMMs" if FP8_ACTIVATIONS else "bf16")
     # GPU time per denoising step by kind (an event at every callback_on_step_end), and - `--ktimer` - the per-shape
     # launch table of one more edit (HIP events around every GEMM / attention launch, like bench.py)
     evs = [torch.cuda.Event(enable_timing=True)]
@@ -191,6 +193,7 @@ def run_case(name, family, size, frac, device, cfg_scale=None, T=512, Tn=None, t
 
 
 KTIMER = False
+FP8_ACTIVATIONS = False
 
 
 CASES = {
@@ -217,17 +220,23 @@ CASES = {
     "qwen_quick": [("qwen_image_edit_1024_cfg4 (configs[2]), one full-token run", "qwen", 1024, 0.25, dict(cfg_scale=4.0, Tn=384, vanilla_runs=1))],
     "flux_cfg_quick": [("flux_1024_truecfg6_ke25, one full-token run", "flux", 1024, 0.25, dict(cfg_scale=6.0, vanilla_runs=1))],
     "qwen_1024": [("qwen_image_edit_1024_cfg4 (configs[2])", "qwen", 1024, 0.25, dict(cfg_scale=4.0, Tn=384))],
+    # the FLUX 1024^2 row on bf16 / fp8 weights with one full-token run: the A/B rows of --fp8-activations
+    "flux_quick": [("flux_1024_ke25, one full-token run", "flux", 1024, 0.25, dict(vanilla_runs=1))],
+    "flux_fp8_quick": [("flux_1024_ke25 fp8 weights, one full-token run", "flux", 1024, 0.25, dict(vanilla_runs=1, fp8=True))],
 }
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("cases", nargs="*", default=[c for c in CASES if not c.startswith("step1x_v1p2_2048_50") and c not in ("qwen_sweep", "qwen_quick", "flux_cfg_quick")])
+    ap.add_argument("cases", nargs="*", default=[c for c in CASES if not c.startswith("step1x_v1p2_2048_50") and c not in ("qwen_sweep", "qwen_quick", "flux_cfg_quick", "flux_quick", "flux_fp8_quick")])
     ap.add_argument("--out", default=None)
     ap.add_argument("--ktimer", action="store_true", help="per-shape launch table of one more edit (HIP events around every GEMM / attention launch)")
+    ap.add_argument("--fp8-activations", action="store_true",
+                    help="every case on fp8 weights AND fp8 activations (quantize_fp8_(activations=True)): the opt-in trunk compute path")
     args = ap.parse_args()
-    global KTIMER
+    global KTIMER, FP8_ACTIVATIONS
     KTIMER = args.ktimer
+    FP8_ACTIVATIONS = args.fp8_activations
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
     results = []
