@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 118
+#define RGN_ABI_VERSION 119
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -691,6 +691,41 @@ typedef struct rgn_lora_term {
     float scale;
 } rgn_lora_term;
 int rgn_lora_merge_bf16(void* dst, int ldd, const void* W, int ldw, int N, int K, const rgn_lora_term* terms, int n_terms, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * a12  Image pre- and post-processing around the VAEs and the vision tower (csrc/image.hip; no reference counterpart: the reference
+ * leaves this to the host pipeline's PIL / numpy / torch code).  The contract of every entry is EQUALITY OF BITS with that host code;
+ * integer and table arithmetic, one writer per output element, no atomics: a repeated call is bit-identical.  Images are uint8
+ * [H, W, 3] (interleaved RGB, dense); src / dst / X pointers are 16-byte aligned, except the src of rgn_image_patchify_u8, which is
+ * read byte by byte and may sit anywhere; at most 2^28 pixels per image (RGN_E_UNSUPPORTED).
+ * Every other refusal is RGN_E_BADARG before any launch.
+ *
+ * rgn_image_resample_u8: ONE separable pass of Pillow's 8-bit resampler.  axis 0 resamples along x (src [in_h, in_w, 3] ->
+ * dst [in_h, out_w, 3]), axis 1 along y (-> dst [out_h, in_w, 3]); the other dimension must not change.  Per output index i of the
+ * resampled dimension the DEVICE tables give bounds[2 i] = first, bounds[2 i + 1] = count (int32) and weights[i * ksize + k], k < count
+ * (int32, 22-bit fixed point; the host builds them in float64 as Pillow's precompute_coeffs + normalize_coeffs_8bpc do):
+ *   acc = 1 << 21;  for k < count: acc += src[first + k] * weights[i, k];  dst = clip(acc >> 22, 0, 255)       (int32, arithmetic shift)
+ * A table entry outside the input (first < 0, count < 0, count > ksize, first + count > size) reads nothing and stores 0.  A resize is
+ * the x pass into a uint8 intermediate, then the y pass; the caller skips a pass whose size does not change, as Pillow does. */
+int rgn_image_resample_u8(const void* src, int in_h, int in_w, void* dst, int out_h, int out_w, const void* bounds, const void* weights,
+                          int ksize, int axis, void* stream);
+/* dst[c, y, x] = table[src[y, x, c]]: uint8 [H, W, 3] -> bf16 [1, 3, H, W] through a 256-entry bf16 DEVICE table (the caller builds it
+ * with the host's own expression, e.g. 2 * (v / 255) - 1 in fp32 rounded to bf16). */
+int rgn_image_u8_to_nchw_bf16(const void* src, void* dst, int H, int W, const void* table, void* stream);
+/* The patch rows of the Qwen2-VL image processor (patch 14, merge 2, temporal 2 with the one frame duplicated) from uint8 [H, W, 3], H and
+ * W positive multiples of 28: N = (H / 14) (W / 14) rows; row ((bh * (W / 28) + bw) * 2 + ih) * 2 + iw is the patch (2 bh + ih, 2 bw + iw),
+ * column ((c * 2 + t) * 14 + dy) * 14 + dx = table[c * 256 + byte] (table: fp32 [3, 256] on the device, the processor's
+ * rescale-then-normalise of every byte).  out_bf16 = 0: dst fp32 [N, 1176], ldo = 1176 (what the processor returns); out_bf16 = 1: dst
+ * bf16 [N, ldo], ldo >= 1176 a multiple of 8, columns [1176, ldo) zero (what rgn_cast_pad_rows makes of the fp32 rows). */
+int rgn_image_patchify_u8(const void* src, int H, int W, const void* table, void* dst, int out_bf16, int ldo, void* stream);
+/* A decoded bf16 image -> uint8 [H, W, 3].  layout RGN_IMAGE_PADDED: X is a padded pixel-major image (pixel (y, x) = row
+ * (y + 1) (W + 2) + x + 1 of `ld` bf16, channels 0..2; ld a multiple of 4; the border is skipped); RGN_IMAGE_NCHW: X is [1, 3, H, W]
+ * (ld ignored).  Per element, as torch on bf16 and numpy on fp32 round:
+ *   t = bf16(x * 0.5);  t = bf16(t + 0.5);  t = clamp(t, 0, 1);  dst = (uint8) rint_half_even(float(t) * 255.0f)
+ * NaN is out of contract. */
+#define RGN_IMAGE_PADDED 0
+#define RGN_IMAGE_NCHW 1
+int rgn_image_bf16_to_u8(const void* X, int layout, int ld, void* dst, int H, int W, void* stream);
 
 /* Device properties the host side needs for roofline reporting (no torch types). */
 int rgn_device_info(int* cu_count, int* clock_khz, size_t* hbm_bytes);

@@ -178,6 +178,11 @@ SIGNATURES = {
     "rgn_mmdit_block_bytes": [],
     # a11: LoRA merge into a bf16 weight at adoption (csrc/lora.hip)
     "rgn_lora_merge_bf16": [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _term_p, _c_int, _c_void_p],
+    # a12: image pre- and post-processing, bit-exact with the host's PIL / numpy / torch code (csrc/image.hip)
+    "rgn_image_resample_u8": [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p],
+    "rgn_image_u8_to_nchw_bf16": [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p],
+    "rgn_image_patchify_u8": [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p],
+    "rgn_image_bf16_to_u8": [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p],
 }
 _RESTYPE = {"rgn_last_error": C.c_char_p, "rgn_abi_struct_bytes": C.c_size_t, "rgn_attention_workspace_bytes": C.c_size_t,
             "rgn_gemm_workspace_bytes": C.c_size_t, "rgn_groupnorm_workspace_bytes": C.c_size_t,

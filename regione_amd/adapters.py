@@ -735,6 +735,181 @@ def _decode_qwen_image(host, vae, z, dev):
     return vae.decode(z, return_dict=False)[0][:, :, 0]
 
 
+# ---- image pre- and post-processing on the device (regione_amd/image_ops.py) ------------------------------------------------------------
+# The stages a hosted call may run on the device, and the ones that do so without being asked (`pipe._regione_hip_image` unset): a stage
+# is on by default when its device path, upload and download included, beat the host leg of tools/image_processing_bench.py on the GPU
+# host - all four did (profiles/r24_image_processing_bench.json), and the outputs are the same bits.
+IMAGE_STAGES = ("resize", "preprocess", "postprocess", "vlm")
+IMAGE_STAGES_DEFAULT = frozenset(IMAGE_STAGES)
+
+
+def _cfg_get(cfg, name):
+    return cfg.get(name) if isinstance(cfg, dict) else getattr(cfg, name, None)
+
+
+def _is_rgb_pil(img) -> bool:
+    return getattr(img, "mode", None) == "RGB" and hasattr(img, "size") and hasattr(img, "resize") and not isinstance(img, torch.Tensor)
+
+
+def hip_image_ops_for(host, dev, stage: str):
+    """The HipImageOps of this host (made once, kept on it as `_regione_hip_image_ops`) when `stage` of its image work runs on the device,
+    else None: `pipe._regione_hip_image = False` keeps every stage on the host's own methods, `= True` moves every stage a call qualifies
+    for, unset moves the stages of IMAGE_STAGES_DEFAULT.  A call qualifies when the host's `image_processor.config` says do_resize,
+    do_normalize and resample == "lanczos" and sets none of do_binarize, do_convert_grayscale, do_convert_rgb: the arithmetic the kernels
+    restate.  Every other host keeps its own methods, silently."""
+    flag = host.__dict__.get("_regione_hip_image", None)
+    if flag is False or (flag is not True and stage not in IMAGE_STAGES_DEFAULT):
+        return None
+    cfg = getattr(getattr(host, "image_processor", None), "config", None)
+    if cfg is None or not (_cfg_get(cfg, "do_resize") and _cfg_get(cfg, "do_normalize") and _cfg_get(cfg, "resample") == "lanczos"):
+        return None
+    if _cfg_get(cfg, "do_binarize") or _cfg_get(cfg, "do_convert_grayscale") or _cfg_get(cfg, "do_convert_rgb"):
+        return None
+    io = host.__dict__.get("_regione_hip_image_ops")
+    if io is None:
+        from .image_ops import HipImageOps
+        io = host._regione_hip_image_ops = HipImageOps(dev)
+    return io
+
+
+def _image_inputs_on_device(host, dev, images):
+    """HipImageOps when the condition images' resize + preprocess run on the device: every image one RGB PIL image, both stages on, and
+    the VAE encoder adopted (it reads bf16, the rounding the device preprocess ends in; a host encoder keeps the host's fp32 tensor)."""
+    if not images or not all(_is_rgb_pil(i) for i in images):
+        return None
+    io = hip_image_ops_for(host, dev, "resize")
+    if io is None or hip_image_ops_for(host, dev, "preprocess") is None or hip_vae_encoder_for(host, dev) is None:
+        return None
+    return io
+
+
+def _postprocess_image(host, vae, lat, dev, output_type):
+    """`image_processor.postprocess(vae.decode(lat))` of the FLUX / Step1X calls; output_type "pil" with the adopted decoder ends in the
+    byte kernel (decode_u8) and one download."""
+    io = hip_image_ops_for(host, dev, "postprocess") if output_type == "pil" else None
+    hv = hip_vae_for(host, dev) if io is not None else None
+    if hv is not None and hasattr(hv, "decode_u8") and lat.dim() == 4 and lat.shape[0] == 1:
+        return [io.to_pil(hv.decode_u8(lat.to(dev)))]
+    return host.image_processor.postprocess(_decode_image(host, vae, lat, dev), output_type=output_type)
+
+
+def _postprocess_qwen_image(host, vae, z, dev, output_type):
+    """The same for the Qwen pipelines (`vae.decode(z)[0][:, :, 0]`)."""
+    from . import qwen_vae as Q
+    io = hip_image_ops_for(host, dev, "postprocess") if output_type == "pil" else None
+    hv = hip_vae_for(host, dev) if io is not None else None
+    if isinstance(hv, Q.HipQwenVaeDecoder) and hv.out_dtype == torch.bfloat16 and _qwen_vae_refusal(vae, z, "decode") is None:
+        return [io.to_pil(hv.decode_u8(z.to(dev)))]
+    return host.image_processor.postprocess(_decode_qwen_image(host, vae, z, dev), output_type=output_type)
+
+
+def _qwen2vl_processor_refusal(own) -> Optional[str]:
+    """Why the device does not restate this VLM image processor (None: it is transformers' PIL backend with the Qwen2-VL defaults, the
+    arithmetic the kernels restate)."""
+    from .image_ops import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD
+    if not callable(own):
+        return "not callable"
+    # the PIL / numpy backend ONLY: transformers' torchvision backend (`Qwen2VLImageProcessor`, what AutoProcessor picks when torchvision
+    # is installed) carries the same attribute values and other arithmetic - torchvision's antialiased bicubic, rescale and normalise
+    # fused as (v - 255 mean) / (255 std) in torch fp32 - so it is told apart by class and `backend`, never by its settings
+    if not any(c.__name__ == "Qwen2VLImageProcessorPil" for c in type(own).__mro__) or getattr(own, "backend", None) != "pil":
+        return f"{type(own).__name__} (backend {getattr(own, 'backend', None)!r}): Qwen2VLImageProcessorPil, the PIL backend, is covered"
+    for name, want in (("do_resize", True), ("do_rescale", True), ("do_normalize", True), ("patch_size", 14), ("merge_size", 2),
+                       ("temporal_patch_size", 2)):
+        if getattr(own, name, None) != want:
+            return f"{name} = {getattr(own, name, None)!r}"
+    if int(getattr(own, "resample", -1) or -1) != 3:                      # PILImageResampling.BICUBIC
+        return f"resample = {getattr(own, 'resample', None)!r}"
+    if getattr(own, "rescale_factor", None) != 1 / 255:
+        return f"rescale_factor = {getattr(own, 'rescale_factor', None)!r}"
+    for name, want in (("image_mean", OPENAI_CLIP_MEAN), ("image_std", OPENAI_CLIP_STD)):
+        got = getattr(own, name, None)
+        if got is None or tuple(float(v) for v in got) != want:
+            return f"{name} = {got!r}"
+    size = getattr(own, "size", None)
+    if _cfg_get(size, "shortest_edge") is None or _cfg_get(size, "longest_edge") is None:
+        return f"size = {size!r}"
+    if getattr(own, "do_pad", None) or getattr(own, "do_center_crop", None):
+        return "do_pad / do_center_crop"
+    return None
+
+
+class _HipQwen2VLImageProcessor:
+    """What `processor.image_processor` is bound to during a hosted Qwen `encode_prompt`: `(images=[...], return_tensors="pt")` of RGB PIL
+    images is answered on the device - smart_resize, bicubic resize, rescale / normalise / patchify - with `pixel_values` ON the device
+    (fp32 [N, 1176], or the vision tower's padded bf16 rows when the HIP tower reads them) and `image_grid_thw`.  Anything else - videos,
+    other keyword arguments, other image types, a size outside the processor's pixel limits - goes to the host's own image processor, as
+    does every attribute (`merge_size`, `get_number_of_image_patches`, ...)."""
+
+    def __init__(self, own, io, twins, Kp=None):
+        self.__dict__.update(_own=own, _io=io, _twins=twins, _Kp=Kp)
+
+    def __getattr__(self, name):
+        return getattr(self.__dict__["_own"], name)
+
+    def __call__(self, images=None, *args, **kw):
+        own, io = self._own, self._io
+        imgs = list(images) if isinstance(images, (list, tuple)) else [images]
+        if args or set(kw) - {"return_tensors"} or kw.get("return_tensors") != "pt" or not imgs or \
+                not all(id(i) in self._twins or _is_rgb_pil(i) for i in imgs):
+            return own(images, *args, **kw)
+        lo, hi = _cfg_get(own.size, "shortest_edge"), _cfg_get(own.size, "longest_edge")
+        plan = []
+        for i in imgs:
+            w, h = i.size
+            if min(h, w) < 1 or max(h, w) / min(h, w) > 200:
+                return own(images, **kw)
+            rh, rw = round(h / 28) * 28, round(w / 28) * 28
+            if rh < 28 or rw < 28 or not lo <= rh * rw <= hi:             # the processor's rescaling branches: its own code
+                return own(images, **kw)
+            plan.append((i, rh, rw))
+        rows, grids = [], []
+        for i, rh, rw in plan:
+            u8 = self._twins.get(id(i))
+            u8 = io.upload(i) if u8 is None else u8
+            u8 = io.resize(u8, rh, rw, "bicubic")
+            rows.append(io.to_patch_rows(u8, out="padded_bf16", Kp=self._Kp) if self._Kp else io.to_patch_rows(u8))
+            grids.append([1, rh // 14, rw // 14])
+        data = {"pixel_values": rows[0] if len(rows) == 1 else torch.cat(rows, 0), "image_grid_thw": torch.tensor(grids, dtype=torch.int64)}
+        try:
+            from transformers.feature_extraction_utils import BatchFeature
+            return BatchFeature(data=data)
+        except ImportError:
+            return data
+
+
+class _hip_qwen_image_processor:
+    """`with _hip_qwen_image_processor(host, dev, twins): host.encode_prompt(...)` - the host's own code runs with
+    `processor.image_processor` bound (in the processor's instance dict) to a _HipQwen2VLImageProcessor; undone on exit, an exception
+    included.  `twins`: id(PIL image) -> its uint8 twin on the device, so an image this call made on the device is not uploaded again."""
+
+    def __init__(self, host, dev, twins=None):
+        self.host, self.dev, self.twins, self.proc = host, dev, {} if twins is None else twins, None
+
+    def __enter__(self):
+        proc = getattr(self.host, "processor", None)
+        own = getattr(proc, "image_processor", None)
+        io = hip_image_ops_for(self.host, self.dev, "vlm") if own is not None and hasattr(proc, "__dict__") else None
+        if io is None or _qwen2vl_processor_refusal(own) is not None:
+            return self
+        tower = getattr(hip_qwen_text_encoder_for(self.host, self.dev), "vision", None)
+        if type(tower).__name__ != "HipQwen25VLVisionTower":     # the rows stay on the device: only the HIP tower is known to read them there
+            return self
+        Kp = tower.Kp if tower.Kp != tower.K else None
+        self.proc, self.saved = proc, proc.__dict__.get("image_processor", _NO_HIP_VAE)
+        proc.__dict__["image_processor"] = _HipQwen2VLImageProcessor(own, io, self.twins, Kp)
+        return self
+
+    def __exit__(self, *a):
+        if self.proc is not None:
+            if self.saved is _NO_HIP_VAE:
+                del self.proc.__dict__["image_processor"]
+            else:
+                self.proc.__dict__["image_processor"] = self.saved
+            self.proc = None
+        return False
+
+
 class _Clock:
     """Wall-clock of the stages of an edit (end-to-end = encode + loop + decode)."""
 
@@ -774,8 +949,12 @@ def _hosted_flux(host, eng, image=None, prompt=None, prompt_2=None, negative_pro
             ar = image_width / image_height
             _, image_width, image_height = min((abs(ar - w / h), w, h) for w, h in preferred)
         image_width, image_height = image_width // multiple_of * multiple_of, image_height // multiple_of * multiple_of
-        image = host.image_processor.resize(image, image_height, image_width)
-        image = host.image_processor.preprocess(image, image_height, image_width)
+        io = _image_inputs_on_device(host, dev, image if isinstance(image, list) else [image])
+        if io is not None and not (isinstance(image, list) and len(image) != 1):
+            image = io.to_vae_input(io.resize(io.upload(img), image_height, image_width, "lanczos"))     # the same bits, on the device
+        else:
+            image = host.image_processor.resize(image, image_height, image_width)
+            image = host.image_processor.preprocess(image, image_height, image_width)
         height, width = image.shape[-2], image.shape[-1]
     else:
         height = height or host.default_sample_size * host.vae_scale_factor
@@ -822,7 +1001,7 @@ def _hosted_flux(host, eng, image=None, prompt=None, prompt_2=None, negative_pro
         lat = host._unpack_latents(latents.to(vae.dtype if hasattr(vae, "dtype") else latents.dtype), height, width,
                                    host.vae_scale_factor)
         lat = lat / vae.config.scaling_factor + vae.config.shift_factor
-        out = host.image_processor.postprocess(_decode_image(host, vae, lat, dev), output_type=output_type)
+        out = _postprocess_image(host, vae, lat, dev, output_type)
     if hasattr(host, "maybe_free_model_hooks"):
         host.maybe_free_model_hooks()
     clk.mark("decode_s")
@@ -1080,7 +1259,7 @@ def _hosted_step1x(host, eng, image=None, prompt=None, negative_prompt=None, tru
         vae = host.vae
         lat = host._unpack_latents(latents.to(getattr(vae, "dtype", latents.dtype)), height, width, host.vae_scale_factor)
         lat = lat / vae.config.scaling_factor + vae.config.shift_factor
-        out = host.image_processor.postprocess(_decode_image(host, vae, lat, dev), output_type=output_type)
+        out = _postprocess_image(host, vae, lat, dev, output_type)
         out = host._output_process_image(out, img_info)
     if hasattr(host, "maybe_free_model_hooks"):
         host.maybe_free_model_hooks()
@@ -1120,16 +1299,33 @@ def _hosted_qwen(host, eng, image=None, prompt=None, negative_prompt=None, true_
     width, height = width // multiple_of * multiple_of, height // multiple_of * multiple_of
     tok = lambda px: px // host.vae_scale_factor // 2
     is_latent = isinstance(image, torch.Tensor) and image.size(1) == getattr(host, "latent_channels", -1)
+    io = None if is_latent or (not plus and isinstance(image, list)) else _image_inputs_on_device(host, dev, imgs)
+    twins = {}                                             # id(prompt image) -> its uint8 twin on the device (the VLM stage reads it there)
+
+    def prompt_twin(u8):
+        pil = io.to_pil(u8)                                # the host's encode_prompt wants a PIL image: one download
+        twins[id(pil)] = u8
+        return pil
     if plus and not is_latent:
         prompt_image, vae_images, cond_shapes = [], [], []
         for img in imgs:
             iw, ih = img.size if hasattr(img, "size") and not isinstance(img, torch.Tensor) else (img.shape[-1], img.shape[-2])
             cw, ch = _qwen_dims(QWEN_CONDITION_IMAGE_SIZE, iw / ih)
             vw, vh = _qwen_dims(QWEN_VAE_IMAGE_SIZE, iw / ih)
-            prompt_image.append(host.image_processor.resize(img, ch, cw))
-            vae_images.append(host.image_processor.preprocess(img, vh, vw).unsqueeze(2))
+            if io is not None:
+                u8 = io.upload(img)
+                prompt_image.append(prompt_twin(io.resize(u8, ch, cw, "lanczos")))
+                vae_images.append(io.to_vae_input(io.resize(u8, vh, vw, "lanczos")).unsqueeze(2))
+            else:
+                prompt_image.append(host.image_processor.resize(img, ch, cw))
+                vae_images.append(host.image_processor.preprocess(img, vh, vw).unsqueeze(2))
             cond_shapes.append((tok(vh), tok(vw)))
         image = vae_images
+    elif not is_latent and io is not None:
+        u8 = io.resize(io.upload(image), calc_h, calc_w, "lanczos")
+        prompt_image = prompt_twin(u8)
+        image = io.to_vae_input(u8).unsqueeze(2)
+        cond_shapes = [(tok(calc_h), tok(calc_w))]
     elif not is_latent:
         image = host.image_processor.resize(image, calc_h, calc_w)
         prompt_image = image
@@ -1141,7 +1337,8 @@ def _hosted_qwen(host, eng, image=None, prompt=None, negative_prompt=None, true_
     do_true_cfg = true_cfg_scale > 1 and has_neg
     enc = lambda p, e, m: host.encode_prompt(image=prompt_image, prompt=p, prompt_embeds=e, prompt_embeds_mask=m, device=exec_dev,
                                              num_images_per_prompt=1, max_sequence_length=max_sequence_length)
-    with _hip_qwen_text_encoder(host, dev):                # the Qwen2.5-VL language model of encode_prompt on the HIP kernels
+    # the Qwen2.5-VL language model of encode_prompt on the HIP kernels; its image processor on the device
+    with _hip_qwen_text_encoder(host, dev), _hip_qwen_image_processor(host, dev, twins):
         prompt_embeds, prompt_embeds_mask = enc(prompt, prompt_embeds, prompt_embeds_mask)
         if do_true_cfg:
             negative_prompt_embeds, negative_prompt_embeds_mask = enc(negative_prompt, negative_prompt_embeds, negative_prompt_embeds_mask)
@@ -1164,7 +1361,7 @@ def _hosted_qwen(host, eng, image=None, prompt=None, negative_prompt=None, true_
         lat = host._unpack_latents(latents, height, width, host.vae_scale_factor).to(vae.dtype)
         mean = torch.tensor(vae.config.latents_mean).view(1, vae.config.z_dim, 1, 1, 1).to(lat.device, lat.dtype)
         inv_std = 1.0 / torch.tensor(vae.config.latents_std).view(1, vae.config.z_dim, 1, 1, 1).to(lat.device, lat.dtype)
-        out = host.image_processor.postprocess(_decode_qwen_image(host, vae, lat / inv_std + mean, dev), output_type=output_type)
+        out = _postprocess_qwen_image(host, vae, lat / inv_std + mean, dev, output_type)
     if hasattr(host, "maybe_free_model_hooks"):
         host.maybe_free_model_hooks()
     clk.mark("decode_s")

@@ -9,14 +9,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libregione_hip.so")
-SOURCES = ["region.hip", "gemm.hip", "norm.hip", "attn.hip", "vae.hip", "text.hip", "vision.hip", "decode.hip", "connector.hip", "block.hip", "lora.hip"]
+SOURCES = ["region.hip", "gemm.hip", "norm.hip", "attn.hip", "vae.hip", "text.hip", "vision.hip", "decode.hip", "connector.hip", "block.hip", "lora.hip", "image.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 # region / norm kernels mirror eager op sequences rounding-for-rounding: a*b+c must NOT contract to fma
 # attention: no NaN can reach the running max (masked scores are -inf, m_run starts finite), and telling the
 # compiler so drops the v_max canonicalisation of every MFMA output and lets max(max(a,b),c) become v_max3
 EXTRA = {"region.hip": ["-ffp-contract=off"], "norm.hip": ["-ffp-contract=off"], "attn.hip": ["-fno-honor-nans"],
-         "text.hip": ["-ffp-contract=off"], "vision.hip": ["-ffp-contract=off"], "decode.hip": ["-ffp-contract=off"], "connector.hip": ["-ffp-contract=off"]}
+         "text.hip": ["-ffp-contract=off"], "vision.hip": ["-ffp-contract=off"], "decode.hip": ["-ffp-contract=off"], "connector.hip": ["-ffp-contract=off"], "image.hip": ["-ffp-contract=off"]}
 
 
 TORCH_LIB_PATH = os.path.join(LIB_DIR, "libregione_torch.so")

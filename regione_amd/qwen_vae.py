@@ -241,10 +241,22 @@ class HipQwenVaeDecoder(_QwenBase):
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:
+        return self._to_host(self._forward(z, "decode"), 3, clamp=True)
+
+    @torch.no_grad()
+    def decode_u8(self, z: torch.Tensor) -> torch.Tensor:
+        """The same forward, ending in the bytes of the host's `postprocess(decode(z)[:, :, 0], "pil")`: uint8 [8h, 8w, 3] on the device.
+        decode()'s clamp to [-1, 1] needs no launch here: `x * 0.5 + 0.5` is monotone through its bf16 roundings and sends -1 to 0 and 1 to
+        1, so the byte map's own clamp to [0, 1] gives every value beyond +-1 the byte the clamped value gets."""
+        if self.out_dtype != torch.bfloat16:
+            raise _lib.RegionEHipError(f"HipQwenVaeDecoder.decode_u8: out_dtype {self.out_dtype} (the host's bf16 postprocess arithmetic is covered)")
+        return self._to_u8(self._forward(z, "decode_u8"))
+
+    def _forward(self, z: torch.Tensor, who: str):
         if not z.is_cuda or z.dim() != 5 or z.shape[0] != 1 or z.shape[1] != self.zc or z.shape[2] != 1:
-            raise _lib.RegionEHipError(f"HipQwenVaeDecoder.decode: one latent frame [1, {self.zc}, 1, h, w] on the GPU, got {tuple(z.shape)} on {z.device}")
+            raise _lib.RegionEHipError(f"HipQwenVaeDecoder.{who}: one latent frame [1, {self.zc}, 1, h, w] on the GPU, got {tuple(z.shape)} on {z.device}")
         h, w = z.shape[3], z.shape[4]
-        check_image_size(8 * h, 8 * w, "HipQwenVaeDecoder.decode")
+        check_image_size(8 * h, 8 * w, f"HipQwenVaeDecoder.{who}")
         top = cs(self.top)
         zq = self._conv_to(self._load(z[:, :, 0].to(torch.bfloat16).contiguous(), self.zc, h, w), "post_quant_conv", 64)
         x = self._run_mid(self._conv_to(zq, "conv_in", top), top)
@@ -253,7 +265,7 @@ class HipQwenVaeDecoder(_QwenBase):
                 x = self._run_resnet(x, f"up_blocks.{i}.resnets.{j}", cs(co))
             if up:
                 x = self._up(x, f"up_blocks.{i}.upsamplers.0.resample.1", cs(co // 2))
-        return self._to_host(self._head(x, "norm_out", 8), 3, clamp=True)
+        return self._head(x, "norm_out", 8)
 
     def flops(self, h: int, w: int) -> float:
         """Algorithmic FLOPs of one decode of an h x w latent frame as the 2-D network (valid channels; no padding, no time taps)."""

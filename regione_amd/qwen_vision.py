@@ -200,7 +200,8 @@ class HipQwen25VLVisionTower:
     """`Qwen2_5_VisionTransformerPretrainedModel(pixel_values, grid_thw)` on the HIP kernels.  Adopts the tower of a
     Qwen2_5_VLForConditionalGeneration (`model.visual.*`), the tower itself, or a state dict of either with its config.  Returns an object
     with `.pooler_output` [N / merge^2, out_hidden_size] (the merged rows in the module's original order) and `.last_hidden_state` [N, d]
-    (window order, as the module's), both freshly allocated bf16."""
+    (window order, as the module's), both freshly allocated bf16.  `pixel_values`: fp32 or bf16 [N, K] as the image processor returns
+    them, or bf16 [N, Kp] rows whose columns [K, Kp) the caller has zeroed (they skip rgn_cast_pad_rows and are not checked)."""
     what = "HipQwen25VLVisionTower"
 
     def __init__(self, module_or_state_dict, device=None, config=None, max_patches: int = 16384):
@@ -268,8 +269,13 @@ class HipQwen25VLVisionTower:
         if kw:
             _refuse(self.what, f"arguments {sorted(kw)} are not implemented")
         key, N, tab = self._tables(grid_thw)
-        if not isinstance(pixel_values, torch.Tensor) or pixel_values.dim() != 2 or tuple(pixel_values.shape) != (N, self.K):
-            _refuse(self.what, f"pixel_values of shape {tuple(getattr(pixel_values, 'shape', ()))} for grid_thw {list(key)} (rows [{N}, {self.K}])")
+        # bf16 rows already padded to the GEMM's K ([N, Kp]: HipImageOps.to_patch_rows(out="padded_bf16")) are the patch GEMM's operand as
+        # they stand.  CALLER'S OBLIGATION: the columns [K, Kp) are zero - they are not looked at (a device read), and anything else there
+        # is multiplied into the patch embedding.
+        padded = isinstance(pixel_values, torch.Tensor) and self.Kp != self.K and pixel_values.dtype == torch.bfloat16 and \
+            tuple(pixel_values.shape) == (N, self.Kp)
+        if not padded and (not isinstance(pixel_values, torch.Tensor) or pixel_values.dim() != 2 or tuple(pixel_values.shape) != (N, self.K)):
+            _refuse(self.what, f"pixel_values of shape {tuple(getattr(pixel_values, 'shape', ()))} for grid_thw {list(key)} (rows [{N}, {self.K}], or bf16 [{N}, {self.Kp}] zero-padded by the caller)")
         if pixel_values.dtype not in (torch.float32, torch.bfloat16):
             _refuse(self.what, f"pixel_values of dtype {pixel_values.dtype} (fp32 or bf16)")
         x = pixel_values.detach().to(self.device).contiguous()
@@ -279,7 +285,10 @@ class HipQwen25VLVisionTower:
                                    m=(M, self.unit * d)))
         xp, h, n, qkv, a, ff, g, m1 = (t[k] for k in ("xp", "h", "n", "qkv", "a", "ff", "g", "m"))
         lib = _lib.lib()
-        _lib.check(lib.rgn_cast_pad_rows(_p(x), ops._dt(x), x.stride(0), _p(xp), N, self.K, self.Kp, _stream()), "rgn_cast_pad_rows")
+        if padded:
+            xp = x
+        else:
+            _lib.check(lib.rgn_cast_pad_rows(_p(x), ops._dt(x), x.stride(0), _p(xp), N, self.K, self.Kp, _stream()), "rgn_cast_pad_rows")
         ops.gemm(xp, w["patch"], None, h, out_rows=tab["patch_rows"])
         cos, sin = tab["cos"], tab["sin"]
         for i in range(self.depth):

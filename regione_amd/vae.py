@@ -577,6 +577,13 @@ class _KLBase:
         self.pool.put(y)
         return out
 
+    def _to_u8(self, y: PaddedImage) -> torch.Tensor:
+        """The decoded image's channels 0..2 as uint8 [H, W, 3]: the host's `postprocess` arithmetic (rgn_image_bf16_to_u8)."""
+        out = torch.empty((y.H, y.W, 3), dtype=torch.uint8, device=self.device)
+        _lib.check(_lib.lib().rgn_image_bf16_to_u8(y.ptr(), 0, y.C, _p(out), y.H, y.W, _stream()), "rgn_image_bf16_to_u8")
+        self.pool.put(y)
+        return out
+
 
 class HipVaeDecoder(_KLBase):
     """AutoencoderKL decoder ([EXT] diffusers layout) on libregione_hip.so.  `decode(z)`: z [1, Cz, h, w] -> image [1, 3, 8h, 8w] bf16."""
@@ -609,10 +616,18 @@ class HipVaeDecoder(_KLBase):
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:
+        return self._to_host(self._forward(z, "decode"), 3)
+
+    @torch.no_grad()
+    def decode_u8(self, z: torch.Tensor) -> torch.Tensor:
+        """The same forward, ending in the bytes of the host's `postprocess(decode(z), "pil")`: uint8 [8h, 8w, 3] on the device."""
+        return self._to_u8(self._forward(z, "decode_u8"))
+
+    def _forward(self, z: torch.Tensor, who: str) -> PaddedImage:
         if not z.is_cuda or z.dim() != 4 or z.shape[0] != 1 or z.shape[1] != self.zc:
-            raise _lib.RegionEHipError(f"HipVaeDecoder.decode: one latent image [1, {self.zc}, h, w] on the GPU, got {tuple(z.shape)} on {z.device}")
+            raise _lib.RegionEHipError(f"HipVaeDecoder.{who}: one latent image [1, {self.zc}, h, w] on the GPU, got {tuple(z.shape)} on {z.device}")
         h, w = z.shape[2], z.shape[3]
-        check_image_size(8 * h, 8 * w, "HipVaeDecoder.decode")
+        check_image_size(8 * h, 8 * w, f"HipVaeDecoder.{who}")
         top = self.ch[-1]
         x = self._conv_to(self._load(z.to(torch.bfloat16).contiguous(), self.zc, h, w), "conv_in", top, gn=self.fuse_gn)
         x = self._run_mid(x, top)
@@ -621,7 +636,7 @@ class HipVaeDecoder(_KLBase):
                 x = self._run_resnet(x, f"up_blocks.{i}.resnets.{j}", co)
             if up:
                 x = self._up(x, f"up_blocks.{i}.upsamplers.0.conv", co)
-        return self._to_host(self._head(x, "conv_norm_out", 8), 3)
+        return self._head(x, "conv_norm_out", 8)
 
     def flops(self, h: int, w: int) -> float:
         """Algorithmic FLOPs of one decode of an h x w latent (2 * valid pixels * Cout * taps * Cin per convolution + the attention GEMMs)."""
