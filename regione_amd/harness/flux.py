@@ -891,7 +891,7 @@ class FluxTransformer2DModel:
     def weight_slots(self) -> Dict[str, Tuple[object, str, int, Optional[int]]]:
         """Where load_state_dict_stream puts every 2-D weight: diffusers FLUX name -> (object, attribute, first row, end row) - a row
         range of a packed tensor (w_kvq / w_add_kvq / w_kvqm, the AdaLN table mod_w) or (0, None) for a tensor of its own.  The
-        adapter's LoRA re-merge (regione_amd/adapters.py) rewrites exactly these rows."""
+        adapter's LoRA re-merge (regione_amd.adapters.lora_sync) rewrites exactly these rows."""
         d, ff = self.cfg_model.d, self.cfg_model.d * self.cfg_model.mlp_ratio
         slots: Dict[str, Tuple[object, str, int, Optional[int]]] = {}
         for i, blk in enumerate(self.transformer_blocks):

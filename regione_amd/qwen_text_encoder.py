@@ -41,7 +41,7 @@ the loop), which overwrites the id slot: still no token visits the host inside a
 `uniforms=`, not from torch.multinomial: a seed gives transformers' distribution, not transformers' tokens.
 
 There is no eager fallback inside: what the kernels do not implement raises RegionEHipError before any launch, and the adapter
-(regione_amd/adapters.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
+(regione_amd.adapters, components.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
 only; every call returns freshly allocated outputs.
 """
 from __future__ import annotations

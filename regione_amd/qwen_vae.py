@@ -20,7 +20,7 @@ For one image (T = 1, the first and only causal chunk) the module reduces to a 2
 The 96-channel level is stored at 128 channels (zero weights, bias and gamma in channels 96..127: rgn_conv_bf16 walks K in steps of 64, and
 the 128-channel pixel-group path fills the 256-wide MFMA tile); 192 channels fill 3/4 of a 256-wide tile.  Activations are bf16 (fp32
 accumulation, one bf16 rounding per launch); the output is converted to the host VAE's dtype (bf16 or fp32) by the last launch.
-No CPU / eager fallback inside: a missing library raises RegionEHipError; the adapter (regione_amd/adapters.py) decides, before calling,
+No CPU / eager fallback inside: a missing library raises RegionEHipError; the adapter (regione_amd.adapters, components.py) decides, before calling,
 whether the kernels cover a call and otherwise keeps the host module.
 """
 from __future__ import annotations

@@ -19,7 +19,7 @@ table [H][2 Lmax - 1] is built at adoption with transformers' own `compute_bias`
 of distances 16, 32 and 64 depends on the last bit of a float32 `log`, so it is not recomputed elsewhere.
 
 There is no eager fallback inside: what the kernels do not implement (an attention mask, hidden states of every layer, L > Lmax, another
-activation) raises RegionEHipError, and the adapter (regione_amd/adapters.py) keeps the host module for layouts it cannot adopt.
+activation) raises RegionEHipError, and the adapter (regione_amd.adapters, components.py) keeps the host module for layouts it cannot adopt.
 Activation buffers are kept for the last sequence length only; every call returns freshly allocated outputs.
 """
 from __future__ import annotations

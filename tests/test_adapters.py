@@ -1,4 +1,4 @@
-"""Host-pipeline adapter (regione_amd/adapters.py): a stock-pipeline-shaped object goes on the HIP engine.
+"""Host-pipeline adapter (the regione_amd.adapters package): a stock-pipeline-shaped object goes on the HIP engine.
 
 Host stand-ins: the `torch.nn` module trees of tests/host_trunks.py (host parameter naming, their own vanilla CPU forward and
 stock attention processors) + a minimal host pipeline with the method surface the reference's `__call__` uses

@@ -1,4 +1,4 @@
-"""LoRA adoption and hot-swap at FLUX.1 dimensions (regione_amd/adapters.py, rgn_lora_merge_bf16): what `enable()` and a later
+"""LoRA adoption and hot-swap at FLUX.1 dimensions (regione_amd.adapters `adopt_engine` / `lora_sync`, rgn_lora_merge_bf16): what `enable()` and a later
 `set_adapters` / call-time scale cost.
 
 A FLUX-size host transformer (the module tree of tests/host_trunks.py at the public dimensions: 19 double + 38 single blocks, d = 3072,
