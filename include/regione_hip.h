@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 119
+#define RGN_ABI_VERSION 120
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -309,6 +309,27 @@ int rgn_ln_modulate_a8(const void* x, int ldx, void* q, int ldq, float* scale, i
                        const void* shift0, const void* scale0, const void* shift1, const void* scale1, void* stream);
 int rgn_ln_modulate_segs_a8(const void* x, int ldx, void* q, int ldq, float* scale, int M, int d, float eps, int nseg,
                             const int* seg_end_host, const void* const* shift_host, const void* const* scale_host, void* stream);
+
+/* "mx8 rows": activations as OCP MXFP8 (opt-in; no reference counterpart) - the format of GEMM inputs that no row-wise kernel produces
+ * (GELU and attention outputs), where one scale per row would need a pass of its own over the row:
+ *   q [M, K]     OCP e4m3fn bytes, row stride in BYTES, a multiple of 16; q 16-byte aligned;
+ *   s [M, K/32]  E8M0 bytes, value 2^(b - 127), one per 32 consecutive k; row stride in BYTES, a multiple of 4; s 4-byte aligned - every
+ *                K tile of 128 has one aligned dword of scales per row;
+ *   K % 128 == 0.
+ * The quantiser of a block of 32 bf16 values with amax a:  X = 2^(b - 127) is the smallest power of two with a / X <= 448, taken from the
+ * bits of a (exponent field E, mantissa m in [1, 2): b = E - 8, + 1 if m > 1.75), b clamped to [0, 254] - 255, the NaN of E8M0, is
+ * never written; a block of zeros (either sign) gets b = 127;  q = e4m3fn_rne(x / X), an exact quotient, and with this X nothing
+ * saturates; -0 keeps its sign (code 0x80).  Non-finite input is the caller's error and is not detected: a NaN does not enter the amax
+ * and becomes the NaN code 0x7f, a block that holds an infinity gets b = 247 and its infinities become what the hardware convert makes
+ * of them (0x7f or +-448); no other block is affected.  tests/gemm_mx8_model.py is the specification in numpy; every kernel that writes
+ * mx8 rows equals it bit for bit.
+ *
+ * rgn_quantize_rows_mx8: bf16 rows x [M, K] (row stride ldx elements, rows 16-byte aligned) become mx8 rows in one pass, written at
+ * destination columns [col0, col0 + K) of q and scale columns [col0 / 32, (col0 + K) / 32) of s (col0 % 128 == 0, ldq >= col0 + K,
+ * lds >= (col0 + K) / 32): a result can land in some columns of a wider buffer whose other columns another producer fills.  Nothing
+ * outside those columns is written.  One wave per row, plain vector loads and stores, one writer per byte, no atomics; row bands cut
+ * it like rgn_quantize_rows_a8 (a launch per band on the band's rows). */
+int rgn_quantize_rows_mx8(const void* x, int ldx, void* q, int ldq, void* s, int lds, int col0, int M, int K, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Region-Instruction KV-cache write (RegoionEFluxAttnProcessor2_0, inplace.py:717-763,792-794):

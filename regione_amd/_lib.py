@@ -116,6 +116,8 @@ SIGNATURES = {
                            _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "rgn_ln_modulate_segs_a8": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_float, _c_int, C.POINTER(_c_int),
                                 C.POINTER(_c_void_p), C.POINTER(_c_void_p), _c_void_p],
+    # mx8 rows: e4m3fn bytes + one E8M0 scale byte per 32 values (x, ldx, q, ldq, s, lds, col0, M, K, stream)
+    "rgn_quantize_rows_mx8": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p],
     "rgn_qk_norm_rope_store": [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p,
                                _c_void_p, _c_void_p, _c_void_p, _c_float, _c_void_p, _c_void_p, _c_void_p,
                                _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p],

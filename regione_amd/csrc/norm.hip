@@ -359,6 +359,59 @@ __global__ __launch_bounds__(256) void quantize_rows_a8_kernel(const uint16_t* _
     }
 }
 
+// mx8 rows (include/regione_hip.h, "mx8 rows"): one E8M0 scale byte per 32 consecutive values.  With E the exponent field of the block's
+// amax a = m 2^(E-127), m in [1, 2): a / 2^t <= 448 = 1.75 * 2^8 holds from t = E - 135 on if m <= 1.75 and from t = E - 134 on if not, so
+// the byte is b = t + 127 = E - 8 + (mantissa > 0.75), clamped at 0 (amax below 2^-119, the bf16 subnormals included: X = 2^-127, the
+// quotients only get smaller); the upper clamp of the format, 254, is never reached (E <= 254 gives b <= 247; the exponent field 255 of a
+// non-finite amax gives 247 or 248).  A block of zeros gets X = 1.  x / X is the product with 2^(127-b), a normal fp32 (exponent field
+// 254 - b in [6, 254]): exact, except where it falls below 2^-126, far under half the smallest e4m3fn value, which converts to zero.
+__device__ __forceinline__ uint32_t mx8_scale_byte(float amax) {
+    const uint32_t u = __float_as_uint(amax);
+    if (u == 0u) return 127u;
+    const int b = (int)(u >> 23) - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
+    return (uint32_t)(b < 0 ? 0 : b);
+}
+
+// bf16 rows -> mx8 rows (rgn_quantize_rows_mx8): one wave per row, 512 columns per pass - a lane holds 8 values (one 16-byte load, one
+// 8-byte store), four neighbouring lanes a block of 32, sixteen a K tile of 128 whose four scale bytes leave as the tile's one dword.
+// `q` / `s` point at the first destination column of row 0.
+__global__ __launch_bounds__(256) void quantize_rows_mx8_kernel(const uint16_t* __restrict__ x, int ldx, int M, int K,
+                                                                uint8_t* __restrict__ q, int ldq, uint8_t* __restrict__ s, int lds) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;                                        // a whole wave leaves: the shuffles below stay wave-uniform
+    const uint16_t* xr = x + (size_t)row * ldx;
+    uint8_t* qr = q + (size_t)row * ldq;
+    uint8_t* sr = s + (size_t)row * lds;
+    for (int c0 = 0; c0 < K; c0 += 512) {
+        const int c = c0 + lane * 8;
+        const bool on = c < K;                                   // K % 128 == 0: uniform over each group of 16 lanes
+        uint4 t = make_uint4(0u, 0u, 0u, 0u);
+        if (on) t = *(const uint4*)(xr + c);
+        const uint32_t w[4] = {t.x, t.y, t.z, t.w};
+        float amax = a8_amax8(w);
+        amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+        const uint32_t b = mx8_scale_byte(amax);
+        const float inv = __uint_as_float((254u - b) << 23);
+        float y[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { y[2 * k] = __uint_as_float(w[k] << 16) * inv; y[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u) * inv; }
+        int lo = 0, hi = 0;
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], lo, false);
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], hi, false);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
+        const int g = lane & ~15;
+        const uint32_t sw = (uint32_t)__shfl((int)b, g, 64) | ((uint32_t)__shfl((int)b, g + 4, 64) << 8) |
+                            ((uint32_t)__shfl((int)b, g + 8, 64) << 16) | ((uint32_t)__shfl((int)b, g + 12, 64) << 24);
+        if (on) {
+            *(uint2*)(qr + c) = make_uint2((uint32_t)lo, (uint32_t)hi);
+            if ((lane & 15) == 0) *(uint32_t*)(sr + (c >> 5)) = sw;
+        }
+    }
+}
+
 static int launch_ln_rows_a8(const uint16_t* x, int ldx, const A8Out& a8, int M, int d, float eps, const LnSegs& segs, hipStream_t st) {
     if (d % 512 == 0) {          // the same kernel choice as the bf16 rows: the two kernels sum in different orders
         const dim3 grid((M + 3) / 4), blk(256);
@@ -624,6 +677,21 @@ int rgn_quantize_rows_a8(const void* x, int ldx, void* q, int ldq, float* scale,
     else if (nv <= 16) hipLaunchKernelGGL(quantize_rows_a8_kernel<16>, grid, blk, 0, st, xx, ldx, M, K, o);
     else hipLaunchKernelGGL(quantize_rows_a8_kernel<32>, grid, blk, 0, st, xx, ldx, M, K, o);
     return check_launch("quantize_rows_a8_kernel");
+}
+
+int rgn_quantize_rows_mx8(const void* x, int ldx, void* q, int ldq, void* s, int lds, int col0, int M, int K, void* stream) {
+    if (M == 0) return 0;
+    if (!x || M < 0 || K <= 0 || (K % 128) || (ldx % 8) || ldx < K || ((uintptr_t)x & 15))
+        return fail(RGN_E_BADARG, "quantize_rows_mx8: bad argument (K a multiple of 128, x rows 16-byte aligned with ldx >= K)");
+    if (col0 < 0 || (col0 % 128) || col0 > 0x7fffffff - K)
+        return fail(RGN_E_BADARG, "quantize_rows_mx8: the destination column offset must be a non-negative multiple of 128");
+    if (!q || (ldq % 16) || ldq < col0 + K || ((uintptr_t)q & 15))
+        return fail(RGN_E_BADARG, "quantize_rows_mx8: q rows must be 16-byte aligned (ldq in bytes, a multiple of 16, >= col0 + K)");
+    if (!s || (lds % 4) || lds < (col0 + K) / 32 || ((uintptr_t)s & 3))
+        return fail(RGN_E_BADARG, "quantize_rows_mx8: s rows must be 4-byte aligned (lds in bytes, a multiple of 4, >= (col0 + K) / 32)");
+    hipLaunchKernelGGL(quantize_rows_mx8_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, ldx, M, K,
+                       (uint8_t*)q + col0, ldq, (uint8_t*)s + col0 / 32, lds);
+    return check_launch("quantize_rows_mx8_kernel");
 }
 
 static int ln_modulate_segs(const void* x, int ldx, void* out, int ldo, int M, int d, float eps, int nseg, const int* seg_end_host,

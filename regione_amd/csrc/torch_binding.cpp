@@ -382,6 +382,23 @@ std::tuple<Tensor, Tensor> quantize_rows_a8(const Tensor& x) {
     return std::make_tuple(q, scale);
 }
 
+// x bf16 [M, K], K % 128 == 0 -> (q fp8 e4m3fn [M, K], s E8M0 uint8 [M, K / 32]): "mx8 rows" of include/regione_hip.h
+std::tuple<Tensor, Tensor> quantize_rows_mx8(const Tensor& x) {
+    RGN_DEVICE_GUARD(x);
+    bf16_rows("quantize_rows_mx8", {&x});
+    TORCH_CHECK(x.dim() == 2, "quantize_rows_mx8: x [M, K]");
+    const int64_t M = x.size(0), K = x.size(1);
+    TORCH_CHECK(K >= 128 && K % 128 == 0 && K < (int64_t(1) << 31), "quantize_rows_mx8: K = ", K, " must be a positive multiple of 128");
+    TORCH_CHECK(M < (int64_t(1) << 31), "quantize_rows_mx8: too many rows");
+    TORCH_CHECK(M == 0 || (x.stride(0) >= K && x.stride(0) % 8 == 0 && x.stride(0) < (int64_t(1) << 31) && ((uintptr_t)x.data_ptr() & 15) == 0),
+                "quantize_rows_mx8: rows of x must be 16-byte aligned (row stride ", x.stride(0), " elements)");
+    Tensor q = at::empty({M, K}, x.options().dtype(at::kFloat8_e4m3fn));
+    Tensor s = at::empty({M, K / 32}, x.options().dtype(at::kByte));
+    check_rc(rgn_quantize_rows_mx8(ptr(x), (int)x.stride(0), q.data_ptr(), (int)K, s.data_ptr(), (int)(K / 32), 0, (int)M, (int)K, stream_of(x)),
+             "rgn_quantize_rows_mx8");
+    return std::make_tuple(q, s);
+}
+
 void head_rms_norm_(Tensor qkv, const Tensor& wq, const Tensor& wk, int64_t heads, double eps) {
     RGN_DEVICE_GUARD(qkv);
     bf16_rows("head_rms_norm_", {&qkv, &wq, &wk});
@@ -559,6 +576,7 @@ TORCH_LIBRARY(regione_mi, m) {
     m.def("workspace(Tensor like, int kind) -> Tensor");
     // the connector's row kernels (regione_amd/torch_ops.py: ROW_SCHEMAS)
     m.def("quantize_rows_a8(Tensor x) -> (Tensor, Tensor)");
+    m.def("quantize_rows_mx8(Tensor x) -> (Tensor, Tensor)");
     m.def("masked_mean_rows(Tensor x, int n_valid, float scale=1.0) -> Tensor");
     m.def("head_rms_norm_(Tensor(a!) qkv, Tensor wq, Tensor wk, int heads, float eps=1e-6) -> ()");
     m.def("gate_resid_rows_(Tensor p, Tensor gate, Tensor resid, Tensor(a!) out) -> ()");
@@ -585,6 +603,7 @@ TORCH_LIBRARY_IMPL(regione_mi, CUDA, m) {
     m.impl("region_attention", &region_attention);
     m.impl("workspace", &workspace_op);
     m.impl("quantize_rows_a8", &quantize_rows_a8);
+    m.impl("quantize_rows_mx8", &quantize_rows_mx8);
     m.impl("masked_mean_rows", &masked_mean_rows);
     m.impl("head_rms_norm_", &head_rms_norm_);
     m.impl("gate_resid_rows_", &gate_resid_rows_);

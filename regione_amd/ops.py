@@ -260,6 +260,53 @@ def _a8_out(out: torch.Tensor, M: int, K: int, dev, what: str) -> torch.Tensor:
     return sc
 
 
+def mx8_rows(M: int, K: int, device) -> torch.Tensor:
+    """An empty mx8 buffer (include/regione_hip.h, "mx8 rows"): fp8 e4m3fn [M, K] whose E8M0 block scales, uint8 [M, K / 32], travel ON it
+    as `._rgn_mx_scale` - a name of their own, so that no consumer takes them for the fp32 row scales of `._rgn_scale`."""
+    if K <= 0 or K % 128:
+        raise _lib.RegionEHipError(f"mx8 rows: K = {K} must be a positive multiple of 128")
+    q = torch.empty((M, K), dtype=FP8, device=device)
+    q._rgn_mx_scale = torch.empty((M, K // 32), dtype=torch.uint8, device=device)
+    return q
+
+
+def mx8_arows(A: torch.Tensor, lo: Optional[int] = None, hi: Optional[int] = None) -> torch.Tensor:
+    """A[lo:hi] (rows) of an mx8 buffer with its block scales sliced alike (a plain slice loses the attribute): the rows of a row band."""
+    s = getattr(A, "_rgn_mx_scale", None)
+    if s is None:
+        raise _lib.RegionEHipError("mx8_arows: not an mx8 buffer (no `._rgn_mx_scale`; use ops.mx8_rows)")
+    v = A[lo:hi]
+    v._rgn_mx_scale = s[lo:hi]
+    return v
+
+
+def quantize_rows_mx8(x: torch.Tensor, out: Optional[torch.Tensor] = None, col: int = 0) -> torch.Tensor:
+    """bf16 activations [M, K] -> mx8 rows (rgn_quantize_rows_mx8): e4m3fn bytes with one power-of-two scale per 32 consecutive values,
+    the smallest that keeps the block's amax at or below 448 - bit-identical to tests/gemm_mx8_model.py.  `out` (from ops.mx8_rows, at
+    least `col + K` columns wide) receives the rows at columns [col, col + K), `col` a multiple of 128; its other columns stay as they
+    are.  Returns `out` (a new [M, K] buffer when none is given)."""
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or x.stride(1) != 1:
+        raise _lib.RegionEHipError(f"quantize_rows_mx8: x must be bf16 [M, K] with unit column stride (got {x.dtype} {tuple(x.shape)})")
+    M, K = x.shape
+    if K <= 0 or K % 128 or col < 0 or col % 128:
+        raise _lib.RegionEHipError(f"quantize_rows_mx8: K = {K} must be a positive multiple of 128, col = {col} a non-negative one")
+    if out is None:
+        if col:
+            raise _lib.RegionEHipError("quantize_rows_mx8: a column offset needs the `out` buffer it refers to")
+        out = mx8_rows(M, K, x.device)
+    s = getattr(out, "_rgn_mx_scale", None)
+    if out.dtype != FP8 or out.dim() != 2 or out.shape[0] != M or out.shape[1] < col + K or out.stride(1) != 1 or out.device != x.device:
+        raise _lib.RegionEHipError(f"quantize_rows_mx8: out must be fp8 e4m3fn [{M}, >= {col + K}] on {x.device} "
+                                   f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
+    if (s is None or s.dtype != torch.uint8 or s.dim() != 2 or s.shape[0] != M or s.shape[1] * 32 < col + K or s.stride(1) != 1
+            or s.device != x.device):
+        raise _lib.RegionEHipError(f"quantize_rows_mx8: an mx8 out carries its block scales as `._rgn_mx_scale`, uint8 [{M}, >= {(col + K) // 32}], "
+                                   f"on {x.device} (use ops.mx8_rows)")
+    rc = _lib.lib().rgn_quantize_rows_mx8(_p(x), x.stride(0), _p(out), out.stride(0), _p(s), s.stride(0), col, M, K, _stream())
+    _lib.check(rc, "rgn_quantize_rows_mx8")
+    return out
+
+
 def arows(A: torch.Tensor, lo: Optional[int] = None, hi: Optional[int] = None) -> torch.Tensor:
     """A[lo:hi] (rows) of an activation matrix; for fp8 activations the row scales are sliced with it, as wrows does for weights."""
     v = A[lo:hi]

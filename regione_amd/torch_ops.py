@@ -258,6 +258,18 @@ _define("quantize_rows_a8", "(Tensor x) -> (Tensor, Tensor)", _quantize_rows_a8,
         lambda x: (x.new_empty(x.shape, dtype=ops.FP8), x.new_empty((x.shape[0],), dtype=torch.float32)), A8_SCHEMAS, _a8_defined)
 
 
+def _quantize_rows_mx8(x):
+    q = ops.quantize_rows_mx8(x)
+    return q, q._rgn_mx_scale
+
+
+# x bf16 [M, K], K % 128 == 0 -> (fp8 e4m3fn [M, K], E8M0 block scales uint8 [M, K / 32]): "mx8 rows" of include/regione_hip.h; a caller
+# attaches the scales (`q._rgn_mx_scale = s`).  Writing into columns of a wider buffer is ops.quantize_rows_mx8(x, out=, col=).
+_define("quantize_rows_mx8", "(Tensor x) -> (Tensor, Tensor)", _quantize_rows_mx8,
+        lambda x: (x.new_empty(x.shape, dtype=ops.FP8), x.new_empty((x.shape[0], x.shape[1] // 32), dtype=torch.uint8)),
+        A8_SCHEMAS, _a8_defined)
+
+
 # ---- one masked MMDiT block per call (csrc/block.hip) ------------------------------------------------
 BLOCK_SCHEMAS = {}              # listed apart like ROW_SCHEMAS: SCHEMAS stays the region-op surface
 _block_defined = set()

@@ -192,6 +192,27 @@ def bench_a8():
     force({})
 
 
+def bench_mx8():
+    """rgn_quantize_rows_mx8 (bf16 rows -> e4m3fn bytes + one E8M0 scale per 32 values) next to the row-scaled quantiser on the same rows, at
+    the inputs no row-wise kernel produces: FF-down / proj_out / attention out-projection operands, full-step (M = 8704) and region-step
+    (M = 1536) rows.  Alternating legs; bytes moved = 2 read + 1 (+ 1 / 32) written per value."""
+    shapes = [("ff down", 8704, 12288), ("proj_out", 8704, 15360), ("attn out", 8704, 3072),
+              ("R ff down", 1536, 12288), ("R proj_out", 1536, 15360), ("R attn out", 1536, 3072)]
+    for name, M, K in shapes:
+        A = rnd(M, K)
+        AX, A8 = ops.quantize_rows_mx8(A), ops.quantize_rows_a8(A)
+        legs = [("quantize_rows_mx8", lambda: ops.quantize_rows_mx8(A, out=AX), 3 + 1 / 32), ("quantize_rows_a8", lambda: ops.quantize_rows_a8(A, out=A8), 3)]
+        res = {label: [] for label, *_ in legs}
+        for _ in range(3):
+            for label, fn, _b in legs:
+                med, _ = timeit(fn, iters=3, warm=1, inner=10)
+                res[label].append(med)
+        for label, _fn, per in legs:
+            med = sorted(res[label])[1]
+            print(f"mx8 {name:<12} M={M:<6} K={K:<6} {label:<18} {med*1e3:8.1f} us  {M*K*per/med/1e6:7.1f} GB/s")
+        del A, AX, A8
+
+
 def bench_region():
     """The region-partition ops (O(L * 64) bytes -> launch-latency bound; achieved GB/s reported for
     honesty) next to the oracle's CPU time for the same call."""
@@ -268,5 +289,6 @@ if __name__ == "__main__":
     if "region" in which: bench_region()
     if "w8" in which: bench_w8()
     if "a8" in which: bench_a8()
+    if "mx8" in which: bench_mx8()
     if "attn" in which: bench_attn()
     if "gemv" in which: bench_gemv()
