@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 120
+#define RGN_ABI_VERSION 121
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -549,6 +549,36 @@ size_t rgn_lm_decode_attention_workspace_bytes(int Hq, int n);
 int rgn_lm_head_argmax(const void* W, const void* x, int V, int K, void* token_out, float* logits_out, void* workspace,
                        size_t workspace_bytes, void* stream);
 size_t rgn_lm_head_workspace_bytes(int V);
+/* The same decode step for B sequences at once (`generate` over a batch of up to RGN_LM_MAX_BATCH prompts): every weight is streamed ONCE
+ * per step for all of them.  The batch is invariant: row b of each result below is BIT FOR BIT what the one-sequence entry above gives for
+ * row b alone, for every B in 1..8 - the same per-lane fmaf chain in the same k order, the same wave butterfly, the same roundings.  No
+ * atomics, fixed reduction orders, a repeated call is bit-identical.  The row kernels (rgn_rms_norm_rows, rgn_mrope_bf16, rgn_swiglu_bf16,
+ * rgn_text_embed) run at M = B.  Per-sequence lengths are HOST arrays of B ints that travel to the kernel by value: no device read, no upload.
+ *
+ * Y[b, n] = the layer of rgn_lm_gemv_bf16 applied to row b of X, b < B.  X [B, ldx], Y [B, ldy], resid [B, ldr] bf16; strides in elements,
+ * multiples of 8, ldx >= K, ldy >= N, ldr >= N; Y may be resid.  Rows >= B and columns >= N are never written.  A weight vector is loaded
+ * once (non-temporal) and converted once for all rows; x is widened to fp32 once per block and kept in LDS (B x 8 KB). */
+#define RGN_LM_MAX_BATCH 8
+int rgn_lm_gemv_bf16_rows(const void* W, const void* X, int ldx, const void* bias, const void* resid, int ldr, void* Y, int ldy, int B, int N,
+                          int K, void* stream);
+/* The same over fp8 weights: row b bit-identical to rgn_lm_gemv_w8 on X[b] (exact v_cvt_pk_f32_fp8, the scale once on the reduced sum). */
+int rgn_lm_gemv_w8_rows(const void* W8, const float* wscale, const void* X, int ldx, const void* bias, const void* resid, int ldr, void* Y,
+                        int ldy, int B, int N, int K, void* stream);
+/* rgn_lm_head_argmax for B rows of X from one stream of W: token_out[b * token_stride] (int64 elements) = the argmax of row b, the lowest
+ * index on a tie; logits_out != NULL receives fp32 [B, V] with row stride ldl >= V.  The finalize step runs one block per row.
+ * workspace_bytes >= B * rgn_lm_head_workspace_bytes(V). */
+int rgn_lm_head_argmax_rows(const void* W, const void* X, int ldx, int B, int V, int K, void* token_out, int token_stride, float* logits_out,
+                            int ldl, void* workspace, size_t workspace_bytes, void* stream);
+/* Row b of QKV [B, ld] (after rgn_mrope_bf16) into cache b = cache + b * cache_stride (elements; a multiple of 8, >= cap 2 Hkv 128) at row
+ * row0_host[b], 0 <= row0_host[b] < cap <= 4096, bit for bit. */
+int rgn_lm_kv_append_bf16_rows(const void* QKV, int ld, void* cache, size_t cache_stride, int cap, const int* row0_host, int B, int Hq, int Hkv,
+                               void* stream);
+/* B query tokens, query b (row b of Q [B, ldq]: the q columns of its QKV row) against the first n_host[b] rows of cache b; O [B, ldo].
+ * 1 <= n_host[b] <= 4096.  One grid with the batch on its z axis, sized for the longest cache: a block whose 64-key slice lies at or past
+ * n[b] returns before any barrier.  Partials and the merge are per row; row b is bit-identical to rgn_lm_decode_attention_bf16 at n[b], and
+ * cache rows >= n[b] are never read.  workspace_bytes >= B * rgn_lm_decode_attention_workspace_bytes(Hq, max_b n[b]). */
+int rgn_lm_decode_attention_bf16_rows(const void* Q, int ldq, const void* cache, size_t cache_stride, void* O, int ldo, const int* n_host, int B,
+                                      int Hq, int Hkv, float scale, void* workspace, size_t workspace_bytes, void* stream);
 /* Repetition penalty and sampling for that decode (transformers' RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper,
  * TopKLogitsWarper, TopPLogitsWarper and the multinomial draw, in the order of _get_logits_processor).
  *

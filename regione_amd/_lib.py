@@ -161,6 +161,15 @@ SIGNATURES = {
     "rgn_lm_decode_attention_workspace_bytes": [_c_int, _c_int],
     "rgn_lm_head_argmax": [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, C.c_size_t, _c_void_p],
     "rgn_lm_head_workspace_bytes": [_c_int],
+    # the same step for B <= 8 sequences from one stream of the weights; per-sequence lengths are host int arrays
+    "rgn_lm_gemv_bf16_rows": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p],
+    "rgn_lm_gemv_w8_rows": [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int,
+                            _c_void_p],
+    "rgn_lm_head_argmax_rows": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p,
+                                C.c_size_t, _c_void_p],
+    "rgn_lm_kv_append_bf16_rows": [_c_void_p, _c_int, _c_void_p, C.c_size_t, _c_int, C.POINTER(_c_int), _c_int, _c_int, _c_int, _c_void_p],
+    "rgn_lm_decode_attention_bf16_rows": [_c_void_p, _c_int, _c_void_p, C.c_size_t, _c_void_p, _c_int, C.POINTER(_c_int), _c_int, _c_int,
+                                          _c_int, _c_float, _c_void_p, C.c_size_t, _c_void_p],
     "rgn_lm_seen_mark": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p],
     "rgn_lm_pick": [_c_void_p, _c_int, _c_void_p, _c_float, _c_int, _c_float, _c_int, C.c_double, _c_void_p, _c_void_p, _c_void_p,
                     _c_void_p, C.c_size_t, _c_void_p],

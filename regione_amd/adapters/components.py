@@ -217,7 +217,9 @@ def hip_qwen_text_encoder_for(host, dev):
     `pipe._regione_hip_text_weights = "fp8"` before the first call adopts the layers' projection matrices as fp8 e4m3fn with per-channel
     scales (HipQwen25VLTextEncoder(weights="fp8")); absent, the adoption is "bf16"; another value raises ValueError naming the two.
     `pipe._regione_hip_text_sampling = True` before the first call adopts with `sampling=True` (generate honours do_sample, temperature,
-    top_k, top_p and repetition_penalty); absent, it is False; a value that is not a bool raises ValueError."""
+    top_k, top_p and repetition_penalty); absent, it is False; a value that is not a bool raises ValueError.
+    `pipe._regione_hip_text_batch = N` before the first call adopts with `max_batch=N` (generate takes up to N left-padded rows and
+    decodes them from one weight stream); absent, it is 1; a value that is not an int in 1..8 raises ValueError naming the range."""
     if _memo(host, "_regione_hip_text") is False:
         return None
     cached = _memo(host, "_regione_hip_qwen_text")
@@ -229,6 +231,9 @@ def hip_qwen_text_encoder_for(host, dev):
     sampling = host.__dict__.get("_regione_hip_text_sampling", False)
     if not isinstance(sampling, bool):
         raise ValueError(f"pipe._regione_hip_text_sampling = {sampling!r}: True and False are accepted")
+    batch = host.__dict__.get("_regione_hip_text_batch", 1)
+    if isinstance(batch, bool) or not isinstance(batch, int) or not 1 <= batch <= 8:
+        raise ValueError(f"pipe._regione_hip_text_batch = {batch!r}: an int in 1..8 is accepted")
     mod = getattr(host, "text_encoder", None)
     enc = None
     if type(mod).__name__ == "Qwen2_5_VLForConditionalGeneration" and getattr(mod, "config", None) is not None:
@@ -237,7 +242,8 @@ def hip_qwen_text_encoder_for(host, dev):
         if why is None and any("lora" in n.lower() for n, _ in mod.named_modules()):
             why = "PEFT / LoRA layers in the module"
         enc = _adopt_or_keep("text_encoder", why, stacklevel=3,
-                             make=lambda: QT.HipQwen25VLTextEncoder(mod, dev, weights=fmt, **({"sampling": True} if sampling else {})))
+                             make=lambda: QT.HipQwen25VLTextEncoder(mod, dev, weights=fmt, **({"sampling": True} if sampling else {}),
+                                                                    **({"max_batch": batch} if batch > 1 else {})))
         if enc is not None and _memo(host, "_regione_hip_vision") is not False:
             from .. import qwen_vision as QV
             tower = _adopt_or_keep("vision tower", QV.vision_refusal(mod.config), lambda: QV.HipQwen25VLVisionTower(mod, dev), stacklevel=3)

@@ -14,6 +14,11 @@
 //   lm_seen_mark_kernel         seen[id] = 1 for the prompt ids: the byte map the repetition penalty reads
 //   lm_pick_kernel              one block between lm_head and the next embedding: repetition penalty, temperature, top-k, top-p and the
 //                               pick (argmax, or the inverse CDF at a uniform read from device memory) over the fp32 logits in L2
+// and the same step for a batch of B <= 8 sequences, every weight streamed ONCE for all of them, row b bit-identical to the kernels above:
+//   lm_gemv_rows_kernel         the three one-row products (bf16, fp8, lm_head with per-block maxima) for B rows of x: a weight vector is
+//                               loaded and converted once, x sits in LDS as fp32, one accumulator per (weight row, x row)
+//   lm_head_finalize_rows_kernel, lm_kv_append_rows_kernel, lm_decode_attention_rows_kernel, lm_decode_merge_rows_kernel
+//                               the batch on a grid axis; per-sequence cache lengths travel by value (no device read, no upload)
 // No atomics; every reduction has a fixed order (lanes: the butterfly of wave_sum; k, keys and slices: ascending), so a repeated call is
 // bit-identical.
 #include <math.h>
@@ -153,8 +158,8 @@ __global__ __launch_bounds__(256) void lm_gemv_w8_kernel(const uint8_t* __restri
     }
 }
 
-__global__ __launch_bounds__(1024) void lm_head_finalize_kernel(const float* __restrict__ part_v, const int* __restrict__ part_i, int nparts,
-                                                                int64_t* __restrict__ out) {
+__device__ __forceinline__ void head_finalize_block(const float* __restrict__ part_v, const int* __restrict__ part_i, int nparts,
+                                                    int64_t* __restrict__ out) {
     __shared__ float sv[1024];
     __shared__ int si[1024];
     const int tid = threadIdx.x;
@@ -181,6 +186,11 @@ __global__ __launch_bounds__(1024) void lm_head_finalize_kernel(const float* __r
     if (tid == 0) out[0] = si[0] == 0x7fffffff ? 0 : (int64_t)si[0];
 }
 
+__global__ __launch_bounds__(1024) void lm_head_finalize_kernel(const float* __restrict__ part_v, const int* __restrict__ part_i, int nparts,
+                                                                int64_t* __restrict__ out) {
+    head_finalize_block(part_v, part_i, nparts, out);
+}
+
 // ---- cache[row0 + i, :] = QKV[i, Hq 128 : (Hq + 2 Hkv) 128]: one 16-byte vector per thread and pass --------------------------------
 __global__ __launch_bounds__(256) void lm_kv_append_kernel(const uint16_t* __restrict__ QKV, int ld, int col0, uint16_t* __restrict__ cache,
                                                            int row0, int L, int width) {
@@ -201,8 +211,8 @@ __global__ __launch_bounds__(256) void lm_kv_append_kernel(const uint16_t* __res
 //   P V     thread = (channels 2 lane, 2 lane + 1; keys 16 wave .. 16 wave + 15 in ascending order), the four waves' sums added in wave
 //           order through LDS
 // Rows >= n are not loaded: their score is -inf, their p and v are 0.
-__global__ __launch_bounds__(256) void lm_decode_attention_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ cache, int n,
-                                                                  int Hq, int Hkv, float scale, float* __restrict__ part, int nslices) {
+__device__ __forceinline__ void decode_attention_block(const uint16_t* __restrict__ q, const uint16_t* __restrict__ cache, int n, int Hq,
+                                                       int Hkv, float scale, float* __restrict__ part, int nslices) {
     __shared__ __attribute__((aligned(16))) float ql[DEC_MAX_GROUP * 128];
     __shared__ float sl[DEC_MAX_GROUP * DEC_SLICE];                              // scores, then p
     __shared__ __attribute__((aligned(8))) float ol[3 * DEC_MAX_GROUP * 128];    // the P V sums of waves 1..3
@@ -317,8 +327,13 @@ __global__ __launch_bounds__(256) void lm_decode_attention_kernel(const uint16_t
     }
 }
 
+__global__ __launch_bounds__(256) void lm_decode_attention_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ cache, int n,
+                                                                  int Hq, int Hkv, float scale, float* __restrict__ part, int nslices) {
+    decode_attention_block(q, cache, n, Hq, Hkv, scale, part, nslices);
+}
+
 // Block = one query head, thread = one output channel: M = max of the slices' maxima, then l and o folded in slice order.
-__global__ __launch_bounds__(128) void lm_decode_merge_kernel(const float* __restrict__ part, int nslices, uint16_t* __restrict__ O) {
+__device__ __forceinline__ void decode_merge_head(const float* __restrict__ part, int nslices, uint16_t* __restrict__ O) {
     const int h = blockIdx.x, d = threadIdx.x;
     const float* pr = part + (size_t)h * nslices * DEC_PART;
     float M = -INFINITY;
@@ -332,6 +347,187 @@ __global__ __launch_bounds__(128) void lm_decode_merge_kernel(const float* __res
         o = fmaf(pr[(size_t)s * DEC_PART + 2 + d], a, o);
     }
     O[(size_t)h * 128 + d] = f2bf(o / l);
+}
+
+__global__ __launch_bounds__(128) void lm_decode_merge_kernel(const float* __restrict__ part, int nslices, uint16_t* __restrict__ O) {
+    decode_merge_head(part, nslices, O);
+}
+
+// ---- the same step for B <= 8 sequences from ONE stream of the weights (generate over a batch) ------------------------------------------
+// Row b of every result is bit for bit what the one-row kernel above gives for row b alone: a lane owns the same k (8 per 512-wide step
+// of a bf16 row, 16 per 1024-wide step of an fp8 row) in the same ascending order, adds them with the same fmaf chain into ONE fp32
+// accumulator per (weight row, x row), and the 64 lanes are folded by the same wave_sum butterfly; the round structure of the one-row
+// kernels (how many loads are in flight) is not part of that order, so it is free here.
+//   block = 4 waves x ROWS_R weight rows; a weight vector is loaded once (non-temporal, 16 bytes) and converted once for all B rows
+//   x     the B rows of a chunk of k (1024 wide for bf16 weights, 2048 for fp8) are widened to fp32 ONCE per block and kept in LDS
+//         (B x 4 KB, B x 8 KB), laid out in planes of
+//         float4 so that the lanes of a wave read consecutive 16-byte slots (ds_read_b128 without bank conflicts): both conversions are
+//         exact, so hoisting them changes no bit, and the FMA phase issues one v_fma per product and nothing else
+// The loads of the next chunk (x, then W) are issued before the products of the current one.
+struct LmRows { int v[RGN_LM_MAX_BATCH]; };                                      // one int per sequence, passed to a kernel by value
+constexpr int ROWS_R = 2;
+template <bool W8> constexpr int rows_kc() { return W8 ? 2048 : 1024; }         // k per chunk: two steps of either lane layout
+
+template <int B, bool W8, bool ARGMAX>
+__global__ __launch_bounds__(256) void lm_gemv_rows_kernel(const uint8_t* __restrict__ W, const float* __restrict__ wscale,
+                                                           const uint16_t* __restrict__ X, int ldx, const uint16_t* __restrict__ bias,
+                                                           const uint16_t* resid, int ldr, uint16_t* Y, int ldy, float* __restrict__ logits,
+                                                           int ldl, float* __restrict__ part_v, int* __restrict__ part_i, int nparts, int N, int K) {
+    constexpr int VPL = W8 ? 16 : 8, ES = W8 ? 1 : 2, KC = rows_kc<W8>();        // k per lane and step; bytes per weight; k per chunk
+    constexpr int U = KC / (64 * VPL), PL = VPL / 4, SL = 64 * U;                // steps per chunk; float4 planes; slots per plane
+    constexpr int VR = KC / 8, RPP = 256 / VR, NP = (B + RPP - 1) / RPP;         // staging: 16-byte vectors per row, rows per pass, passes
+    extern __shared__ __attribute__((aligned(16))) uint8_t rows_lds[];
+    float4* xs = (float4*)rows_lds;                                              // [B][PL][SL]
+    __shared__ float bv[4 * ROWS_R * RGN_LM_MAX_BATCH];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n0 = (blockIdx.x * 4 + wave) * ROWS_R;
+    const uint8_t* wr[ROWS_R];
+    float acc[ROWS_R][B];
+#pragma unroll
+    for (int r = 0; r < ROWS_R; ++r) {
+        wr[r] = W + (size_t)(n0 + r < N ? n0 + r : N - 1) * (size_t)K * ES;      // a row past N re-reads row N - 1 and writes nothing
+#pragma unroll
+        for (int b = 0; b < B; ++b) acc[r][b] = 0.f;
+    }
+    const int sk = (tid % VR) * 8, sb = tid / VR;                                // staging: 8 values at k = sk of rows sb, sb + RPP, ...
+    const int sslot = sk / VPL, spl = (sk % VPL) / 4;
+    uint4 xv[NP];
+    u32x4 wv[ROWS_R][U];
+    // the loads of one chunk: x first (the counter of outstanding loads is in order: waiting for x leaves W in flight)
+    auto issue = [&](int kb) {
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            const int b = sb + j * RPP;
+            xv[j] = b < B && kb + sk < K ? *(const uint4*)(X + (size_t)b * ldx + kb + sk) : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int k = kb + (u * 64 + lane) * VPL;
+#pragma unroll
+            for (int r = 0; r < ROWS_R; ++r)                                     // a lane past K loads nothing and adds 0
+                wv[r][u] = k < K ? __builtin_nontemporal_load((const u32x4*)(wr[r] + (size_t)k * ES)) : u32x4{0u, 0u, 0u, 0u};
+        }
+    };
+    issue(0);
+    for (int kb = 0; kb < K; kb += KC) {
+        if (kb) __syncthreads();                                                 // every wave is done with the previous chunk
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            const int b = sb + j * RPP;
+            if (b < B) {
+                const uint32_t a[4] = {xv[j].x, xv[j].y, xv[j].z, xv[j].w};
+                float4* dst = xs + (b * PL + spl) * SL + sslot;
+                dst[0] = make_float4(__uint_as_float(a[0] << 16), __uint_as_float(a[0] & 0xffff0000u), __uint_as_float(a[1] << 16),
+                                     __uint_as_float(a[1] & 0xffff0000u));
+                dst[SL] = make_float4(__uint_as_float(a[2] << 16), __uint_as_float(a[2] & 0xffff0000u), __uint_as_float(a[3] << 16),
+                                      __uint_as_float(a[3] & 0xffff0000u));
+            }
+        }
+        __syncthreads();
+        u32x4 wc[ROWS_R][U];                                                     // this chunk's weights; the next chunk's loads go out
+#pragma unroll                                                                   // before its products, so they fly during them
+        for (int r = 0; r < ROWS_R; ++r)
+#pragma unroll
+            for (int u = 0; u < U; ++u) wc[r][u] = wv[r][u];
+        if (kb + KC < K) issue(kb + KC);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float wf[ROWS_R][VPL];
+#pragma unroll
+            for (int r = 0; r < ROWS_R; ++r) {
+                const uint32_t a[4] = {wc[r][u].x, wc[r][u].y, wc[r][u].z, wc[r][u].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if constexpr (W8) {
+                        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)a[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)a[e], true);
+                        wf[r][4 * e] = lo[0]; wf[r][4 * e + 1] = lo[1]; wf[r][4 * e + 2] = hi[0]; wf[r][4 * e + 3] = hi[1];
+                    } else {
+                        wf[r][2 * e] = __uint_as_float(a[e] << 16);
+                        wf[r][2 * e + 1] = __uint_as_float(a[e] & 0xffff0000u);
+                    }
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < B; ++b) {
+#pragma unroll
+                for (int p = 0; p < PL; ++p) {
+                    const float4 x4 = xs[(b * PL + p) * SL + u * 64 + lane];
+#pragma unroll
+                    for (int r = 0; r < ROWS_R; ++r) {                           // ascending k: the chain of dot8 / dot16_w8
+                        float a = acc[r][b];
+                        a = fmaf(wf[r][4 * p], x4.x, a);
+                        a = fmaf(wf[r][4 * p + 1], x4.y, a);
+                        a = fmaf(wf[r][4 * p + 2], x4.z, a);
+                        a = fmaf(wf[r][4 * p + 3], x4.w, a);
+                        acc[r][b] = a;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < ROWS_R; ++r) {
+        const int n = n0 + r;
+#pragma unroll
+        for (int b = 0; b < B; ++b) {
+            const float s = wave_sum(acc[r][b]);
+            if (lane != 0) continue;
+            if constexpr (ARGMAX) {
+                bv[(wave * ROWS_R + r) * B + b] = s;
+                if (logits && n < N) logits[(size_t)b * ldl + n] = s;
+            } else if (n < N) {
+                const float bs = bias ? bf2f(bias[n]) : 0.f;
+                float v;
+                if constexpr (W8) v = fmaf(s, wscale[n], bs);                    // the scale once, on the reduced sum
+                else v = s + bs;
+                Y[(size_t)b * ldy + n] = resid ? f2bf(rbf(v) + bf2f(resid[(size_t)b * ldr + n])) : f2bf(v);   // two roundings
+            }
+        }
+    }
+    if constexpr (ARGMAX) {
+        __syncthreads();
+        if (tid < B) {
+            const int base = blockIdx.x * 4 * ROWS_R;
+            float best = bv[tid];                                                // row `base` exists in every block
+            int at = base;
+            for (int i = 1; i < 4 * ROWS_R; ++i)                                 // ascending index, strict >: the first maximum
+                if (base + i < N && bv[i * B + tid] > best) { best = bv[i * B + tid]; at = base + i; }
+            part_v[(size_t)tid * nparts + blockIdx.x] = best;
+            part_i[(size_t)tid * nparts + blockIdx.x] = at;
+        }
+    }
+}
+
+// One block per sequence folds that sequence's per-block maxima, as lm_head_finalize_kernel does for one.
+__global__ __launch_bounds__(1024) void lm_head_finalize_rows_kernel(const float* __restrict__ part_v, const int* __restrict__ part_i, int nparts,
+                                                                     int64_t* __restrict__ out, int out_stride) {
+    const size_t b = blockIdx.x;
+    head_finalize_block(part_v + b * nparts, part_i + b * nparts, nparts, out + b * out_stride);
+}
+
+// Row b of QKV [B, ld] into cache b (base + b cache_stride) at row row0[b]: one 16-byte vector per thread.
+__global__ __launch_bounds__(256) void lm_kv_append_rows_kernel(const uint16_t* __restrict__ QKV, int ld, int col0, uint16_t* __restrict__ cache,
+                                                                size_t cache_stride, LmRows row0, int width) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i < width / 8)
+        *(uint4*)(cache + b * cache_stride + (size_t)row0.v[b] * width + i * 8) = *(const uint4*)(QKV + (size_t)b * ld + col0 + i * 8);
+}
+
+// Grid = (slices of the LONGEST cache, KV heads, sequences).  A block whose slice starts at or past n[b] has nothing to do and returns
+// before the first barrier (n[b] and the slice are the same for every thread of the block); the others are lm_decode_attention_kernel.
+__global__ __launch_bounds__(256) void lm_decode_attention_rows_kernel(const uint16_t* __restrict__ Q, int ldq, const uint16_t* __restrict__ cache,
+                                                                       size_t cache_stride, LmRows nb, int Hq, int Hkv, float scale,
+                                                                       float* __restrict__ part, size_t part_stride) {
+    const int b = blockIdx.z, n = nb.v[b];
+    if ((int)blockIdx.x * DEC_SLICE >= n) return;
+    decode_attention_block(Q + (size_t)b * ldq, cache + b * cache_stride, n, Hq, Hkv, scale, part + b * part_stride,
+                           (n + DEC_SLICE - 1) / DEC_SLICE);
+}
+
+__global__ __launch_bounds__(128) void lm_decode_merge_rows_kernel(const float* __restrict__ part, size_t part_stride, LmRows nb,
+                                                                   uint16_t* __restrict__ O, int ldo) {
+    const int b = blockIdx.y;
+    decode_merge_head(part + b * part_stride, (nb.v[b] + DEC_SLICE - 1) / DEC_SLICE, O + (size_t)b * ldo);
 }
 
 // ---- repetition penalty and sampling: the pick between lm_head and the next embedding -------------------------------------------------
@@ -597,6 +793,17 @@ __global__ __launch_bounds__(PICK_T) void lm_pick_kernel(const float* __restrict
 
 using namespace rgn;
 
+template <bool W8, bool ARGMAX, typename... Args>
+static void launch_gemv_rows(int B, int N, hipStream_t st, Args... args) {
+    const dim3 grid((N + 4 * ROWS_R - 1) / (4 * ROWS_R)), block(256);
+    const size_t lds = (size_t)B * rows_kc<W8>() * sizeof(float);
+    switch (B) {
+#define RGN_ROWS_CASE(b) case b: hipLaunchKernelGGL((lm_gemv_rows_kernel<b, W8, ARGMAX>), grid, block, lds, st, args...); break;
+        RGN_ROWS_CASE(1) RGN_ROWS_CASE(2) RGN_ROWS_CASE(3) RGN_ROWS_CASE(4) RGN_ROWS_CASE(5) RGN_ROWS_CASE(6) RGN_ROWS_CASE(7) RGN_ROWS_CASE(8)
+#undef RGN_ROWS_CASE
+    }
+}
+
 extern "C" {
 
 static inline bool dal16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
@@ -681,6 +888,111 @@ int rgn_lm_decode_attention_bf16(const void* q, const void* cache, void* O, int 
                        (float*)workspace, ns);
     hipLaunchKernelGGL(lm_decode_merge_kernel, dim3(Hq), dim3(128), 0, st, (const float*)workspace, ns, (uint16_t*)O);
     return check_launch("lm_decode_attention");
+}
+
+// ---- the entries over B <= RGN_LM_MAX_BATCH sequences -----------------------------------------------------------------------------------
+static inline bool batch_ok(int B) { return B >= 1 && B <= RGN_LM_MAX_BATCH; }
+
+int rgn_lm_gemv_bf16_rows(const void* W, const void* X, int ldx, const void* bias, const void* resid, int ldr, void* Y, int ldy, int B, int N,
+                          int K, void* stream) {
+    if (!W || !X || !Y || N < 1 || K < 64) return fail(RGN_E_BADARG, "lm_gemv_rows: bad argument (W, X, Y non-null; N >= 1; K >= 64)");
+    if (!batch_ok(B)) return fail(RGN_E_BADARG, "lm_gemv_rows: B outside [1, 8]");
+    if (K % 64) return fail(RGN_E_BADARG, "lm_gemv_rows: K must be a multiple of 64");
+    if (ldx % 8 || ldy % 8 || ldx < K || ldy < N || (resid && (ldr % 8 || ldr < N)))
+        return fail(RGN_E_BADARG, "lm_gemv_rows: strides must be multiples of 8, ldx >= K, ldy >= N, ldr >= N");
+    if (!dal16(W) || !dal16(X)) return fail(RGN_E_BADARG, "lm_gemv_rows: W and X must be 16-byte aligned");
+    if (((uintptr_t)Y | (uintptr_t)bias | (uintptr_t)resid) & 1u) return fail(RGN_E_BADARG, "lm_gemv_rows: Y, bias and resid must be 2-byte aligned");
+    launch_gemv_rows<false, false>(B, N, (hipStream_t)stream, (const uint8_t*)W, (const float*)nullptr, (const uint16_t*)X, ldx,
+                                   (const uint16_t*)bias, (const uint16_t*)resid, ldr, (uint16_t*)Y, ldy, (float*)nullptr, 0, (float*)nullptr,
+                                   (int*)nullptr, 0, N, K);
+    return check_launch("lm_gemv_rows_kernel");
+}
+
+int rgn_lm_gemv_w8_rows(const void* W8, const float* wscale, const void* X, int ldx, const void* bias, const void* resid, int ldr, void* Y,
+                        int ldy, int B, int N, int K, void* stream) {
+    if (!W8 || !wscale || !X || !Y || N < 1 || K < 64)
+        return fail(RGN_E_BADARG, "lm_gemv_w8_rows: bad argument (W8, wscale, X, Y non-null; N >= 1; K >= 64)");
+    if (!batch_ok(B)) return fail(RGN_E_BADARG, "lm_gemv_w8_rows: B outside [1, 8]");
+    if (K % 16) return fail(RGN_E_BADARG, "lm_gemv_w8_rows: K must be a multiple of 16");
+    if (ldx % 8 || ldy % 8 || ldx < K || ldy < N || (resid && (ldr % 8 || ldr < N)))
+        return fail(RGN_E_BADARG, "lm_gemv_w8_rows: strides must be multiples of 8, ldx >= K, ldy >= N, ldr >= N");
+    if (!dal16(W8) || !dal16(wscale) || !dal16(X) || !dal16(Y))
+        return fail(RGN_E_BADARG, "lm_gemv_w8_rows: W8, wscale, X and Y must be 16-byte aligned");
+    if (((uintptr_t)bias | (uintptr_t)resid) & 1u) return fail(RGN_E_BADARG, "lm_gemv_w8_rows: bias and resid must be 2-byte aligned");
+    launch_gemv_rows<true, false>(B, N, (hipStream_t)stream, (const uint8_t*)W8, wscale, (const uint16_t*)X, ldx, (const uint16_t*)bias,
+                                  (const uint16_t*)resid, ldr, (uint16_t*)Y, ldy, (float*)nullptr, 0, (float*)nullptr, (int*)nullptr, 0, N, K);
+    return check_launch("lm_gemv_rows_kernel");
+}
+
+int rgn_lm_head_argmax_rows(const void* W, const void* X, int ldx, int B, int V, int K, void* token_out, int token_stride, float* logits_out,
+                            int ldl, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!W || !X || !token_out || !workspace || V < 1 || K < 64)
+        return fail(RGN_E_BADARG, "lm_head_argmax_rows: bad argument (W, X, token_out, workspace non-null; V >= 1; K >= 64)");
+    if (!batch_ok(B)) return fail(RGN_E_BADARG, "lm_head_argmax_rows: B outside [1, 8]");
+    if (K % 64) return fail(RGN_E_BADARG, "lm_head_argmax_rows: K must be a multiple of 64");
+    if (ldx % 8 || ldx < K || token_stride < 1 || (logits_out && ldl < V))
+        return fail(RGN_E_BADARG, "lm_head_argmax_rows: ldx must be a multiple of 8 and >= K, token_stride >= 1, ldl >= V");
+    if (!dal16(W) || !dal16(X)) return fail(RGN_E_BADARG, "lm_head_argmax_rows: W and X must be 16-byte aligned");
+    if (((uintptr_t)token_out & 7u) || ((uintptr_t)logits_out & 3u) || ((uintptr_t)workspace & 3u))
+        return fail(RGN_E_BADARG, "lm_head_argmax_rows: token_out must be 8-byte, logits_out and workspace 4-byte aligned");
+    if (workspace_bytes < (size_t)B * rgn_lm_head_workspace_bytes(V))
+        return fail(RGN_E_BADARG, "lm_head_argmax_rows: workspace smaller than B rgn_lm_head_workspace_bytes(V)");
+    const int np = (V + 4 * ROWS_R - 1) / (4 * ROWS_R);
+    float* pv = (float*)workspace;
+    int* pi = (int*)(pv + (size_t)B * np);
+    const hipStream_t st = (hipStream_t)stream;
+    launch_gemv_rows<false, true>(B, V, st, (const uint8_t*)W, (const float*)nullptr, (const uint16_t*)X, ldx, (const uint16_t*)nullptr,
+                                  (const uint16_t*)nullptr, 0, (uint16_t*)nullptr, 0, logits_out, ldl, pv, pi, np, V, K);
+    hipLaunchKernelGGL(lm_head_finalize_rows_kernel, dim3(B), dim3(1024), 0, st, (const float*)pv, (const int*)pi, np, (int64_t*)token_out,
+                       token_stride);
+    return check_launch("lm_head_argmax_rows");
+}
+
+int rgn_lm_kv_append_bf16_rows(const void* QKV, int ld, void* cache, size_t cache_stride, int cap, const int* row0_host, int B, int Hq, int Hkv,
+                               void* stream) {
+    if (!QKV || !cache || !row0_host || Hq < 1 || Hkv < 1 || Hq > 1024 || Hkv > 1024 || ld < (Hq + 2 * Hkv) * 128 || ld % 8)
+        return fail(RGN_E_BADARG, "lm_kv_append_rows: bad argument (QKV, cache, row0 non-null; 1 <= Hq, Hkv <= 1024; ld >= (Hq + 2 Hkv) 128, a multiple of 8)");
+    if (!batch_ok(B)) return fail(RGN_E_BADARG, "lm_kv_append_rows: B outside [1, 8]");
+    const int width = 2 * Hkv * 128;
+    if (cap < 1 || cap > DEC_MAX_N || cache_stride % 8 || cache_stride < (size_t)cap * width)
+        return fail(RGN_E_BADARG, "lm_kv_append_rows: caches of 1 <= cap <= 4096 rows, cache_stride >= cap 2 Hkv 128 elements, a multiple of 8");
+    LmRows r{};
+    for (int b = 0; b < B; ++b) {
+        if (row0_host[b] < 0 || row0_host[b] >= cap) return fail(RGN_E_BADARG, "lm_kv_append_rows: row0[b] outside [0, cap)");
+        r.v[b] = row0_host[b];
+    }
+    if (!dal16(QKV) || !dal16(cache)) return fail(RGN_E_BADARG, "lm_kv_append_rows: QKV and cache must be 16-byte aligned");
+    hipLaunchKernelGGL(lm_kv_append_rows_kernel, dim3((width / 8 + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)QKV, ld,
+                       Hq * 128, (uint16_t*)cache, cache_stride, r, width);
+    return check_launch("lm_kv_append_rows_kernel");
+}
+
+int rgn_lm_decode_attention_bf16_rows(const void* Q, int ldq, const void* cache, size_t cache_stride, void* O, int ldo, const int* n_host, int B,
+                                      int Hq, int Hkv, float scale, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!Q || !cache || !O || !n_host || !workspace || Hkv < 1 || Hq < Hkv || Hq > 1024 || !(scale > 0.f) || !(scale < INFINITY))
+        return fail(RGN_E_BADARG, "lm_decode_attention_rows: bad argument (Q, cache, O, n, workspace non-null; 1 <= Hkv <= Hq <= 1024; 0 < scale < inf)");
+    if (Hq % Hkv || Hq / Hkv > DEC_MAX_GROUP) return fail(RGN_E_BADARG, "lm_decode_attention_rows: Hq % Hkv != 0 or Hq / Hkv > 8");
+    if (!batch_ok(B)) return fail(RGN_E_BADARG, "lm_decode_attention_rows: B outside [1, 8]");
+    LmRows nb{};
+    int nmax = 0;
+    for (int b = 0; b < B; ++b) {
+        if (n_host[b] < 1 || n_host[b] > DEC_MAX_N) return fail(RGN_E_BADARG, "lm_decode_attention_rows: n[b] outside [1, 4096]");
+        nb.v[b] = n_host[b];
+        nmax = n_host[b] > nmax ? n_host[b] : nmax;
+    }
+    if (ldq % 8 || ldo % 8 || ldq < Hq * 128 || ldo < Hq * 128 || cache_stride % 8 || cache_stride < (size_t)nmax * 2 * Hkv * 128)
+        return fail(RGN_E_BADARG, "lm_decode_attention_rows: strides must be multiples of 8, ldq and ldo >= Hq 128, cache_stride >= max n 2 Hkv 128");
+    if (!dal16(Q) || !dal16(cache) || !dal16(O) || !dal16(workspace))
+        return fail(RGN_E_BADARG, "lm_decode_attention_rows: Q, cache, O and workspace must be 16-byte aligned");
+    const size_t one = rgn_lm_decode_attention_workspace_bytes(Hq, nmax);
+    if (workspace_bytes < (size_t)B * one)
+        return fail(RGN_E_BADARG, "lm_decode_attention_rows: workspace smaller than B rgn_lm_decode_attention_workspace_bytes(Hq, max n)");
+    const int ns = (nmax + DEC_SLICE - 1) / DEC_SLICE;
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(lm_decode_attention_rows_kernel, dim3(ns, Hkv, B), dim3(256), 0, st, (const uint16_t*)Q, ldq, (const uint16_t*)cache,
+                       cache_stride, nb, Hq, Hkv, scale, (float*)workspace, one / sizeof(float));
+    hipLaunchKernelGGL(lm_decode_merge_rows_kernel, dim3(Hq, B), dim3(128), 0, st, (const float*)workspace, one / sizeof(float), nb, (uint16_t*)O, ldo);
+    return check_launch("lm_decode_attention_rows");
 }
 
 int rgn_lm_seen_mark(const void* ids, int n, void* seen, int V, void* stream) {

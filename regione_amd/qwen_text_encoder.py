@@ -40,6 +40,13 @@ a byte map of the ids so far, temperature, top-k, top-p, argmax or the inverse C
 the loop), which overwrites the id slot: still no token visits the host inside a step.  The uniforms come from `generator=` /
 `uniforms=`, not from torch.multinomial: a seed gives transformers' distribution, not transformers' tokens.
 
+`max_batch=N` (opt-in, 1 <= N <= 8; the default 1 refuses what it refused before) lets `generate` take `input_ids [B, L]` with B <= N
+left-padded rows, as transformers' batched greedy search does: rows prefill one after another over their valid tokens into their own
+caches, then every step decodes all B rows from ONE stream of the weights (the `_rows` entries of csrc/decode.hip).  The batch is
+invariant: row b's tokens and fp32 logits are bit for bit those of the B = 1 call on row b's unpadded prompt.  A row is finished after
+its first EOS and holds `pad_token_id` from then on (`assemble_sequences`); B = 1 under such an adoption takes the one-row launches.
+Sampling over a batch is refused (rgn_lm_pick is one sequence).  Not measured: real checkpoints.
+
 There is no eager fallback inside: what the kernels do not implement raises RegionEHipError before any launch, and the adapter
 (regione_amd.adapters, components.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
 only; every call returns freshly allocated outputs.
@@ -233,6 +240,84 @@ def image_rows(input_ids: torch.Tensor, lengths, image_token_id: int, n_embeds: 
     return rows
 
 
+# ---- generate over a batch (`max_batch=`): the host rules of transformers' greedy search for several rows -----------------------------
+MAX_BATCH = 8                                                                    # RGN_LM_MAX_BATCH of include/regione_hip.h
+
+
+def left_valid_lengths(attention_mask: Optional[torch.Tensor], B: int, L: int, what: str = "HipQwen25VLTextEncoder"):
+    """Valid length per row of a [B, L] mask that is a run of zeros followed by a run of ones (left padding, the decoder-only convention
+    of a batched generate), or all ones; right padding, holes and an empty row are refused by name."""
+    if attention_mask is None:
+        return [L] * B
+    m = attention_mask.detach().cpu() if isinstance(attention_mask, torch.Tensor) else None
+    if m is None or tuple(m.shape) != (B, L):
+        _refuse(what, f"attention_mask of shape {tuple(getattr(attention_mask, 'shape', ()))} for input_ids [{B}, {L}]")
+    m = m != 0
+    n = m.sum(dim=1)
+    if int(n.min()) < 1:
+        _refuse(what, "attention_mask with an empty row")
+    if not torch.equal(m, torch.arange(L)[None, :] >= (L - n)[:, None]):
+        if torch.equal(m, torch.arange(L)[None, :] < n[:, None]):
+            _refuse(what, "attention_mask with right padding: a batched generate takes left padding (zeros, then ones), as transformers' "
+                          "decoder-only generate does")
+        _refuse(what, "attention_mask with holes: every row must be a run of zeros followed by a run of ones (left padding)")
+    return [int(v) for v in n]
+
+
+def image_rows_left(input_ids: torch.Tensor, lengths, image_token_id: int, n_embeds: int, what: str = "HipQwen25VLTextEncoder"):
+    """`image_rows` for left-padded rows: per batch row, the positions of `image_token_id` counted from the row's FIRST VALID token (the
+    row the prefill sees).  Embedding rows are assigned in row order, as transformers' masked scatter does; the placeholder count over
+    the batch must equal the embedding rows."""
+    ids = input_ids.detach().cpu()
+    L = ids.shape[1]
+    hit = ids == image_token_id
+    total = int(hit.sum())
+    if total != n_embeds:
+        raise ValueError(f"Image features and image tokens do not match, tokens: {total}, features: {n_embeds}")
+    rows = []
+    for b, n in enumerate(lengths):
+        if bool(hit[b, :L - n].any()):
+            _refuse(what, "image tokens in the padded part of a row")
+        rows.append(torch.nonzero(hit[b, L - n:]).flatten())
+    return rows
+
+
+def resolve_pad_token_id(pad_token_id, generation_config, eos):
+    """The id that fills a finished row: the argument, else generation_config.pad_token_id, else the first EOS id (transformers'
+    fallback, taken without its warning); None with no EOS at all - then no row ever finishes and nothing is padded."""
+    if pad_token_id is None:
+        pad_token_id = getattr(generation_config, "pad_token_id", None)
+    if isinstance(pad_token_id, torch.Tensor):
+        pad_token_id = int(pad_token_id.flatten()[0])
+    if pad_token_id is None and eos:
+        pad_token_id = eos[0]
+    return None if pad_token_id is None else int(pad_token_id)
+
+
+def eos_cuts(new_ids: torch.Tensor, eos):
+    """Per row of time-major new ids [k, B] (CPU): the number of new tokens up to and including the row's first EOS, None without one."""
+    k, B = new_ids.shape
+    hit = torch.zeros(k, B, dtype=torch.bool)
+    for e in eos:
+        hit |= new_ids == e
+    return [int(torch.nonzero(hit[:, b])[0]) + 1 if bool(hit[:, b].any()) else None for b in range(B)]
+
+
+def assemble_sequences(prompt_ids: torch.Tensor, new_ids: torch.Tensor, eos, pad_token_id):
+    """transformers' batched greedy search over ids the device has already decoded: `prompt_ids` [B, L] and time-major `new_ids` [k, B]
+    (CPU).  A row is finished after its first EOS and holds `pad_token_id` from then on; the search stops after the step at which the
+    last row finishes.  Returns (sequences [B, L + n_new], n_new): n_new is the largest cut over the rows, or k if some row never
+    finished.  What the device decoded for a finished row is overwritten here."""
+    k, B = new_ids.shape
+    cuts = eos_cuts(new_ids, eos) if eos else [None] * B
+    n_new = max(cuts) if all(c is not None for c in cuts) else k
+    new = new_ids[:n_new].t().clone()
+    for b, c in enumerate(cuts):
+        if c is not None and c < n_new:
+            new[b, c:] = pad_token_id
+    return torch.cat([prompt_ids.to(torch.int64), new.to(torch.int64)], dim=1), n_new
+
+
 class HipQwen25VLTextEncoder(_HipTextEncoder):
     """`Qwen2_5_VLForConditionalGeneration(input_ids, attention_mask, pixel_values, image_grid_thw, output_hidden_states=True)` with the
     language model on the HIP kernels.  Returns an object with `.last_hidden_state` [B, L, d] bf16 and `.hidden_states`, a ONE-element
@@ -241,12 +326,14 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
     what = "HipQwen25VLTextEncoder"
 
     def __init__(self, module_or_state_dict, device=None, config=None, max_length: int = 4096, vision=None, weights: str = "bf16",
-                 sampling: bool = False):
+                 sampling: bool = False, max_batch: int = 1):
         if weights not in WEIGHT_FORMATS:
             _refuse(self.what, f"weights={weights!r} (the layer matrices are kept as one of {WEIGHT_FORMATS})")
         if not isinstance(sampling, bool):
             _refuse(self.what, f"sampling={sampling!r} (True or False)")
-        self.weights, self.sampling = weights, sampling
+        if isinstance(max_batch, bool) or not isinstance(max_batch, int) or not 1 <= max_batch <= MAX_BATCH:
+            _refuse(self.what, f"max_batch={max_batch!r} (an int in [1, {MAX_BATCH}]: the rows one generate decodes from one weight stream)")
+        self.weights, self.sampling, self.max_batch = weights, sampling, max_batch
         sd, cfg, dev, mod = _source(module_or_state_dict, config, device, self.what)
         self.vision = vision                               # a HipQwen25VLVisionTower, or None: the adopted module's eager tower
         why = qwen25vl_refusal(cfg)
@@ -296,9 +383,11 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         self.kv = _Buffers(dev)
 
     # ---- host-side preparation (no kernel) -----------------------------------------------------------------------------------------
-    def position_ids_for(self, input_ids, attention_mask=None, image_grid_thw=None, position_ids=None, mm_token_type_ids=None):
+    def position_ids_for(self, input_ids, attention_mask=None, image_grid_thw=None, position_ids=None, mm_token_type_ids=None,
+                         text_from_mask=False):
         """[3, B, L] int64: the caller's `position_ids`, else what the adopted module computes (`model.compute_3d_position_ids`), else
-        the arange of Qwen2_5_VLTextModel.forward."""
+        the arange of Qwen2_5_VLTextModel.forward - or, with `text_from_mask` (a left-padded batch of generate), the text positions
+        transformers' generate derives from the mask: cumsum(mask) - 1 on every axis, 0 on the padding."""
         B, L = input_ids.shape
         if position_ids is None:
             if self.module is None:
@@ -306,7 +395,10 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             position_ids = self.module.model.compute_3d_position_ids(
                 input_ids=input_ids, image_grid_thw=image_grid_thw, video_grid_thw=None, inputs_embeds=None, attention_mask=attention_mask,
                 past_key_values=None, mm_token_type_ids=mm_token_type_ids)
-            if position_ids is None:
+            if position_ids is None and text_from_mask and attention_mask is not None:
+                m = attention_mask.detach().cpu().long()
+                position_ids = (m.cumsum(-1) - 1).masked_fill(m == 0, 0)[None].expand(3, -1, -1)
+            elif position_ids is None:
                 position_ids = torch.arange(L).view(1, 1, -1).expand(3, B, -1)
         if position_ids.ndim == 2:
             position_ids = position_ids[None, ...].expand(3, position_ids.shape[0], -1)
@@ -316,7 +408,8 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             _refuse(self.what, f"position_ids of shape {tuple(position_ids.shape)} for input_ids [{B}, {L}]")
         return position_ids
 
-    def _prepare(self, input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids, image_embeds, kw):
+    def _prepare(self, input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids, image_embeds, kw,
+                 left=False):
         for k in ("pixel_values_videos", "video_grid_thw", "second_per_grid_ts"):
             if kw.get(k) is not None:
                 _refuse(self.what, f"{k}: videos are not implemented")
@@ -339,12 +432,17 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         ids_cpu = input_ids.detach().cpu()
         if self.video_token_id is not None and bool((ids_cpu == self.video_token_id).any()):
             _refuse(self.what, "video tokens in input_ids: videos are not implemented")
-        lengths = valid_lengths(attention_mask, B, L, self.what)
+        lengths = (left_valid_lengths if left else valid_lengths)(attention_mask, B, L, self.what)
         if pixel_values is not None and image_embeds is not None:
             _refuse(self.what, "pass pixel_values or image_embeds, not both")
         if pixel_values is not None and self.module is None and self.vision is None:
             _refuse(self.what, "adopted from a state dict (no vision tower at hand): pass image_embeds instead of pixel_values")
-        pos = self.position_ids_for(input_ids, attention_mask, image_grid_thw, position_ids, mm_token_type_ids)
+        if left:                                           # a batch: the module's position code runs on CPU copies (no eager kernel is launched)
+            cpu = lambda v: v.detach().cpu() if isinstance(v, torch.Tensor) else v
+            pos = self.position_ids_for(ids_cpu, cpu(attention_mask), cpu(image_grid_thw), cpu(position_ids), cpu(mm_token_type_ids),
+                                        text_from_mask=True)
+        else:
+            pos = self.position_ids_for(input_ids, attention_mask, image_grid_thw, position_ids, mm_token_type_ids)
         tables = mrope_tables(self.inv_freq, pos, self.mrope_section)
         return ids_cpu, lengths, tables, pos
 
@@ -447,14 +545,25 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         if not isinstance(input_ids, torch.Tensor) or input_ids.dim() != 2:
             _refuse(self.what, "input_ids must be a [B, L] tensor")
         B, L = input_ids.shape
-        if B != 1:
-            _refuse(self.what, f"input_ids with B = {B}: generate is implemented for B == 1")
-        if attention_mask is not None and (tuple(attention_mask.shape) != (B, L) or not bool((attention_mask.detach().cpu() != 0).all())):
-            _refuse(self.what, "attention_mask must be all ones for generate (no padding inside a KV cache)")
+        lengths = None
+        if B != 1 and self.max_batch > 1:                                         # a batch: left padding, one cache per row
+            if not 1 <= B <= self.max_batch:
+                _refuse(self.what, f"input_ids with B = {B}: this adoption takes 1 <= B <= max_batch = {self.max_batch}")
+            if self.sampling:
+                _refuse(self.what, f"sampling=True with B = {B}: rgn_lm_pick is one sequence (batched picking is not implemented)")
+            lengths = left_valid_lengths(attention_mask, B, L, self.what)
+        else:
+            if B != 1:
+                _refuse(self.what, f"input_ids with B = {B}: generate is implemented for B == 1")
+            if attention_mask is not None and (tuple(attention_mask.shape) != (B, L) or not bool((attention_mask.detach().cpu() != 0).all())):
+                _refuse(self.what, "attention_mask must be all ones for generate (no padding inside a KV cache)")
         if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
             _refuse(self.what, "max_new_tokens is required and must be an int >= 1 (the decode loop is a `for` over it)")
-        if L + max_new_tokens > self.max_length:
+        if lengths is None and L + max_new_tokens > self.max_length:
             _refuse(self.what, f"L + max_new_tokens = {L + max_new_tokens} exceeds max_length {self.max_length} of this adoption")
+        for b, n in enumerate(lengths or ()):
+            if n + max_new_tokens > self.max_length:
+                _refuse(self.what, f"row {b}: n + max_new_tokens = {n + max_new_tokens} exceeds max_length {self.max_length} of this adoption")
         if isinstance(sync_every, bool) or not isinstance(sync_every, int) or sync_every < 1:
             _refuse(self.what, "sync_every must be an int >= 1")
         if eos_token_id is None:                                                  # transformers' default; an explicit [] asks for no EOS
@@ -540,8 +649,13 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         the ids back every `sync_every` tokens to look for EOS (never without one); the result does not depend on `sync_every`.
         Under `sampling=True` the call also takes do_sample, temperature, top_k, top_p, repetition_penalty (None: the module's
         generation_config value, else off), generator= or uniforms= (fp32 [max_new_tokens] on the device) and output_scores=True; the pick
-        is then rgn_lm_head_argmax for the logits and one rgn_lm_pick per token, still without a host read inside a step."""
+        is then rgn_lm_head_argmax for the logits and one rgn_lm_pick per token, still without a host read inside a step.
+        Under `max_batch=N` the call also takes `input_ids [B, L]`, 2 <= B <= N, with a left-padded `attention_mask` (zeros, then ones)
+        and `pad_token_id` (None: generation_config.pad_token_id, else the first EOS id): LongTensor [B, L + n_new], each row cut after
+        its first EOS and filled with the pad id, n_new the largest cut (max_new_tokens if a row never finished); `.logits` is then a
+        tuple of n_new fp32 [B, V] tensors whose rows past a sequence's EOS are not meaningful (`_generate_rows`)."""
         plan = None
+        pad_arg = kw.pop("pad_token_id", None) if self.max_batch > 1 else None    # a default adoption refuses the argument as before
         if self.sampling:                                                         # opt-in: without it every refusal below is what it was
             mine = {k: kw.pop(k) for k in PICK_ARGS + PICK_EXTRA if k in kw}
             eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, False, sync_every, kw)
@@ -550,6 +664,9 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
                 plan = None
         else:
             eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
+        if input_ids.shape[0] > 1:                                                # only a max_batch > 1 adoption gets here; B = 1 stays below
+            return self._generate_rows(input_ids, attention_mask, pixel_values, image_grid_thw, int(max_new_tokens), eos, pad_arg,
+                                       return_dict_in_generate, output_logits, mm_token_type_ids, image_embeds, position_ids, sync_every)
         ids_cpu, lengths, tables, pos = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids,
                                                       mm_token_type_ids, image_embeds, {})
         L, T = ids_cpu.shape[1], int(max_new_tokens)
@@ -652,3 +769,98 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             return seq
         return QwenGenerateOutput(seq, tuple(logits[k][None] for k in range(n_new)) if logits is not None else None,
                                   tuple(scores[k][None] for k in range(n_new)) if plan is not None and scores is not None else None)
+
+    def _generate_rows(self, input_ids, attention_mask, pixel_values, image_grid_thw, T, eos, pad_arg, return_dict_in_generate, output_logits,
+                       mm_token_type_ids, image_embeds, position_ids, sync_every):
+        """`generate` for 2 <= B <= max_batch left-padded rows (every refusal has been raised): each row is prefilled over its valid tokens
+        by `_prefill_row` into its own cache at rows [0, n_b) - no padded key is ever in a cache, so decode needs no mask - then every step
+        decodes the B rows from ONE stream of the weights (rgn_lm_gemv_bf16_rows / rgn_lm_gemv_w8_rows, rgn_lm_kv_append_bf16_rows,
+        rgn_lm_decode_attention_bf16_rows, rgn_lm_head_argmax_rows, the row kernels at M = B; new ids [T, B] and decode RoPE tables
+        [T, B, 128] time-major, so a step's rows are contiguous).  Row b's tokens and fp32 logits are bit for bit those of the B = 1 call
+        on row b's unpadded prompt.  The device keeps decoding finished rows (a fixed launch count, no dependence on device data); the host
+        overwrites them with the pad id at assembly (`assemble_sequences`).  Logits of a row past its EOS are not meaningful."""
+        import ctypes as C
+        ids_cpu, lens, tables, pos = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids,
+                                                   image_embeds, {}, left=True)
+        B, L = ids_cpu.shape
+        pad = resolve_pad_token_id(pad_arg, getattr(self.module, "generation_config", None), eos)
+        new_tables = mrope_tables(self.inv_freq, decode_position_ids(pos, T), self.mrope_section)        # [2, B, T, 128]
+        head = self._adopt_lm_head()                                               # may refuse: nothing has been launched yet
+        emb = self._image_embeds(pixel_values, image_grid_thw, image_embeds)
+        rows = None
+        if emb is not None:
+            if self.image_token_id is None:
+                _refuse(self.what, "the config has no image_token_id")
+            rows = image_rows_left(ids_cpu, lens, int(self.image_token_id), emb.shape[0], self.what)
+            idx = torch.cat(rows).to(self.device)
+        lib, dev, d, V = _lib.lib(), self.device, self.d, self.tok.shape[0]
+        nmax = max(lens)
+        cap, kvw, nl = nmax + T, 2 * self.Hkv * HEAD_DIM, len(self.layers)
+        ws_a, ws_h = B * lib.rgn_lm_decode_attention_workspace_bytes(self.Hq, cap), B * lib.rgn_lm_head_workspace_bytes(V)
+        c = self.kv.get((B, cap), dict(cache=(nl, B, cap, kvw), h=(B, d), n=(B, d), qkv=(B, self.qkv_cols), a=(B, self.Hq * HEAD_DIM),
+                                       ff=(B, 2 * self.F), g=(B, self.F), ws_a=((ws_a + 1) // 2,), ws_h=((ws_h + 1) // 2,)))
+        t = self.buf.get(nmax, dict(h=(nmax, d), n=(nmax, d), qkv=(nmax, self.qkv_cols), a=(nmax, self.Hq * HEAD_DIM), ff=(nmax, 2 * self.F),
+                                    g=(nmax, self.F)))
+        ids = input_ids.to(dev, torch.int64).contiguous()
+        new = torch.empty(T, B, dtype=torch.int64, device=dev)                    # time-major: a step's B ids are contiguous
+        logits = torch.empty(T, B, V, dtype=torch.float32, device=dev) if output_logits else None
+        tab, ntab = tables.to(dev), new_tables.transpose(1, 2).contiguous().to(dev)                       # [2, B, L, 128], [2, T, B, 128]
+        st, ck = _stream(), _lib.check
+        pn, pnew = c["n"].data_ptr(), new.data_ptr()
+
+        def pick(k):                                                              # tokens k of the B rows from the normalised rows in c["n"]
+            ck(lib.rgn_lm_head_argmax_rows(_p(head), pn, d, B, V, d, pnew + 8 * B * k, 1, None if logits is None else _p(logits[k]), V,
+                                           _p(c["ws_h"]), ws_h, st), "rgn_lm_head_argmax_rows")
+        at = 0
+        for b, n in enumerate(lens):                                              # rows prefill one after another on the existing kernels
+            k = rows[b].numel() if rows is not None else 0
+            h, _ = self._prefill_row(t, ids[b, L - n:], n, tab[0, b, L - n:], tab[1, b, L - n:], emb[at:at + k] if k else None,
+                                     idx[at:at + k] if k else None, cache=c["cache"][:, b])
+            at += k
+            self._rms(h[n - 1:n], self.final_ln, c["n"][b:b + 1])                 # the final norm on the last row only
+        pick(0)
+        ph, pqkv, pa, pff, pg, pws = (c[k].data_ptr() for k in ("h", "qkv", "a", "ff", "g", "ws_a"))
+        if self.weights == "fp8":
+            gemv, gemv_name = lib.rgn_lm_gemv_w8_rows, "rgn_lm_gemv_w8_rows"
+            wp = lambda w: (w.data_ptr(), ops._wscale(w).data_ptr())
+        else:
+            gemv, gemv_name = lib.rgn_lm_gemv_bf16_rows, "rgn_lm_gemv_bf16_rows"
+            wp = lambda w: (w.data_ptr(),)
+        lp = [(p["ln1"].data_ptr(), wp(p["wqkv"]), p["bqkv"].data_ptr(), wp(p["wo"]), p["ln2"].data_ptr(), wp(p["wgu"]),
+               wp(p["wdown"]), c["cache"][i].data_ptr()) for i, p in enumerate(self.layers)]
+        ptok, pfin, pcos, psin = self.tok.data_ptr(), self.final_ln.data_ptr(), ntab[0].data_ptr(), ntab[1].data_ptr()
+        Hq, Hkv, F, eps, scale, qc, ad = self.Hq, self.Hkv, self.F, self.eps, float(self.scale), self.qkv_cols, self.Hq * HEAD_DIM
+        cstride = cap * kvw
+        row0, nn = (C.c_int * B)(), (C.c_int * B)()                               # host arrays: the entries copy them into the launch
+        n_new = T
+        for k in range(1, T + 1):                                                 # bounded by max_new_tokens, never by device data
+            if eos and (k % sync_every == 0 or k == T):                           # the host's look at the ids: the only synchronisation
+                cuts = eos_cuts(new[:k].cpu(), eos)
+                if all(cut is not None for cut in cuts):
+                    n_new = max(cuts)
+                    break
+            if k == T:
+                break
+            for b, n in enumerate(lens):                                          # the tokens picked last: row n + k - 1 of each cache
+                row0[b], nn[b] = n + k - 1, n + k
+            tb = 256 * B * (k - 1)
+            ck(lib.rgn_text_embed(pnew + 8 * B * (k - 1), B, ptok, V, None, 0, ph, d, st), "rgn_text_embed")
+            for ln1, wqkv, bqkv, wo, ln2, wgu, wdown, pc in lp:
+                ck(lib.rgn_rms_norm_rows(ph, d, ln1, pn, d, B, d, eps, st), "rgn_rms_norm_rows")
+                ck(gemv(*wqkv, pn, d, bqkv, None, 0, pqkv, qc, B, qc, d, st), gemv_name)
+                ck(lib.rgn_mrope_bf16(pqkv, qc, pcos + tb, psin + tb, B, Hq, Hkv, st), "rgn_mrope_bf16")
+                ck(lib.rgn_lm_kv_append_bf16_rows(pqkv, qc, pc, cstride, cap, row0, B, Hq, Hkv, st), "rgn_lm_kv_append_bf16_rows")
+                ck(lib.rgn_lm_decode_attention_bf16_rows(pqkv, qc, pc, cstride, pa, ad, nn, B, Hq, Hkv, scale, pws, ws_a, st),
+                   "rgn_lm_decode_attention_bf16_rows")
+                ck(gemv(*wo, pa, ad, None, ph, d, ph, d, B, d, ad, st), gemv_name)
+                ck(lib.rgn_rms_norm_rows(ph, d, ln2, pn, d, B, d, eps, st), "rgn_rms_norm_rows")
+                ck(gemv(*wgu, pn, d, None, None, 0, pff, 2 * F, B, 2 * F, d, st), gemv_name)
+                ck(lib.rgn_swiglu_bf16(pff, 2 * F, pg, F, B, F, st), "rgn_swiglu_bf16")
+                ck(gemv(*wdown, pg, F, None, ph, d, ph, d, B, d, F, st), gemv_name)
+            ck(lib.rgn_rms_norm_rows(ph, d, pfin, pn, d, B, d, eps, st), "rgn_rms_norm_rows")
+            pick(k)
+        seq, n_new = assemble_sequences(ids_cpu, new[:n_new].cpu(), eos, pad)
+        seq = seq.to(input_ids.device)
+        if not return_dict_in_generate:
+            return seq
+        return QwenGenerateOutput(seq, tuple(logits[k] for k in range(n_new)) if logits is not None else None)

@@ -25,6 +25,14 @@ runs one rgn_lm_pick after lm_head.  `*_ms_per_new_token` of a sampled leg again
     python tools/qwen_generate_bench.py --weights both --out profiles/r17_qwen_fp8_generate_bench.json --ab-out profiles/r17_lm_gemv_w8_ab.txt
     rocprofv3 --kernel-trace --stats -d DIR -o kt -- python tools/qwen_generate_bench.py --hip-only --no-ab --iters 2    # the kernel listing
     python tools/qwen_generate_bench.py --weights both --sampling --hip-only --no-ab --out profiles/r19_qwen_sampling_bench.json
+
+`--batch` times a `max_batch=8` adoption (bf16 and fp8 legs) at B = 1, 2, 4, 8 rows of the same length (no padding, no EOS), every leg
+alternating in the one process, beside the B = 1 leg of a default (`max_batch=1`) adoption, which issues the same launches as B = 1 of
+the other.  Per leg: ms per step = (t64 - t1) / 63 of the medians (the B prefills, which run row after row, cancel), tokens per second
+= B / that, the step against B times the B = 1 step, and against the streaming floor of ITS bytes (weights and lm_head once, B caches).
+
+    python tools/qwen_generate_bench.py --batch --no-ab --out profiles/r26_qwen_batched_generate_bench.json
+    rocprofv3 --kernel-trace --stats -d DIR -o kt -- python tools/qwen_generate_bench.py --batch --hip-only --no-ab --iters 1
 """
 import argparse
 import json
@@ -181,6 +189,62 @@ def gemv_w8_ab(rounds=7):
     return rows
 
 
+BATCHES = (1, 2, 4, 8)
+
+
+def batched(a, res):
+    """The `--batch` legs (module docstring): res["L300"], res["L1500"]."""
+    from transformers import Qwen2_5_VLForConditionalGeneration
+    from regione_amd import qwen_text_encoder as QT
+    cfg = full_size_config()
+    tc = cfg.text_config
+    torch.manual_seed(0)
+    with torch.device("cuda"):
+        mod = Qwen2_5_VLForConditionalGeneration(cfg).eval()
+    mod = mod.to(torch.bfloat16)
+    torch.cuda.empty_cache()
+    encs = {}
+    for fmt in ("bf16", "fp8"):
+        encs[fmt] = QT.HipQwen25VLTextEncoder(mod, weights=fmt, max_batch=max(BATCHES))
+        encs[f"{fmt}_default"] = QT.HipQwen25VLTextEncoder(mod, weights=fmt)
+    res["batches"], res["weights"] = list(BATCHES), "both"
+    g = torch.Generator().manual_seed(1)
+    for L in LENGTHS:
+        ids = torch.randint(0, 151000, (max(BATCHES), L), generator=g).cuda()
+        arms = {}
+        for fmt in ("bf16", "fp8"):
+            for n in (1, NEW):
+                arms[f"{fmt}_default_{n}"] = lambda fmt=fmt, n=n: encs[f"{fmt}_default"].generate(ids[:1], max_new_tokens=n, eos_token_id=[])
+                for B in BATCHES:
+                    arms[f"{fmt}_b{B}_{n}"] = lambda fmt=fmt, n=n, B=B: encs[fmt].generate(ids[:B], max_new_tokens=n, eos_token_id=[])
+        ts = {k: [] for k in arms}
+        with torch.no_grad():
+            for fn in arms.values():
+                fn()                                                             # warm
+            for _ in range(a.iters):
+                for k, fn in arms.items():                                       # the legs alternate
+                    ts[k].append(_ms(fn))
+            r = {"L": L, **{k: _stat(v) for k, v in ts.items()}}
+            for fmt in ("bf16", "fp8"):                                          # the batch is invariant, here too
+                full = encs[fmt].generate(ids, max_new_tokens=NEW, eos_token_id=[])
+                assert tuple(full.shape) == (max(BATCHES), L + NEW)
+                assert torch.equal(full[:1], encs[f"{fmt}_default"].generate(ids[:1], max_new_tokens=NEW, eos_token_id=[]))
+        for fmt in ("bf16", "fp8"):
+            per = {leg: (r[f"{fmt}_{leg}_{NEW}"]["median_ms"] - r[f"{fmt}_{leg}_1"]["median_ms"]) / (NEW - 1)
+                   for leg in ("default", *(f"b{B}" for B in BATCHES))}
+            sb = step_bytes(tc, L + NEW // 2, fmt)
+            rows = [dict(leg="default adoption, B = 1", B=1, ms_per_step=per["default"], tokens_per_s=1e3 / per["default"])]
+            for B in BATCHES:
+                by = sb["decoder_weights"] + sb["lm_head"] + B * sb["kv_cache"]
+                floor = by / HBM_BYTES_PER_S * 1e3
+                rows.append(dict(leg=f"max_batch = 8, B = {B}", B=B, ms_per_step=per[f"b{B}"], tokens_per_s=B * 1e3 / per[f"b{B}"],
+                                 over_B_times_the_b1_step=per[f"b{B}"] / (B * per["b1"]), step_bytes=by, streaming_floor_ms=floor,
+                                 over_its_streaming_floor=per[f"b{B}"] / floor))
+            r[f"{fmt}_table"] = rows
+        res[f"L{L}"] = r
+        print(f"L{L}", json.dumps({k: v for k, v in r.items() if k.endswith("_table")}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
@@ -191,6 +255,7 @@ def main():
     ap.add_argument("--no-generate", action="store_true", help="only the GEMV A/B")
     ap.add_argument("--weights", choices=("bf16", "fp8", "both"), default="bf16", help="format of the layers' projection matrices")
     ap.add_argument("--sampling", action="store_true", help="adopt with sampling=True and time two sampled legs beside the greedy one")
+    ap.add_argument("--batch", action="store_true", help="time a max_batch=8 adoption at B = 1, 2, 4, 8 beside a default one (bf16 and fp8)")
     a = ap.parse_args()
     from regione_amd import build
     sha = build.csrc_hash()
@@ -227,7 +292,11 @@ def main():
         if a.ab_out:
             with open(a.ab_out, "w") as f:
                 f.write("\n".join(lines) + "\n")
-    if not a.no_generate:
+    if a.batch:
+        res["stat"] = ("median and min / max of warm, synchronised runs, every leg alternating; ms per step = (t64 - t1) / 63 of the medians; "
+                       "tokens per second = B / that")
+        batched(a, res)
+    elif not a.no_generate:
         from transformers import Qwen2_5_VLForConditionalGeneration
         from regione_amd import qwen_text_encoder as QT
         cfg = full_size_config()
