@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 121
+#define RGN_ABI_VERSION 122
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -605,6 +605,19 @@ int rgn_lm_seen_mark(const void* ids, int n, void* seen, int V, void* stream);
 int rgn_lm_pick(const float* logits, int V, void* seen, float penalty, int sample, float temperature, int top_k, double top_p,
                 const float* uniform, void* token_out, float* scores_out, void* workspace, size_t workspace_bytes, void* stream);
 size_t rgn_lm_pick_workspace_bytes(int V);
+/* rgn_lm_pick for the B rows of a batched decode step, one configuration for all of them: row b reads logits + b * ldl (fp32 [B, ldl], what
+ * rgn_lm_head_argmax_rows(..., logits_out, ldl) wrote), the byte map seen + b * seen_stride (bytes) and uniform[b] (fp32 [B], this step's;
+ * read only when sample != 0), writes token_out[b * token_stride] (int64 elements) and, with scores_out != NULL, row b of scores_out
+ * [B, lds], and sets seen_b[token] = 1.  ONE launch, one block per row: a block is the 16-wave block of rgn_lm_pick with its 128 KB of
+ * LDS, so it has a CU to itself and up to RGN_LM_MAX_BATCH CUs work side by side.  Blocks never communicate: no atomics, no reduction
+ * across rows.  Row b's result - the token, the processed scores, the seen bytes - is BIT FOR BIT what rgn_lm_pick gives for row b
+ * alone, for every B in 1..8 (both kernels run the same device function).  Rows >= B and columns >= V of every buffer are never written,
+ * the logits never at all.  1 <= B <= RGN_LM_MAX_BATCH; ldl >= V, lds >= V (with scores_out), seen_stride >= V, token_stride >= 1; the
+ * ranges and alignments of rgn_lm_pick; scores_out may not overlap the logits; workspace_bytes >= B * rgn_lm_pick_workspace_bytes(V).
+ * Every refusal is raised before the launch.  The prompt ids of row b are marked by rgn_lm_seen_mark on seen + b * seen_stride. */
+int rgn_lm_pick_rows(const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty, int sample, float temperature,
+                     int top_k, double top_p, const float* uniform, void* token_out, int token_stride, float* scores_out, int lds,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * f4  vision tower of the Qwen2.5-VL prompt encoder ([EXT] transformers Qwen2_5_VisionTransformerPretrainedModel: `get_image_features`

@@ -174,6 +174,8 @@ SIGNATURES = {
     "rgn_lm_pick": [_c_void_p, _c_int, _c_void_p, _c_float, _c_int, _c_float, _c_int, C.c_double, _c_void_p, _c_void_p, _c_void_p,
                     _c_void_p, C.c_size_t, _c_void_p],
     "rgn_lm_pick_workspace_bytes": [_c_int],
+    "rgn_lm_pick_rows": [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, C.c_size_t, _c_float, _c_int, _c_float, _c_int, C.c_double, _c_void_p,
+                         _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, C.c_size_t, _c_void_p],
     # f4: vision tower of the Qwen2.5-VL prompt encoder (csrc/vision.hip)
     "rgn_vision_attention_bf16": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p, _c_int, _c_void_p],
     "rgn_vision_rope_bf16": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p],

@@ -19,6 +19,7 @@
 //                               loaded and converted once, x sits in LDS as fp32, one accumulator per (weight row, x row)
 //   lm_head_finalize_rows_kernel, lm_kv_append_rows_kernel, lm_decode_attention_rows_kernel, lm_decode_merge_rows_kernel
 //                               the batch on a grid axis; per-sequence cache lengths travel by value (no device read, no upload)
+//   lm_pick_rows_kernel         the block of lm_pick_kernel once per row (blockIdx.x = b), each on a CU of its own: the same device function
 // No atomics; every reduction has a fixed order (lanes: the butterfly of wave_sum; k, keys and slices: ascending), so a repeated call is
 // bit-identical.
 #include <math.h>
@@ -636,9 +637,11 @@ __device__ float pick_select(const float* s, int V, double* bins, double* tot, f
     return pick_unkey(prefix);
 }
 
-__global__ __launch_bounds__(PICK_T) void lm_pick_kernel(const float* __restrict__ z, int V, uint8_t* __restrict__ seen, float penalty,
-                                                          int sample, float temperature, int top_k, double top_p,
-                                                          const float* __restrict__ uniform, int64_t* __restrict__ token_out, float* s) {
+// The pick of ONE row by the whole block: z [V] the row's logits, `seen` its byte map, uniform[0] its uniform, token_out[0] its id slot,
+// s [V] its scores (scores_out or workspace).  Both kernels below are this body, so a row's result does not depend on which one ran it.
+__device__ __forceinline__ void lm_pick_row(const float* __restrict__ z, int V, uint8_t* __restrict__ seen, float penalty, int sample,
+                                            float temperature, int top_k, double top_p, const float* __restrict__ uniform,
+                                            int64_t* __restrict__ token_out, float* s) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     double* bins = (double*)smem;
     __shared__ double tot[PICK_BINS];
@@ -787,6 +790,23 @@ __global__ __launch_bounds__(PICK_T) void lm_pick_kernel(const float* __restrict
         pick_pass(s, V, [&](int v, float x) {
             if (!(x >= lo)) s[v] = -INFINITY;
         });
+}
+
+__global__ __launch_bounds__(PICK_T) void lm_pick_kernel(const float* __restrict__ z, int V, uint8_t* __restrict__ seen, float penalty,
+                                                          int sample, float temperature, int top_k, double top_p,
+                                                          const float* __restrict__ uniform, int64_t* __restrict__ token_out, float* s) {
+    lm_pick_row(z, V, seen, penalty, sample, temperature, top_k, top_p, uniform, token_out, s);
+}
+
+// One block per row (blockIdx.x = b < B), each the block of lm_pick_kernel with its own 128 KB of LDS, i.e. a CU to itself: the rows run
+// side by side and never communicate.  `uniform` may be null when sample == 0 (never read then).
+__global__ __launch_bounds__(PICK_T) void lm_pick_rows_kernel(const float* __restrict__ z, int ldl, int V, uint8_t* __restrict__ seen,
+                                                               size_t seen_stride, float penalty, int sample, float temperature, int top_k,
+                                                               double top_p, const float* __restrict__ uniform,
+                                                               int64_t* __restrict__ token_out, int token_stride, float* s, size_t lds) {
+    const size_t b = blockIdx.x;
+    lm_pick_row(z + b * (size_t)ldl, V, seen + b * seen_stride, penalty, sample, temperature, top_k, top_p, sample ? uniform + b : uniform,
+                token_out + b * (size_t)token_stride, s + b * lds);
 }
 
 }  // namespace rgn
@@ -1029,6 +1049,41 @@ int rgn_lm_pick(const float* logits, int V, void* seen, float penalty, int sampl
     hipLaunchKernelGGL(lm_pick_kernel, dim3(1), dim3(PICK_T), PICK_LDS, (hipStream_t)stream, logits, V, (uint8_t*)seen, penalty, sample ? 1 : 0,
                        temperature, top_k, top_p, uniform, (int64_t*)token_out, scores_out ? scores_out : (float*)workspace);
     return check_launch("lm_pick_kernel");
+}
+
+int rgn_lm_pick_rows(const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty, int sample, float temperature,
+                     int top_k, double top_p, const float* uniform, void* token_out, int token_stride, float* scores_out, int lds,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (!logits || !seen || !token_out || !workspace || V < 1 || V > PICK_MAX_V)
+        return fail(RGN_E_BADARG, "lm_pick_rows: bad argument (logits, seen, token_out, workspace non-null; 1 <= V <= 1048576)");
+    if (!batch_ok(B)) return fail(RGN_E_BADARG, "lm_pick_rows: B outside [1, 8]");
+    if (ldl < V || (scores_out && lds < V) || seen_stride < (size_t)V || token_stride < 1)
+        return fail(RGN_E_BADARG, "lm_pick_rows: ldl >= V, lds >= V, seen_stride >= V, token_stride >= 1");
+    if (!(penalty > 0.f) || !(penalty < INFINITY)) return fail(RGN_E_BADARG, "lm_pick_rows: the repetition penalty must be in (0, inf)");
+    if (!(temperature > 0.f) || !(temperature < INFINITY)) return fail(RGN_E_BADARG, "lm_pick_rows: the temperature must be in (0, inf)");
+    if (top_k < 0) return fail(RGN_E_BADARG, "lm_pick_rows: top_k must be >= 0 (0 = off)");
+    if (!(top_p > 0.0) || !(top_p <= 1.0)) return fail(RGN_E_BADARG, "lm_pick_rows: top_p must be in (0, 1] (1 = off)");
+    if (sample && !uniform) return fail(RGN_E_BADARG, "lm_pick_rows: sampling reads its uniforms from device memory (uniform non-null)");
+    if (((uintptr_t)token_out & 7u) || (((uintptr_t)logits | (uintptr_t)scores_out | (uintptr_t)workspace | (uintptr_t)uniform) & 3u))
+        return fail(RGN_E_BADARG, "lm_pick_rows: token_out must be 8-byte, logits, scores_out, workspace and uniform 4-byte aligned");
+    if (scores_out) {                   // the spans [first element, last element of row B - 1] of the two matrices may not meet
+        const uintptr_t z0 = (uintptr_t)logits, z1 = z0 + ((size_t)(B - 1) * ldl + V) * sizeof(float);
+        const uintptr_t s0 = (uintptr_t)scores_out, s1 = s0 + ((size_t)(B - 1) * lds + V) * sizeof(float);
+        if (s0 < z1 && z0 < s1) return fail(RGN_E_BADARG, "lm_pick_rows: scores_out may not overlap the logits");
+    }
+    if (workspace_bytes < (size_t)B * rgn_lm_pick_workspace_bytes(V))
+        return fail(RGN_E_BADARG, "lm_pick_rows: workspace smaller than B rgn_lm_pick_workspace_bytes(V)");
+    static bool attr[64] = {};          // per device (one process may drive several GPUs)
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !attr[dev]) {
+        (void)hipFuncSetAttribute((const void*)lm_pick_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PICK_LDS);
+        if (dev >= 0 && dev < 64) attr[dev] = true;
+    }
+    hipLaunchKernelGGL(lm_pick_rows_kernel, dim3(B), dim3(PICK_T), PICK_LDS, (hipStream_t)stream, logits, ldl, V, (uint8_t*)seen, seen_stride,
+                       penalty, sample ? 1 : 0, temperature, top_k, top_p, uniform, (int64_t*)token_out, token_stride,
+                       scores_out ? scores_out : (float*)workspace, scores_out ? (size_t)lds : (size_t)V);
+    return check_launch("lm_pick_rows_kernel");
 }
 
 }  // extern "C"

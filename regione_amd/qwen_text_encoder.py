@@ -45,7 +45,18 @@ left-padded rows, as transformers' batched greedy search does: rows prefill one 
 caches, then every step decodes all B rows from ONE stream of the weights (the `_rows` entries of csrc/decode.hip).  The batch is
 invariant: row b's tokens and fp32 logits are bit for bit those of the B = 1 call on row b's unpadded prompt.  A row is finished after
 its first EOS and holds `pad_token_id` from then on (`assemble_sequences`); B = 1 under such an adoption takes the one-row launches.
-Sampling over a batch is refused (rgn_lm_pick is one sequence).  Not measured: real checkpoints.
+Sampling over a batch is refused (rgn_lm_pick is one sequence) unless the adoption also sets `batch_sampling=True`.
+
+`batch_sampling=True` (opt-in; needs `sampling=True` and `max_batch > 1`; without it every refusal is what it was) lets a batch of B >= 2
+rows take the decoding configuration of `sampling=True`, ONE configuration for the whole batch as in transformers: per step
+rgn_lm_head_argmax_rows writes the fp32 [B, V] logits and ONE rgn_lm_pick_rows (one block per row, each on a CU of its own, row b bit for
+bit rgn_lm_pick on row b) writes the B tokens into the id row the next rgn_text_embed reads.  `uniforms=` is then [max_new_tokens, B],
+time-major like the new ids.  The byte map is [B, V], row b marked over that row's VALID prompt ids only: the left padding is not marked.
+This is a deliberate difference from transformers, whose RepetitionPenaltyLogitsProcessor gathers at the pad positions too and so, for
+Qwen (the pad id is also an EOS id), penalises an EOS in padded rows only; not marking it is what keeps the batch invariant: for given
+`uniforms`, row b's tokens, fp32 logits and scores are bit for bit those of the B = 1 sampled call on row b's unpadded prompt with
+`uniforms[:, b]`.  B = 1 keeps the one-sequence path; a configuration that is greedy as before runs the batched greedy launches
+unchanged.  Not measured: real checkpoints.
 
 There is no eager fallback inside: what the kernels do not implement raises RegionEHipError before any launch, and the adapter
 (regione_amd.adapters, components.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
@@ -163,7 +174,8 @@ def decode_position_ids(prompt_position_ids: torch.Tensor, n_new: int) -> torch.
 class QwenGenerateOutput:
     """`generate(..., return_dict_in_generate=True)`: `.sequences` [1, L + n_new] int64 and, with `output_logits=True`, `.logits`, a tuple
     of n_new fp32 [1, V] tensors (the raw lm_head outputs the tokens were picked from); None otherwise.  Under `sampling=True`,
-    `output_scores=True` adds `.scores`, the same shape: the processed scores of rgn_lm_pick (-inf where top-k / top-p filtered)."""
+    `output_scores=True` adds `.scores`, the same shape: the processed scores of rgn_lm_pick (-inf where top-k / top-p filtered).  Over a
+    batch of B rows every one of these has B rows."""
 
     def __init__(self, sequences, logits=None, scores=None):
         self.sequences, self.logits, self.scores = sequences, logits, scores
@@ -326,14 +338,20 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
     what = "HipQwen25VLTextEncoder"
 
     def __init__(self, module_or_state_dict, device=None, config=None, max_length: int = 4096, vision=None, weights: str = "bf16",
-                 sampling: bool = False, max_batch: int = 1):
+                 sampling: bool = False, max_batch: int = 1, batch_sampling: bool = False):
         if weights not in WEIGHT_FORMATS:
             _refuse(self.what, f"weights={weights!r} (the layer matrices are kept as one of {WEIGHT_FORMATS})")
         if not isinstance(sampling, bool):
             _refuse(self.what, f"sampling={sampling!r} (True or False)")
         if isinstance(max_batch, bool) or not isinstance(max_batch, int) or not 1 <= max_batch <= MAX_BATCH:
             _refuse(self.what, f"max_batch={max_batch!r} (an int in [1, {MAX_BATCH}]: the rows one generate decodes from one weight stream)")
-        self.weights, self.sampling, self.max_batch = weights, sampling, max_batch
+        if not isinstance(batch_sampling, bool):
+            _refuse(self.what, f"batch_sampling={batch_sampling!r} (True or False)")
+        if batch_sampling and not sampling:
+            _refuse(self.what, "batch_sampling=True without sampling=True (it is the decoding configuration of sampling=True over a batch)")
+        if batch_sampling and max_batch == 1:
+            _refuse(self.what, "batch_sampling=True with max_batch=1 (it needs max_batch > 1: one row takes the one-sequence pick)")
+        self.weights, self.sampling, self.max_batch, self.batch_sampling = weights, sampling, max_batch, batch_sampling
         sd, cfg, dev, mod = _source(module_or_state_dict, config, device, self.what)
         self.vision = vision                               # a HipQwen25VLVisionTower, or None: the adopted module's eager tower
         why = qwen25vl_refusal(cfg)
@@ -549,7 +567,7 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         if B != 1 and self.max_batch > 1:                                         # a batch: left padding, one cache per row
             if not 1 <= B <= self.max_batch:
                 _refuse(self.what, f"input_ids with B = {B}: this adoption takes 1 <= B <= max_batch = {self.max_batch}")
-            if self.sampling:
+            if self.sampling and not self.batch_sampling:
                 _refuse(self.what, f"sampling=True with B = {B}: rgn_lm_pick is one sequence (batched picking is not implemented)")
             lengths = left_valid_lengths(attention_mask, B, L, self.what)
         else:
@@ -577,9 +595,10 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             _refuse(self.what, "eos_token_id must be an int or a list of ints")
         return eos
 
-    def _pick_plan(self, do_sample, max_new_tokens, kw):
+    def _pick_plan(self, do_sample, max_new_tokens, kw, B=1):
         """`sampling=True`: the decoding configuration of this call - an argument, else the module's generation_config field, else off -
-        and every refusal that goes with it, before any launch.  `kw` holds the PICK_ARGS / PICK_EXTRA arguments of the call."""
+        and every refusal that goes with it, before any launch.  `kw` holds the PICK_ARGS / PICK_EXTRA arguments of the call.  A batch
+        (`batch_sampling=True`, B >= 2) shares the one configuration; its `uniforms` are [max_new_tokens, B]."""
         gc = getattr(self.module, "generation_config", None)
         if self.tok.shape[0] > 1 << 20:
             _refuse(self.what, f"a vocabulary of {self.tok.shape[0]} under sampling=True (rgn_lm_pick takes V <= 1048576)")
@@ -613,8 +632,12 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         if uniforms is not None:
             here = torch.device(self.device)
             there = uniforms.device if isinstance(uniforms, torch.Tensor) else None
-            if there is None or tuple(uniforms.shape) != (max_new_tokens,) or uniforms.dtype != torch.float32 or not uniforms.is_contiguous() \
+            shape = (max_new_tokens,) if B == 1 else (max_new_tokens, B)
+            if there is None or tuple(uniforms.shape) != shape or uniforms.dtype != torch.float32 or not uniforms.is_contiguous() \
                     or there.type != here.type or (here.index is not None and there.index not in (None, here.index)):
+                if B > 1:
+                    _refuse(self.what, f"uniforms must be a contiguous float32 tensor of shape ({max_new_tokens}, {B}) on "
+                                       f"{torch.device(self.device)} (time-major: one uniform in [0, 1) per new token and row)")
                 _refuse(self.what, f"uniforms must be a contiguous float32 tensor of shape ({max_new_tokens},) on {torch.device(self.device)} "
                                    "(one uniform in [0, 1) per new token)")
         if scores is not None and not isinstance(scores, bool):
@@ -653,20 +676,26 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         Under `max_batch=N` the call also takes `input_ids [B, L]`, 2 <= B <= N, with a left-padded `attention_mask` (zeros, then ones)
         and `pad_token_id` (None: generation_config.pad_token_id, else the first EOS id): LongTensor [B, L + n_new], each row cut after
         its first EOS and filled with the pad id, n_new the largest cut (max_new_tokens if a row never finished); `.logits` is then a
-        tuple of n_new fp32 [B, V] tensors whose rows past a sequence's EOS are not meaningful (`_generate_rows`)."""
+        tuple of n_new fp32 [B, V] tensors whose rows past a sequence's EOS are not meaningful (`_generate_rows`).
+        Under `batch_sampling=True` such a batch also takes the arguments of `sampling=True`, one configuration for all rows: uniforms= is
+        then a contiguous fp32 [max_new_tokens, B] on the device (time-major, like the new ids), generator= fills torch.rand(T, B) once
+        before the loop - so with a generator a row's stream of uniforms depends on B and on the row's place in the batch - and
+        output_scores=True gives `.scores`, a tuple of n_new fp32 [B, V] tensors.  For given `uniforms`, row b is bit for bit the B = 1
+        call on its unpadded prompt with uniforms[:, b].  The repetition penalty of row b sees that row's valid prompt ids and its own
+        new tokens; the left padding is NOT marked (transformers gathers at the pad positions too)."""
         plan = None
         pad_arg = kw.pop("pad_token_id", None) if self.max_batch > 1 else None    # a default adoption refuses the argument as before
         if self.sampling:                                                         # opt-in: without it every refusal below is what it was
             mine = {k: kw.pop(k) for k in PICK_ARGS + PICK_EXTRA if k in kw}
             eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, False, sync_every, kw)
-            plan = self._pick_plan(do_sample, max_new_tokens, mine)
+            plan = self._pick_plan(do_sample, max_new_tokens, mine, input_ids.shape[0])
             if plan.greedy_as_before:
                 plan = None
         else:
             eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
         if input_ids.shape[0] > 1:                                                # only a max_batch > 1 adoption gets here; B = 1 stays below
             return self._generate_rows(input_ids, attention_mask, pixel_values, image_grid_thw, int(max_new_tokens), eos, pad_arg,
-                                       return_dict_in_generate, output_logits, mm_token_type_ids, image_embeds, position_ids, sync_every)
+                                       return_dict_in_generate, output_logits, mm_token_type_ids, image_embeds, position_ids, sync_every, plan)
         ids_cpu, lengths, tables, pos = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids,
                                                       mm_token_type_ids, image_embeds, {})
         L, T = ids_cpu.shape[1], int(max_new_tokens)
@@ -771,14 +800,17 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
                                   tuple(scores[k][None] for k in range(n_new)) if plan is not None and scores is not None else None)
 
     def _generate_rows(self, input_ids, attention_mask, pixel_values, image_grid_thw, T, eos, pad_arg, return_dict_in_generate, output_logits,
-                       mm_token_type_ids, image_embeds, position_ids, sync_every):
+                       mm_token_type_ids, image_embeds, position_ids, sync_every, plan=None):
         """`generate` for 2 <= B <= max_batch left-padded rows (every refusal has been raised): each row is prefilled over its valid tokens
         by `_prefill_row` into its own cache at rows [0, n_b) - no padded key is ever in a cache, so decode needs no mask - then every step
         decodes the B rows from ONE stream of the weights (rgn_lm_gemv_bf16_rows / rgn_lm_gemv_w8_rows, rgn_lm_kv_append_bf16_rows,
         rgn_lm_decode_attention_bf16_rows, rgn_lm_head_argmax_rows, the row kernels at M = B; new ids [T, B] and decode RoPE tables
         [T, B, 128] time-major, so a step's rows are contiguous).  Row b's tokens and fp32 logits are bit for bit those of the B = 1 call
         on row b's unpadded prompt.  The device keeps decoding finished rows (a fixed launch count, no dependence on device data); the host
-        overwrites them with the pad id at assembly (`assemble_sequences`).  Logits of a row past its EOS are not meaningful."""
+        overwrites them with the pad id at assembly (`assemble_sequences`).  Logits of a row past its EOS are not meaningful.
+        With `plan` (a `batch_sampling=True` adoption whose configuration is not greedy as before) the head writes the fp32 [B, V] logits
+        and ONE rgn_lm_pick_rows per step turns them into the B tokens of `new[k]`; `seen` [B, V] is zeroed once and row b marked over
+        ids[b, L - n_b:] only (never the padding).  Finished rows keep being picked; scores past a row's EOS are not meaningful."""
         import ctypes as C
         ids_cpu, lens, tables, pos = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids,
                                                    image_embeds, {}, left=True)
@@ -808,9 +840,35 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         st, ck = _stream(), _lib.check
         pn, pnew = c["n"].data_ptr(), new.data_ptr()
 
-        def pick(k):                                                              # tokens k of the B rows from the normalised rows in c["n"]
-            ck(lib.rgn_lm_head_argmax_rows(_p(head), pn, d, B, V, d, pnew + 8 * B * k, 1, None if logits is None else _p(logits[k]), V,
-                                           _p(c["ws_h"]), ws_h, st), "rgn_lm_head_argmax_rows")
+        scores = None
+        if plan is None:
+            def pick(k):                                                          # tokens k of the B rows from the normalised rows in c["n"]
+                ck(lib.rgn_lm_head_argmax_rows(_p(head), pn, d, B, V, d, pnew + 8 * B * k, 1, None if logits is None else _p(logits[k]), V,
+                                               _p(c["ws_h"]), ws_h, st), "rgn_lm_head_argmax_rows")
+        else:
+            # the pick of this generate, chosen once: lm_head writes the fp32 rows, ONE rgn_lm_pick_rows turns them into the step's id row
+            ws_p = B * lib.rgn_lm_pick_workspace_bytes(V)
+            seen = torch.empty(B, V, dtype=torch.uint8, device=dev)
+            zrows = torch.empty(B, V, dtype=torch.float32, device=dev) if logits is None else None
+            pick_ws = torch.empty((ws_p + 3) // 4, dtype=torch.float32, device=dev)
+            scores = torch.empty(T, B, V, dtype=torch.float32, device=dev) if plan.output_scores else None
+            uni = plan.uniforms
+            if plan.sample and uni is None:                                       # filled before the loop; the kernel has no generator
+                g = plan.generator
+                uni = torch.rand(T, B, dtype=torch.float32, generator=g, device=dev if g is None else g.device).to(dev)
+            ck(lib.rgn_fill_zero(_p(seen), B * V, st), "rgn_fill_zero")
+            for b, n in enumerate(lens):                                          # the row's valid ids only: the padding is never marked
+                ck(lib.rgn_lm_seen_mark(ids.data_ptr() + 8 * (b * L + L - n), n, _p(seen[b]), V, st), "rgn_lm_seen_mark")
+            pen, smp, tmp, tk, tp = plan.penalty, int(plan.sample), plan.temperature, plan.top_k, plan.top_p
+            pu = uni.data_ptr() if plan.sample else None
+
+            def pick(k):
+                z = logits[k] if logits is not None else zrows
+                ck(lib.rgn_lm_head_argmax_rows(_p(head), pn, d, B, V, d, pnew + 8 * B * k, 1, _p(z), V, _p(c["ws_h"]), ws_h, st),
+                   "rgn_lm_head_argmax_rows")
+                ck(lib.rgn_lm_pick_rows(_p(z), V, B, V, _p(seen), V, pen, smp, tmp, tk, tp, None if pu is None else pu + 4 * B * k,
+                                        pnew + 8 * B * k, 1, None if scores is None else _p(scores[k]), V, _p(pick_ws), ws_p, st),
+                   "rgn_lm_pick_rows")
         at = 0
         for b, n in enumerate(lens):                                              # rows prefill one after another on the existing kernels
             k = rows[b].numel() if rows is not None else 0
@@ -863,4 +921,5 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         seq = seq.to(input_ids.device)
         if not return_dict_in_generate:
             return seq
-        return QwenGenerateOutput(seq, tuple(logits[k] for k in range(n_new)) if logits is not None else None)
+        return QwenGenerateOutput(seq, tuple(logits[k] for k in range(n_new)) if logits is not None else None,
+                                  tuple(scores[k] for k in range(n_new)) if scores is not None else None)

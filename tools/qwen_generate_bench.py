@@ -33,6 +33,15 @@ the other.  Per leg: ms per step = (t64 - t1) / 63 of the medians (the B prefill
 
     python tools/qwen_generate_bench.py --batch --no-ab --out profiles/r26_qwen_batched_generate_bench.json
     rocprofv3 --kernel-trace --stats -d DIR -o kt -- python tools/qwen_generate_bench.py --batch --hip-only --no-ab --iters 1
+
+`--batch --sampling` times a `max_batch=8, sampling=True, batch_sampling=True` adoption (bf16 and fp8) at B = 1, 2, 4, 8: a greedy leg and
+the two sampled legs above per B, all alternating in the one process.  Per leg ms per step and tokens per second, and for a sampled leg
+the time the pick adds per step = its step minus the greedy step at that B (B = 1 is the one-sequence path, rgn_lm_pick; B >= 2 runs one
+rgn_lm_pick_rows per step).  Before them `pick_rows_direct`: rgn_lm_pick_rows launched by itself at V = 152064 for B = 1..8 beside
+rgn_lm_pick; `--pick-only` runs only that (no model is built), which is what a kernel trace of the pick needs.
+
+    python tools/qwen_generate_bench.py --batch --sampling --no-ab --out profiles/r27_qwen_batched_sampling_bench.json
+    rocprofv3 --kernel-trace -d DIR -o kt -- python tools/qwen_generate_bench.py --batch --sampling --pick-only --no-ab
 """
 import argparse
 import json
@@ -245,6 +254,100 @@ def batched(a, res):
         print(f"L{L}", json.dumps({k: v for k, v in r.items() if k.endswith("_table")}), flush=True)
 
 
+def pick_rows_direct(res, rounds=20):
+    """rgn_lm_pick_rows by itself at the real vocabulary, B = 1..8 rows of z = 4 randn with 300 seen ids each, beside rgn_lm_pick on one
+    row: median us per launch of `rounds` event-timed launches per arm, the arms alternating.  Under rocprofv3 --kernel-trace the grid
+    size of a lm_pick_rows_kernel dispatch is B x 1024, which is how a trace tells the B of a launch."""
+    from regione_amd import _lib
+    lib = _lib.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    V, R = 152064, 8
+    g = torch.Generator(device="cuda").manual_seed(7)
+    z = (4 * torch.randn(R, V, device="cuda", generator=g)).float()
+    seen = torch.zeros(R, V, dtype=torch.uint8, device="cuda")
+    ids = torch.randint(0, V, (R, 300), device="cuda", generator=g)
+    for b in range(R):
+        _lib.check(lib.rgn_lm_seen_mark(ids[b].data_ptr(), 300, seen[b].data_ptr(), V, st), "rgn_lm_seen_mark")
+    seen0 = seen.clone()
+    uni = torch.rand(R, device="cuda", generator=g)
+    tok = torch.empty(R, dtype=torch.int64, device="cuda")
+    ws = torch.empty(R, V, dtype=torch.float32, device="cuda")
+    nb = lib.rgn_lm_pick_workspace_bytes(V)
+    out = {}
+    for leg, skw in SAMPLED.items():
+        pen, T, k, p = skw["repetition_penalty"], skw["temperature"], skw.get("top_k", 0), skw["top_p"]
+        arms = {"one_row": lambda: lib.rgn_lm_pick(z.data_ptr(), V, seen.data_ptr(), pen, 1, T, k, p, uni.data_ptr(), tok.data_ptr(), None,
+                                                   ws.data_ptr(), nb, st)}
+        for B in range(1, R + 1):
+            arms[f"rows_b{B}"] = lambda B=B: lib.rgn_lm_pick_rows(z.data_ptr(), V, B, V, seen.data_ptr(), V, pen, 1, T, k, p, uni.data_ptr(),
+                                                                  tok.data_ptr(), 1, None, V, ws.data_ptr(), B * nb, st)
+        ts = {name: [] for name in arms}
+        for r in range(rounds + 2):                                              # two warm rounds
+            for name, fn in arms.items():
+                seen.copy_(seen0)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                rc = fn()
+                e1.record()
+                e1.synchronize()
+                _lib.check(rc, name)
+                if r >= 2:
+                    ts[name].append(e0.elapsed_time(e1) * 1e3)
+        out[leg] = {name: {"median_us": statistics.median(v), "min_us": min(v), "max_us": max(v)} for name, v in ts.items()}
+    res["pick_rows_direct"] = dict(V=V, rounds=rounds, stat="event-timed single launches (launch overhead included), arms alternating", **out)
+    print("pick_rows_direct", json.dumps(out), flush=True)
+
+
+def batched_sampling(a, res):
+    """The `--batch --sampling` legs (module docstring): res["L300"], res["L1500"]."""
+    from transformers import Qwen2_5_VLForConditionalGeneration
+    from regione_amd import qwen_text_encoder as QT
+    cfg = full_size_config()
+    torch.manual_seed(0)
+    with torch.device("cuda"):
+        mod = Qwen2_5_VLForConditionalGeneration(cfg).eval()
+    mod = mod.to(torch.bfloat16)
+    torch.cuda.empty_cache()
+    encs = {fmt: QT.HipQwen25VLTextEncoder(mod, weights=fmt, sampling=True, max_batch=max(BATCHES), batch_sampling=True) for fmt in ("bf16", "fp8")}
+    res["batches"], res["weights"], res["sampled_legs"] = list(BATCHES), "both", SAMPLED
+    g = torch.Generator().manual_seed(1)
+    gu = torch.Generator().manual_seed(2)
+    # B = 1 takes the one-sequence path of the adoption (rgn_lm_pick): its uniforms are [n], a batch's [n, B]
+    uni = {(n, B): (torch.rand(n, generator=gu) if B == 1 else torch.rand(n, B, generator=gu)).cuda() for n in (1, NEW) for B in BATCHES}
+    legs = {"greedy": dict(do_sample=False), **SAMPLED}
+    for L in LENGTHS:
+        ids = torch.randint(0, 151000, (max(BATCHES), L), generator=g).cuda()
+        arms = {}
+        for fmt in ("bf16", "fp8"):
+            for B in BATCHES:
+                for leg, skw in legs.items():
+                    for n in (1, NEW):
+                        extra = {} if leg == "greedy" else {"uniforms": uni[(n, B)]}
+                        arms[f"{fmt}_b{B}_{leg}_{n}"] = lambda fmt=fmt, B=B, skw=skw, n=n, extra=extra: encs[fmt].generate(
+                            ids[:B], max_new_tokens=n, eos_token_id=[], **skw, **extra)
+        ts = {k: [] for k in arms}
+        with torch.no_grad():
+            for fn in arms.values():
+                fn()                                                             # warm
+            for _ in range(a.iters):
+                for k, fn in arms.items():                                       # the greedy and the sampled legs alternate
+                    ts[k].append(_ms(fn))
+        r = {"L": L, **{k: _stat(v) for k, v in ts.items()}}
+        for fmt in ("bf16", "fp8"):
+            rows = []
+            for B in BATCHES:
+                per = {leg: (r[f"{fmt}_b{B}_{leg}_{NEW}"]["median_ms"] - r[f"{fmt}_b{B}_{leg}_1"]["median_ms"]) / (NEW - 1) for leg in legs}
+                for leg in legs:
+                    row = dict(leg=leg, B=B, ms_per_step=per[leg], tokens_per_s=B * 1e3 / per[leg])
+                    if leg != "greedy":
+                        row["pick_adds_ms_per_step"] = per[leg] - per["greedy"]
+                        row["over_the_greedy_step"] = per[leg] / per["greedy"]
+                    rows.append(row)
+            r[f"{fmt}_table"] = rows
+        res[f"L{L}"] = r
+        print(f"L{L}", json.dumps({k: v for k, v in r.items() if k.endswith("_table")}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
@@ -256,6 +359,7 @@ def main():
     ap.add_argument("--weights", choices=("bf16", "fp8", "both"), default="bf16", help="format of the layers' projection matrices")
     ap.add_argument("--sampling", action="store_true", help="adopt with sampling=True and time two sampled legs beside the greedy one")
     ap.add_argument("--batch", action="store_true", help="time a max_batch=8 adoption at B = 1, 2, 4, 8 beside a default one (bf16 and fp8)")
+    ap.add_argument("--pick-only", action="store_true", help="with --batch --sampling: only the direct rgn_lm_pick_rows launches (for a kernel trace)")
     a = ap.parse_args()
     from regione_amd import build
     sha = build.csrc_hash()
@@ -292,7 +396,13 @@ def main():
         if a.ab_out:
             with open(a.ab_out, "w") as f:
                 f.write("\n".join(lines) + "\n")
-    if a.batch:
+    if a.batch and a.sampling:
+        res["stat"] = ("median and min / max of warm, synchronised runs, the greedy and the sampled legs alternating; ms per step = "
+                       "(t64 - t1) / 63 of the medians; tokens per second = B / that; pick_adds = the sampled step minus the greedy step at that B")
+        pick_rows_direct(res)
+        if not a.pick_only:
+            batched_sampling(a, res)
+    elif a.batch:
         res["stat"] = ("median and min / max of warm, synchronised runs, every leg alternating; ms per step = (t64 - t1) / 63 of the medians; "
                        "tokens per second = B / that")
         batched(a, res)
