@@ -554,6 +554,8 @@ size_t rgn_lm_head_workspace_bytes(int V);
  * row b alone, for every B in 1..8 - the same per-lane fmaf chain in the same k order, the same wave butterfly, the same roundings.  No
  * atomics, fixed reduction orders, a repeated call is bit-identical.  The row kernels (rgn_rms_norm_rows, rgn_mrope_bf16, rgn_swiglu_bf16,
  * rgn_text_embed) run at M = B.  Per-sequence lengths are HOST arrays of B ints that travel to the kernel by value: no device read, no upload.
+ * B = 1 of a `_rows` entry IS the one-sequence entry above: the same checks, the same kernels with the same grid, so a decode loop calls
+ * the `_rows` entries for every B.  No stride is read at B = 1 (one row has none), so the stride conditions below bind from B = 2 on.
  *
  * Y[b, n] = the layer of rgn_lm_gemv_bf16 applied to row b of X, b < B.  X [B, ldx], Y [B, ldy], resid [B, ldr] bf16; strides in elements,
  * multiples of 8, ldx >= K, ldy >= N, ldr >= N; Y may be resid.  Rows >= B and columns >= N are never written.  A weight vector is loaded
@@ -570,7 +572,7 @@ int rgn_lm_gemv_w8_rows(const void* W8, const float* wscale, const void* X, int 
 int rgn_lm_head_argmax_rows(const void* W, const void* X, int ldx, int B, int V, int K, void* token_out, int token_stride, float* logits_out,
                             int ldl, void* workspace, size_t workspace_bytes, void* stream);
 /* Row b of QKV [B, ld] (after rgn_mrope_bf16) into cache b = cache + b * cache_stride (elements; a multiple of 8, >= cap 2 Hkv 128) at row
- * row0_host[b], 0 <= row0_host[b] < cap <= 4096, bit for bit. */
+ * row0_host[b], 0 <= row0_host[b] < cap <= 4096, bit for bit.  B = 1 is rgn_lm_kv_append_bf16 with L = 1. */
 int rgn_lm_kv_append_bf16_rows(const void* QKV, int ld, void* cache, size_t cache_stride, int cap, const int* row0_host, int B, int Hq, int Hkv,
                                void* stream);
 /* B query tokens, query b (row b of Q [B, ldq]: the q columns of its QKV row) against the first n_host[b] rows of cache b; O [B, ldo].
@@ -614,6 +616,7 @@ size_t rgn_lm_pick_workspace_bytes(int V);
  * alone, for every B in 1..8 (both kernels run the same device function).  Rows >= B and columns >= V of every buffer are never written,
  * the logits never at all.  1 <= B <= RGN_LM_MAX_BATCH; ldl >= V, lds >= V (with scores_out), seen_stride >= V, token_stride >= 1; the
  * ranges and alignments of rgn_lm_pick; scores_out may not overlap the logits; workspace_bytes >= B * rgn_lm_pick_workspace_bytes(V).
+ * B = 1 is rgn_lm_pick itself (its one-block launch; no stride is read), except that this entry still refuses any overlap.
  * Every refusal is raised before the launch.  The prompt ids of row b are marked by rgn_lm_seen_mark on seen + b * seen_stride. */
 int rgn_lm_pick_rows(const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty, int sample, float temperature,
                      int top_k, double top_p, const float* uniform, void* token_out, int token_stride, float* scores_out, int lds,

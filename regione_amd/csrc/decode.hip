@@ -20,6 +20,8 @@
 //   lm_head_finalize_rows_kernel, lm_kv_append_rows_kernel, lm_decode_attention_rows_kernel, lm_decode_merge_rows_kernel
 //                               the batch on a grid axis; per-sequence cache lengths travel by value (no device read, no upload)
 //   lm_pick_rows_kernel         the block of lm_pick_kernel once per row (blockIdx.x = b), each on a CU of its own: the same device function
+// That invariant is what the host side rests on: an operation is ONE implementation over 1 <= B <= 8 rows, reached through its `_rows`
+// entry, which launches the one-row kernels at B == 1 and the `_rows` kernels from B = 2 on; the one-row entry is its B = 1 case.
 // No atomics; every reduction has a fixed order (lanes: the butterfly of wave_sum; k, keys and slices: ascending), so a repeated call is
 // bit-identical.
 #include <math.h>
@@ -819,72 +821,145 @@ static void launch_gemv_rows(int B, int N, hipStream_t st, Args... args) {
     const size_t lds = (size_t)B * rows_kc<W8>() * sizeof(float);
     switch (B) {
 #define RGN_ROWS_CASE(b) case b: hipLaunchKernelGGL((lm_gemv_rows_kernel<b, W8, ARGMAX>), grid, block, lds, st, args...); break;
-        RGN_ROWS_CASE(1) RGN_ROWS_CASE(2) RGN_ROWS_CASE(3) RGN_ROWS_CASE(4) RGN_ROWS_CASE(5) RGN_ROWS_CASE(6) RGN_ROWS_CASE(7) RGN_ROWS_CASE(8)
+        RGN_ROWS_CASE(2) RGN_ROWS_CASE(3) RGN_ROWS_CASE(4) RGN_ROWS_CASE(5) RGN_ROWS_CASE(6) RGN_ROWS_CASE(7) RGN_ROWS_CASE(8)
 #undef RGN_ROWS_CASE
     }
 }
 
-extern "C" {
-
+// ---- the entries ------------------------------------------------------------------------------------------------------------------------
+// Every operation is written once, over 1 <= B <= RGN_LM_MAX_BATCH rows, under the name of the public entry that called it (`who`, the
+// prefix of its messages).  B == 1 launches the one-row kernels and reads no stride, so stride conditions bind from B = 2 on.
 static inline bool dal16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+static inline bool batch_ok(int B) { return B >= 1 && B <= RGN_LM_MAX_BATCH; }
+static int bad(const char* who, const char* what) { snprintf(g_err, sizeof(g_err), "%s: %s", who, what); return RGN_E_BADARG; }
 
-int rgn_lm_gemv_bf16(const void* W, const void* x, const void* bias, const void* resid, void* y, int N, int K, void* stream) {
-    if (!W || !x || !y || N < 1 || K < 64) return fail(RGN_E_BADARG, "lm_gemv: bad argument (W, x, y non-null; N >= 1; K >= 64)");
-    if (K % 64) return fail(RGN_E_BADARG, "lm_gemv: K must be a multiple of 64");
-    if (!dal16(W) || !dal16(x)) return fail(RGN_E_BADARG, "lm_gemv: W and x must be 16-byte aligned");
-    if (((uintptr_t)y | (uintptr_t)bias | (uintptr_t)resid) & 1u) return fail(RGN_E_BADARG, "lm_gemv: y, bias and resid must be 2-byte aligned");
-    hipLaunchKernelGGL((lm_gemv_kernel<false>), dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)W, (const uint16_t*)x,
-                       (const uint16_t*)bias, (const uint16_t*)resid, (uint16_t*)y, (float*)nullptr, (float*)nullptr, (int*)nullptr, N, K);
-    return check_launch("lm_gemv_kernel");
+// The linear layer in either weight format: W8 reads e4m3fn bytes with `wscale`, else W is bf16 and wscale null.
+template <bool W8>
+static int gemv(const char* who, const void* W, const float* wscale, const void* X, int ldx, const void* bias, const void* resid, int ldr,
+                void* Y, int ldy, int B, int N, int K, void* stream) {
+    if (!W || (W8 && !wscale) || !X || !Y || N < 1 || K < 64)
+        return bad(who, W8 ? "bad argument (W8, wscale, X, Y non-null; N >= 1; K >= 64)" : "bad argument (W, X, Y non-null; N >= 1; K >= 64)");
+    if (!batch_ok(B)) return bad(who, "B outside [1, 8]");
+    if (K % (W8 ? 16 : 64)) return bad(who, W8 ? "K must be a multiple of 16" : "K must be a multiple of 64");
+    if (B > 1 && (ldx % 8 || ldy % 8 || ldx < K || ldy < N || (resid && (ldr % 8 || ldr < N))))
+        return bad(who, "strides must be multiples of 8, ldx >= K, ldy >= N, ldr >= N");
+    if (!dal16(W) || !dal16(wscale) || !dal16(X) || (W8 && !dal16(Y)))
+        return bad(who, W8 ? "W8, wscale, X and Y must be 16-byte aligned" : "W and X must be 16-byte aligned");
+    if (((uintptr_t)Y | (uintptr_t)bias | (uintptr_t)resid) & 1u)
+        return bad(who, W8 ? "bias and resid must be 2-byte aligned" : "Y, bias and resid must be 2-byte aligned");
+    const uint16_t *x = (const uint16_t*)X, *bs = (const uint16_t*)bias, *rs = (const uint16_t*)resid;
+    if (B > 1) {
+        launch_gemv_rows<W8, false>(B, N, (hipStream_t)stream, (const uint8_t*)W, wscale, x, ldx, bs, rs, ldr, (uint16_t*)Y, ldy, (float*)nullptr, 0,
+                                    (float*)nullptr, (int*)nullptr, 0, N, K);
+        return check_launch("lm_gemv_rows_kernel");
+    }
+    if constexpr (W8) {
+        constexpr int rows = 4 * W8_ROWS;
+        hipLaunchKernelGGL((lm_gemv_w8_kernel<W8_ROWS, W8_U>), dim3((N + rows - 1) / rows), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)W,
+                           wscale, x, bs, rs, (uint16_t*)Y, N, K);
+    } else {
+        hipLaunchKernelGGL((lm_gemv_kernel<false>), dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)W, x, bs, rs, (uint16_t*)Y,
+                           (float*)nullptr, (float*)nullptr, (int*)nullptr, N, K);
+    }
+    return check_launch(W8 ? "lm_gemv_w8_kernel" : "lm_gemv_kernel");
 }
 
+extern "C" {
+
+int rgn_lm_gemv_bf16(const void* W, const void* x, const void* bias, const void* resid, void* y, int N, int K, void* stream) {
+    return gemv<false>("lm_gemv", W, nullptr, x, 0, bias, resid, 0, y, 0, 1, N, K, stream);
+}
+int rgn_lm_gemv_bf16_rows(const void* W, const void* X, int ldx, const void* bias, const void* resid, int ldr, void* Y, int ldy, int B, int N,
+                          int K, void* stream) {
+    return gemv<false>("lm_gemv_rows", W, nullptr, X, ldx, bias, resid, ldr, Y, ldy, B, N, K, stream);
+}
 int rgn_lm_gemv_w8(const void* W8, const float* wscale, const void* x, const void* bias, const void* resid, void* y, int N, int K,
                    void* stream) {
-    if (!W8 || !wscale || !x || !y || N < 1 || K < 64)
-        return fail(RGN_E_BADARG, "lm_gemv_w8: bad argument (W8, wscale, x, y non-null; N >= 1; K >= 64)");
-    if (K % 16) return fail(RGN_E_BADARG, "lm_gemv_w8: K must be a multiple of 16");
-    if (!dal16(W8) || !dal16(wscale) || !dal16(x) || !dal16(y)) return fail(RGN_E_BADARG, "lm_gemv_w8: W8, wscale, x and y must be 16-byte aligned");
-    if (((uintptr_t)bias | (uintptr_t)resid) & 1u) return fail(RGN_E_BADARG, "lm_gemv_w8: bias and resid must be 2-byte aligned");
-    constexpr int rows = 4 * W8_ROWS;
-    hipLaunchKernelGGL((lm_gemv_w8_kernel<W8_ROWS, W8_U>), dim3((N + rows - 1) / rows), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)W8,
-                       wscale, (const uint16_t*)x, (const uint16_t*)bias, (const uint16_t*)resid, (uint16_t*)y, N, K);
-    return check_launch("lm_gemv_w8_kernel");
+    return gemv<true>("lm_gemv_w8", W8, wscale, x, 0, bias, resid, 0, y, 0, 1, N, K, stream);
+}
+int rgn_lm_gemv_w8_rows(const void* W8, const float* wscale, const void* X, int ldx, const void* bias, const void* resid, int ldr, void* Y,
+                        int ldy, int B, int N, int K, void* stream) {
+    return gemv<true>("lm_gemv_w8_rows", W8, wscale, X, ldx, bias, resid, ldr, Y, ldy, B, N, K, stream);
 }
 
 static inline int head_parts(int V) { return (V + 3) / 4; }                 // lm_gemv_kernel<true>: 4 rows per block
 
 size_t rgn_lm_head_workspace_bytes(int V) { return V < 1 ? 0 : (size_t)head_parts(V) * (sizeof(float) + sizeof(int)); }
 
+static int head_argmax(const char* who, const void* W, const void* X, int ldx, int B, int V, int K, void* token_out, int token_stride,
+                       float* logits_out, int ldl, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!W || !X || !token_out || !workspace || V < 1 || K < 64)
+        return bad(who, "bad argument (W, X, token_out, workspace non-null; V >= 1; K >= 64)");
+    if (!batch_ok(B)) return bad(who, "B outside [1, 8]");
+    if (K % 64) return bad(who, "K must be a multiple of 64");
+    if (B > 1 && (ldx % 8 || ldx < K || token_stride < 1 || (logits_out && ldl < V)))
+        return bad(who, "ldx must be a multiple of 8 and >= K, token_stride >= 1, ldl >= V");
+    if (!dal16(W) || !dal16(X)) return bad(who, "W and X must be 16-byte aligned");
+    if (((uintptr_t)token_out & 7u) || ((uintptr_t)logits_out & 3u) || ((uintptr_t)workspace & 3u))
+        return bad(who, "token_out must be 8-byte, logits_out and workspace 4-byte aligned");
+    if (workspace_bytes < (size_t)B * rgn_lm_head_workspace_bytes(V)) return bad(who, "workspace smaller than B rgn_lm_head_workspace_bytes(V)");
+    const int np = B == 1 ? head_parts(V) : (V + 4 * ROWS_R - 1) / (4 * ROWS_R);        // the blocks of the product, each with one maximum
+    float* pv = (float*)workspace;
+    int* pi = (int*)(pv + (size_t)B * np);
+    const hipStream_t st = (hipStream_t)stream;
+    if (B == 1) {
+        hipLaunchKernelGGL((lm_gemv_kernel<true>), dim3(np), dim3(256), 0, st, (const uint16_t*)W, (const uint16_t*)X, (const uint16_t*)nullptr,
+                           (const uint16_t*)nullptr, (uint16_t*)nullptr, logits_out, pv, pi, V, K);
+        hipLaunchKernelGGL(lm_head_finalize_kernel, dim3(1), dim3(1024), 0, st, (const float*)pv, (const int*)pi, np, (int64_t*)token_out);
+    } else {
+        launch_gemv_rows<false, true>(B, V, st, (const uint8_t*)W, (const float*)nullptr, (const uint16_t*)X, ldx, (const uint16_t*)nullptr,
+                                      (const uint16_t*)nullptr, 0, (uint16_t*)nullptr, 0, logits_out, ldl, pv, pi, np, V, K);
+        hipLaunchKernelGGL(lm_head_finalize_rows_kernel, dim3(B), dim3(1024), 0, st, (const float*)pv, (const int*)pi, np, (int64_t*)token_out,
+                           token_stride);
+    }
+    return check_launch(who);
+}
+
 int rgn_lm_head_argmax(const void* W, const void* x, int V, int K, void* token_out, float* logits_out, void* workspace,
                        size_t workspace_bytes, void* stream) {
-    if (!W || !x || !token_out || !workspace || V < 1 || K < 64)
-        return fail(RGN_E_BADARG, "lm_head_argmax: bad argument (W, x, token_out, workspace non-null; V >= 1; K >= 64)");
-    if (K % 64) return fail(RGN_E_BADARG, "lm_head_argmax: K must be a multiple of 64");
-    if (!dal16(W) || !dal16(x)) return fail(RGN_E_BADARG, "lm_head_argmax: W and x must be 16-byte aligned");
-    if (((uintptr_t)token_out & 7u) || ((uintptr_t)logits_out & 3u) || ((uintptr_t)workspace & 3u))
-        return fail(RGN_E_BADARG, "lm_head_argmax: token_out must be 8-byte, logits_out and workspace 4-byte aligned");
-    if (workspace_bytes < rgn_lm_head_workspace_bytes(V)) return fail(RGN_E_BADARG, "lm_head_argmax: workspace smaller than rgn_lm_head_workspace_bytes(V)");
-    const int np = head_parts(V);
-    float* pv = (float*)workspace;
-    int* pi = (int*)(pv + np);
-    const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL((lm_gemv_kernel<true>), dim3(np), dim3(256), 0, st, (const uint16_t*)W, (const uint16_t*)x, (const uint16_t*)nullptr,
-                       (const uint16_t*)nullptr, (uint16_t*)nullptr, logits_out, pv, pi, V, K);
-    hipLaunchKernelGGL(lm_head_finalize_kernel, dim3(1), dim3(1024), 0, st, (const float*)pv, (const int*)pi, np, (int64_t*)token_out);
-    return check_launch("lm_head_argmax");
+    return head_argmax("lm_head_argmax", W, x, 0, 1, V, K, token_out, 0, logits_out, 0, workspace, workspace_bytes, stream);
+}
+int rgn_lm_head_argmax_rows(const void* W, const void* X, int ldx, int B, int V, int K, void* token_out, int token_stride, float* logits_out,
+                            int ldl, void* workspace, size_t workspace_bytes, void* stream) {
+    return head_argmax("lm_head_argmax_rows", W, X, ldx, B, V, K, token_out, token_stride, logits_out, ldl, workspace, workspace_bytes, stream);
+}
+
+// L rows of QKV into each of B caches from row row0[b] on.  The two public forms are its two edges: L rows into ONE cache (the prefill;
+// lm_kv_append_kernel, which is also what one decoded row takes) and ONE row into each of B >= 2 caches (lm_kv_append_rows_kernel).
+static int kv_append(const char* who, bool rows, const void* QKV, int ld, void* cache, size_t cache_stride, int cap, const int* row0, int B, int L,
+                     int Hq, int Hkv, void* stream) {
+    if (!QKV || !cache || !row0 || L < 1 || (!rows && row0[0] < 0) || Hq < 1 || Hkv < 1 || Hq > 1024 || Hkv > 1024 || ld < (Hq + 2 * Hkv) * 128 || ld % 8)
+        return bad(who, rows ? "bad argument (QKV, cache, row0 non-null; 1 <= Hq, Hkv <= 1024; ld >= (Hq + 2 Hkv) 128, a multiple of 8)"
+                             : "bad argument (QKV, cache non-null; L, row0 >= 0; 1 <= Hq, Hkv <= 1024; ld >= (Hq + 2 Hkv) 128, a multiple of 8)");
+    if (!batch_ok(B)) return bad(who, "B outside [1, 8]");
+    const int width = 2 * Hkv * 128;
+    if (cap < 1 || cap > DEC_MAX_N || (B > 1 && (cache_stride % 8 || cache_stride < (size_t)cap * width)))
+        return bad(who, rows ? "caches of 1 <= cap <= 4096 rows, cache_stride >= cap 2 Hkv 128 elements, a multiple of 8"
+                             : "a cache of 1 <= cap <= 4096 rows");
+    LmRows r{};
+    for (int b = 0; b < B; ++b) {
+        if (row0[b] < 0 || row0[b] > cap - L) return bad(who, rows ? "row0[b] outside [0, cap)" : "rows [row0, row0 + L) must lie in [0, cap)");
+        r.v[b] = row0[b];
+    }
+    if (!dal16(QKV) || !dal16(cache)) return bad(who, "QKV and cache must be 16-byte aligned");
+    if (B == 1) {
+        const size_t items = (size_t)L * (width / 8), g = (items + 255) / 256;
+        hipLaunchKernelGGL(lm_kv_append_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)QKV,
+                           ld, Hq * 128, (uint16_t*)cache, r.v[0], L, width);
+        return check_launch("lm_kv_append_kernel");
+    }
+    hipLaunchKernelGGL(lm_kv_append_rows_kernel, dim3((width / 8 + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)QKV, ld,
+                       Hq * 128, (uint16_t*)cache, cache_stride, r, width);
+    return check_launch("lm_kv_append_rows_kernel");
 }
 
 int rgn_lm_kv_append_bf16(const void* QKV, int ld, void* cache, int cap, int row0, int L, int Hq, int Hkv, void* stream) {
     if (L == 0) return 0;
-    if (!QKV || !cache || L < 0 || row0 < 0 || Hq < 1 || Hkv < 1 || Hq > 1024 || Hkv > 1024 || ld < (Hq + 2 * Hkv) * 128 || ld % 8)
-        return fail(RGN_E_BADARG, "lm_kv_append: bad argument (QKV, cache non-null; L, row0 >= 0; 1 <= Hq, Hkv <= 1024; ld >= (Hq + 2 Hkv) 128, a multiple of 8)");
-    if (cap < 1 || cap > DEC_MAX_N || row0 > cap - L) return fail(RGN_E_BADARG, "lm_kv_append: rows [row0, row0 + L) must lie in a cache of 1 <= cap <= 4096 rows");
-    if (!dal16(QKV) || !dal16(cache)) return fail(RGN_E_BADARG, "lm_kv_append: QKV and cache must be 16-byte aligned");
-    const int width = 2 * Hkv * 128;
-    const size_t items = (size_t)L * (width / 8), g = (items + 255) / 256;
-    hipLaunchKernelGGL(lm_kv_append_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)QKV, ld,
-                       Hq * 128, (uint16_t*)cache, row0, L, width);
-    return check_launch("lm_kv_append_kernel");
+    return kv_append("lm_kv_append", false, QKV, ld, cache, 0, cap, &row0, 1, L, Hq, Hkv, stream);
+}
+int rgn_lm_kv_append_bf16_rows(const void* QKV, int ld, void* cache, size_t cache_stride, int cap, const int* row0_host, int B, int Hq, int Hkv,
+                               void* stream) {
+    return kv_append("lm_kv_append_rows", true, QKV, ld, cache, cache_stride, cap, row0_host, B, 1, Hq, Hkv, stream);
 }
 
 size_t rgn_lm_decode_attention_workspace_bytes(int Hq, int n) {
@@ -892,127 +967,47 @@ size_t rgn_lm_decode_attention_workspace_bytes(int Hq, int n) {
     return (size_t)Hq * ((n + DEC_SLICE - 1) / DEC_SLICE) * DEC_PART * sizeof(float);
 }
 
-int rgn_lm_decode_attention_bf16(const void* q, const void* cache, void* O, int n, int Hq, int Hkv, float scale, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-    if (!q || !cache || !O || !workspace || Hkv < 1 || Hq < Hkv || Hq > 1024 || !(scale > 0.f) || !(scale < INFINITY))
-        return fail(RGN_E_BADARG, "lm_decode_attention: bad argument (q, cache, O, workspace non-null; 1 <= Hkv <= Hq <= 1024; 0 < scale < inf)");
-    if (Hq % Hkv || Hq / Hkv > DEC_MAX_GROUP) return fail(RGN_E_BADARG, "lm_decode_attention: Hq % Hkv != 0 or Hq / Hkv > 8");
-    if (n < 1 || n > DEC_MAX_N) return fail(RGN_E_BADARG, "lm_decode_attention: n outside [1, 4096]");
-    if (!dal16(q) || !dal16(cache) || !dal16(O) || !dal16(workspace))
-        return fail(RGN_E_BADARG, "lm_decode_attention: q, cache, O and workspace must be 16-byte aligned");
-    if (workspace_bytes < rgn_lm_decode_attention_workspace_bytes(Hq, n))
-        return fail(RGN_E_BADARG, "lm_decode_attention: workspace smaller than rgn_lm_decode_attention_workspace_bytes(Hq, n)");
-    const int ns = (n + DEC_SLICE - 1) / DEC_SLICE;
-    const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(lm_decode_attention_kernel, dim3(ns, Hkv), dim3(256), 0, st, (const uint16_t*)q, (const uint16_t*)cache, n, Hq, Hkv, scale,
-                       (float*)workspace, ns);
-    hipLaunchKernelGGL(lm_decode_merge_kernel, dim3(Hq), dim3(128), 0, st, (const float*)workspace, ns, (uint16_t*)O);
-    return check_launch("lm_decode_attention");
-}
-
-// ---- the entries over B <= RGN_LM_MAX_BATCH sequences -----------------------------------------------------------------------------------
-static inline bool batch_ok(int B) { return B >= 1 && B <= RGN_LM_MAX_BATCH; }
-
-int rgn_lm_gemv_bf16_rows(const void* W, const void* X, int ldx, const void* bias, const void* resid, int ldr, void* Y, int ldy, int B, int N,
-                          int K, void* stream) {
-    if (!W || !X || !Y || N < 1 || K < 64) return fail(RGN_E_BADARG, "lm_gemv_rows: bad argument (W, X, Y non-null; N >= 1; K >= 64)");
-    if (!batch_ok(B)) return fail(RGN_E_BADARG, "lm_gemv_rows: B outside [1, 8]");
-    if (K % 64) return fail(RGN_E_BADARG, "lm_gemv_rows: K must be a multiple of 64");
-    if (ldx % 8 || ldy % 8 || ldx < K || ldy < N || (resid && (ldr % 8 || ldr < N)))
-        return fail(RGN_E_BADARG, "lm_gemv_rows: strides must be multiples of 8, ldx >= K, ldy >= N, ldr >= N");
-    if (!dal16(W) || !dal16(X)) return fail(RGN_E_BADARG, "lm_gemv_rows: W and X must be 16-byte aligned");
-    if (((uintptr_t)Y | (uintptr_t)bias | (uintptr_t)resid) & 1u) return fail(RGN_E_BADARG, "lm_gemv_rows: Y, bias and resid must be 2-byte aligned");
-    launch_gemv_rows<false, false>(B, N, (hipStream_t)stream, (const uint8_t*)W, (const float*)nullptr, (const uint16_t*)X, ldx,
-                                   (const uint16_t*)bias, (const uint16_t*)resid, ldr, (uint16_t*)Y, ldy, (float*)nullptr, 0, (float*)nullptr,
-                                   (int*)nullptr, 0, N, K);
-    return check_launch("lm_gemv_rows_kernel");
-}
-
-int rgn_lm_gemv_w8_rows(const void* W8, const float* wscale, const void* X, int ldx, const void* bias, const void* resid, int ldr, void* Y,
-                        int ldy, int B, int N, int K, void* stream) {
-    if (!W8 || !wscale || !X || !Y || N < 1 || K < 64)
-        return fail(RGN_E_BADARG, "lm_gemv_w8_rows: bad argument (W8, wscale, X, Y non-null; N >= 1; K >= 64)");
-    if (!batch_ok(B)) return fail(RGN_E_BADARG, "lm_gemv_w8_rows: B outside [1, 8]");
-    if (K % 16) return fail(RGN_E_BADARG, "lm_gemv_w8_rows: K must be a multiple of 16");
-    if (ldx % 8 || ldy % 8 || ldx < K || ldy < N || (resid && (ldr % 8 || ldr < N)))
-        return fail(RGN_E_BADARG, "lm_gemv_w8_rows: strides must be multiples of 8, ldx >= K, ldy >= N, ldr >= N");
-    if (!dal16(W8) || !dal16(wscale) || !dal16(X) || !dal16(Y))
-        return fail(RGN_E_BADARG, "lm_gemv_w8_rows: W8, wscale, X and Y must be 16-byte aligned");
-    if (((uintptr_t)bias | (uintptr_t)resid) & 1u) return fail(RGN_E_BADARG, "lm_gemv_w8_rows: bias and resid must be 2-byte aligned");
-    launch_gemv_rows<true, false>(B, N, (hipStream_t)stream, (const uint8_t*)W8, wscale, (const uint16_t*)X, ldx, (const uint16_t*)bias,
-                                  (const uint16_t*)resid, ldr, (uint16_t*)Y, ldy, (float*)nullptr, 0, (float*)nullptr, (int*)nullptr, 0, N, K);
-    return check_launch("lm_gemv_rows_kernel");
-}
-
-int rgn_lm_head_argmax_rows(const void* W, const void* X, int ldx, int B, int V, int K, void* token_out, int token_stride, float* logits_out,
-                            int ldl, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!W || !X || !token_out || !workspace || V < 1 || K < 64)
-        return fail(RGN_E_BADARG, "lm_head_argmax_rows: bad argument (W, X, token_out, workspace non-null; V >= 1; K >= 64)");
-    if (!batch_ok(B)) return fail(RGN_E_BADARG, "lm_head_argmax_rows: B outside [1, 8]");
-    if (K % 64) return fail(RGN_E_BADARG, "lm_head_argmax_rows: K must be a multiple of 64");
-    if (ldx % 8 || ldx < K || token_stride < 1 || (logits_out && ldl < V))
-        return fail(RGN_E_BADARG, "lm_head_argmax_rows: ldx must be a multiple of 8 and >= K, token_stride >= 1, ldl >= V");
-    if (!dal16(W) || !dal16(X)) return fail(RGN_E_BADARG, "lm_head_argmax_rows: W and X must be 16-byte aligned");
-    if (((uintptr_t)token_out & 7u) || ((uintptr_t)logits_out & 3u) || ((uintptr_t)workspace & 3u))
-        return fail(RGN_E_BADARG, "lm_head_argmax_rows: token_out must be 8-byte, logits_out and workspace 4-byte aligned");
-    if (workspace_bytes < (size_t)B * rgn_lm_head_workspace_bytes(V))
-        return fail(RGN_E_BADARG, "lm_head_argmax_rows: workspace smaller than B rgn_lm_head_workspace_bytes(V)");
-    const int np = (V + 4 * ROWS_R - 1) / (4 * ROWS_R);
-    float* pv = (float*)workspace;
-    int* pi = (int*)(pv + (size_t)B * np);
-    const hipStream_t st = (hipStream_t)stream;
-    launch_gemv_rows<false, true>(B, V, st, (const uint8_t*)W, (const float*)nullptr, (const uint16_t*)X, ldx, (const uint16_t*)nullptr,
-                                  (const uint16_t*)nullptr, 0, (uint16_t*)nullptr, 0, logits_out, ldl, pv, pi, np, V, K);
-    hipLaunchKernelGGL(lm_head_finalize_rows_kernel, dim3(B), dim3(1024), 0, st, (const float*)pv, (const int*)pi, np, (int64_t*)token_out,
-                       token_stride);
-    return check_launch("lm_head_argmax_rows");
-}
-
-int rgn_lm_kv_append_bf16_rows(const void* QKV, int ld, void* cache, size_t cache_stride, int cap, const int* row0_host, int B, int Hq, int Hkv,
-                               void* stream) {
-    if (!QKV || !cache || !row0_host || Hq < 1 || Hkv < 1 || Hq > 1024 || Hkv > 1024 || ld < (Hq + 2 * Hkv) * 128 || ld % 8)
-        return fail(RGN_E_BADARG, "lm_kv_append_rows: bad argument (QKV, cache, row0 non-null; 1 <= Hq, Hkv <= 1024; ld >= (Hq + 2 Hkv) 128, a multiple of 8)");
-    if (!batch_ok(B)) return fail(RGN_E_BADARG, "lm_kv_append_rows: B outside [1, 8]");
-    const int width = 2 * Hkv * 128;
-    if (cap < 1 || cap > DEC_MAX_N || cache_stride % 8 || cache_stride < (size_t)cap * width)
-        return fail(RGN_E_BADARG, "lm_kv_append_rows: caches of 1 <= cap <= 4096 rows, cache_stride >= cap 2 Hkv 128 elements, a multiple of 8");
-    LmRows r{};
-    for (int b = 0; b < B; ++b) {
-        if (row0_host[b] < 0 || row0_host[b] >= cap) return fail(RGN_E_BADARG, "lm_kv_append_rows: row0[b] outside [0, cap)");
-        r.v[b] = row0_host[b];
-    }
-    if (!dal16(QKV) || !dal16(cache)) return fail(RGN_E_BADARG, "lm_kv_append_rows: QKV and cache must be 16-byte aligned");
-    hipLaunchKernelGGL(lm_kv_append_rows_kernel, dim3((width / 8 + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)QKV, ld,
-                       Hq * 128, (uint16_t*)cache, cache_stride, r, width);
-    return check_launch("lm_kv_append_rows_kernel");
-}
-
-int rgn_lm_decode_attention_bf16_rows(const void* Q, int ldq, const void* cache, size_t cache_stride, void* O, int ldo, const int* n_host, int B,
-                                      int Hq, int Hkv, float scale, void* workspace, size_t workspace_bytes, void* stream) {
+static int decode_attention(const char* who, const void* Q, int ldq, const void* cache, size_t cache_stride, void* O, int ldo, const int* n_host,
+                            int B, int Hq, int Hkv, float scale, void* workspace, size_t workspace_bytes, void* stream) {
     if (!Q || !cache || !O || !n_host || !workspace || Hkv < 1 || Hq < Hkv || Hq > 1024 || !(scale > 0.f) || !(scale < INFINITY))
-        return fail(RGN_E_BADARG, "lm_decode_attention_rows: bad argument (Q, cache, O, n, workspace non-null; 1 <= Hkv <= Hq <= 1024; 0 < scale < inf)");
-    if (Hq % Hkv || Hq / Hkv > DEC_MAX_GROUP) return fail(RGN_E_BADARG, "lm_decode_attention_rows: Hq % Hkv != 0 or Hq / Hkv > 8");
-    if (!batch_ok(B)) return fail(RGN_E_BADARG, "lm_decode_attention_rows: B outside [1, 8]");
+        return bad(who, "bad argument (Q, cache, O, n, workspace non-null; 1 <= Hkv <= Hq <= 1024; 0 < scale < inf)");
+    if (Hq % Hkv || Hq / Hkv > DEC_MAX_GROUP) return bad(who, "Hq % Hkv != 0 or Hq / Hkv > 8");
+    if (!batch_ok(B)) return bad(who, "B outside [1, 8]");
     LmRows nb{};
     int nmax = 0;
     for (int b = 0; b < B; ++b) {
-        if (n_host[b] < 1 || n_host[b] > DEC_MAX_N) return fail(RGN_E_BADARG, "lm_decode_attention_rows: n[b] outside [1, 4096]");
+        if (n_host[b] < 1 || n_host[b] > DEC_MAX_N) return bad(who, "n[b] outside [1, 4096]");
         nb.v[b] = n_host[b];
         nmax = n_host[b] > nmax ? n_host[b] : nmax;
     }
-    if (ldq % 8 || ldo % 8 || ldq < Hq * 128 || ldo < Hq * 128 || cache_stride % 8 || cache_stride < (size_t)nmax * 2 * Hkv * 128)
-        return fail(RGN_E_BADARG, "lm_decode_attention_rows: strides must be multiples of 8, ldq and ldo >= Hq 128, cache_stride >= max n 2 Hkv 128");
-    if (!dal16(Q) || !dal16(cache) || !dal16(O) || !dal16(workspace))
-        return fail(RGN_E_BADARG, "lm_decode_attention_rows: Q, cache, O and workspace must be 16-byte aligned");
+    if (B > 1 && (ldq % 8 || ldo % 8 || ldq < Hq * 128 || ldo < Hq * 128 || cache_stride % 8 || cache_stride < (size_t)nmax * 2 * Hkv * 128))
+        return bad(who, "strides must be multiples of 8, ldq and ldo >= Hq 128, cache_stride >= max n 2 Hkv 128");
+    if (!dal16(Q) || !dal16(cache) || !dal16(O) || !dal16(workspace)) return bad(who, "Q, cache, O and workspace must be 16-byte aligned");
     const size_t one = rgn_lm_decode_attention_workspace_bytes(Hq, nmax);
-    if (workspace_bytes < (size_t)B * one)
-        return fail(RGN_E_BADARG, "lm_decode_attention_rows: workspace smaller than B rgn_lm_decode_attention_workspace_bytes(Hq, max n)");
+    if (workspace_bytes < (size_t)B * one) return bad(who, "workspace smaller than B rgn_lm_decode_attention_workspace_bytes(Hq, max n)");
     const int ns = (nmax + DEC_SLICE - 1) / DEC_SLICE;
     const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(lm_decode_attention_rows_kernel, dim3(ns, Hkv, B), dim3(256), 0, st, (const uint16_t*)Q, ldq, (const uint16_t*)cache,
-                       cache_stride, nb, Hq, Hkv, scale, (float*)workspace, one / sizeof(float));
-    hipLaunchKernelGGL(lm_decode_merge_rows_kernel, dim3(Hq, B), dim3(128), 0, st, (const float*)workspace, one / sizeof(float), nb, (uint16_t*)O, ldo);
-    return check_launch("lm_decode_attention_rows");
+    if (B == 1) {
+        hipLaunchKernelGGL(lm_decode_attention_kernel, dim3(ns, Hkv), dim3(256), 0, st, (const uint16_t*)Q, (const uint16_t*)cache, nmax, Hq, Hkv,
+                           scale, (float*)workspace, ns);
+        hipLaunchKernelGGL(lm_decode_merge_kernel, dim3(Hq), dim3(128), 0, st, (const float*)workspace, ns, (uint16_t*)O);
+    } else {
+        hipLaunchKernelGGL(lm_decode_attention_rows_kernel, dim3(ns, Hkv, B), dim3(256), 0, st, (const uint16_t*)Q, ldq, (const uint16_t*)cache,
+                           cache_stride, nb, Hq, Hkv, scale, (float*)workspace, one / sizeof(float));
+        hipLaunchKernelGGL(lm_decode_merge_rows_kernel, dim3(Hq, B), dim3(128), 0, st, (const float*)workspace, one / sizeof(float), nb,
+                           (uint16_t*)O, ldo);
+    }
+    return check_launch(who);
+}
+
+int rgn_lm_decode_attention_bf16(const void* q, const void* cache, void* O, int n, int Hq, int Hkv, float scale, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    return decode_attention("lm_decode_attention", q, 0, cache, 0, O, 0, &n, 1, Hq, Hkv, scale, workspace, workspace_bytes, stream);
+}
+int rgn_lm_decode_attention_bf16_rows(const void* Q, int ldq, const void* cache, size_t cache_stride, void* O, int ldo, const int* n_host, int B,
+                                      int Hq, int Hkv, float scale, void* workspace, size_t workspace_bytes, void* stream) {
+    return decode_attention("lm_decode_attention_rows", Q, ldq, cache, cache_stride, O, ldo, n_host, B, Hq, Hkv, scale, workspace,
+                            workspace_bytes, stream);
 }
 
 int rgn_lm_seen_mark(const void* ids, int n, void* seen, int V, void* stream) {
@@ -1026,64 +1021,63 @@ int rgn_lm_seen_mark(const void* ids, int n, void* seen, int V, void* stream) {
 
 size_t rgn_lm_pick_workspace_bytes(int V) { return V < 1 ? 0 : (size_t)V * sizeof(float); }
 
-int rgn_lm_pick(const float* logits, int V, void* seen, float penalty, int sample, float temperature, int top_k, double top_p,
-                const float* uniform, void* token_out, float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!logits || !seen || !token_out || !workspace || V < 1 || V > PICK_MAX_V)
-        return fail(RGN_E_BADARG, "lm_pick: bad argument (logits, seen, token_out, workspace non-null; 1 <= V <= 1048576)");
-    if (!(penalty > 0.f) || !(penalty < INFINITY)) return fail(RGN_E_BADARG, "lm_pick: the repetition penalty must be in (0, inf)");
-    if (!(temperature > 0.f) || !(temperature < INFINITY)) return fail(RGN_E_BADARG, "lm_pick: the temperature must be in (0, inf)");
-    if (top_k < 0) return fail(RGN_E_BADARG, "lm_pick: top_k must be >= 0 (0 = off)");
-    if (!(top_p > 0.0) || !(top_p <= 1.0)) return fail(RGN_E_BADARG, "lm_pick: top_p must be in (0, 1] (1 = off)");
-    if (sample && !uniform) return fail(RGN_E_BADARG, "lm_pick: sampling reads its uniform from device memory (uniform non-null)");
-    if (((uintptr_t)token_out & 7u) || (((uintptr_t)logits | (uintptr_t)scores_out | (uintptr_t)workspace | (uintptr_t)uniform) & 3u))
-        return fail(RGN_E_BADARG, "lm_pick: token_out must be 8-byte, logits, scores_out, workspace and uniform 4-byte aligned");
-    if (scores_out == logits) return fail(RGN_E_BADARG, "lm_pick: scores_out may not be the logits");
-    if (workspace_bytes < rgn_lm_pick_workspace_bytes(V)) return fail(RGN_E_BADARG, "lm_pick: workspace smaller than rgn_lm_pick_workspace_bytes(V)");
-    static bool attr[64] = {};          // per device (one process may drive several GPUs)
+// A pick block's PICK_LDS bytes of dynamic LDS are more than a kernel gets unasked: allowed once per kernel and device (of several GPUs).
+static void pick_allow_lds(const void* kernel, bool (&done)[64]) {
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr[dev]) {
-        (void)hipFuncSetAttribute((const void*)lm_pick_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PICK_LDS);
-        if (dev >= 0 && dev < 64) attr[dev] = true;
+    if (dev < 0 || dev >= 64 || !done[dev]) {
+        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PICK_LDS);
+        if (dev >= 0 && dev < 64) done[dev] = true;
     }
-    hipLaunchKernelGGL(lm_pick_kernel, dim3(1), dim3(PICK_T), PICK_LDS, (hipStream_t)stream, logits, V, (uint8_t*)seen, penalty, sample ? 1 : 0,
-                       temperature, top_k, top_p, uniform, (int64_t*)token_out, scores_out ? scores_out : (float*)workspace);
-    return check_launch("lm_pick_kernel");
 }
 
-int rgn_lm_pick_rows(const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty, int sample, float temperature,
-                     int top_k, double top_p, const float* uniform, void* token_out, int token_stride, float* scores_out, int lds,
-                     void* workspace, size_t workspace_bytes, void* stream) {
+static int pick(const char* who, bool rows, const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty,
+                int sample, float temperature, int top_k, double top_p, const float* uniform, void* token_out, int token_stride,
+                float* scores_out, int lds, void* workspace, size_t workspace_bytes, void* stream) {
     if (!logits || !seen || !token_out || !workspace || V < 1 || V > PICK_MAX_V)
-        return fail(RGN_E_BADARG, "lm_pick_rows: bad argument (logits, seen, token_out, workspace non-null; 1 <= V <= 1048576)");
-    if (!batch_ok(B)) return fail(RGN_E_BADARG, "lm_pick_rows: B outside [1, 8]");
-    if (ldl < V || (scores_out && lds < V) || seen_stride < (size_t)V || token_stride < 1)
-        return fail(RGN_E_BADARG, "lm_pick_rows: ldl >= V, lds >= V, seen_stride >= V, token_stride >= 1");
-    if (!(penalty > 0.f) || !(penalty < INFINITY)) return fail(RGN_E_BADARG, "lm_pick_rows: the repetition penalty must be in (0, inf)");
-    if (!(temperature > 0.f) || !(temperature < INFINITY)) return fail(RGN_E_BADARG, "lm_pick_rows: the temperature must be in (0, inf)");
-    if (top_k < 0) return fail(RGN_E_BADARG, "lm_pick_rows: top_k must be >= 0 (0 = off)");
-    if (!(top_p > 0.0) || !(top_p <= 1.0)) return fail(RGN_E_BADARG, "lm_pick_rows: top_p must be in (0, 1] (1 = off)");
-    if (sample && !uniform) return fail(RGN_E_BADARG, "lm_pick_rows: sampling reads its uniforms from device memory (uniform non-null)");
+        return bad(who, "bad argument (logits, seen, token_out, workspace non-null; 1 <= V <= 1048576)");
+    if (!batch_ok(B)) return bad(who, "B outside [1, 8]");
+    if (B > 1 && (ldl < V || (scores_out && lds < V) || seen_stride < (size_t)V || token_stride < 1))
+        return bad(who, "ldl >= V, lds >= V, seen_stride >= V, token_stride >= 1");
+    if (!(penalty > 0.f) || !(penalty < INFINITY)) return bad(who, "the repetition penalty must be in (0, inf)");
+    if (!(temperature > 0.f) || !(temperature < INFINITY)) return bad(who, "the temperature must be in (0, inf)");
+    if (top_k < 0) return bad(who, "top_k must be >= 0 (0 = off)");
+    if (!(top_p > 0.0) || !(top_p <= 1.0)) return bad(who, "top_p must be in (0, 1] (1 = off)");
+    if (sample && !uniform) return bad(who, "sampling reads its uniforms from device memory (uniform non-null)");
     if (((uintptr_t)token_out & 7u) || (((uintptr_t)logits | (uintptr_t)scores_out | (uintptr_t)workspace | (uintptr_t)uniform) & 3u))
-        return fail(RGN_E_BADARG, "lm_pick_rows: token_out must be 8-byte, logits, scores_out, workspace and uniform 4-byte aligned");
+        return bad(who, "token_out must be 8-byte, logits, scores_out, workspace and uniform 4-byte aligned");
     if (scores_out) {                   // the spans [first element, last element of row B - 1] of the two matrices may not meet
         const uintptr_t z0 = (uintptr_t)logits, z1 = z0 + ((size_t)(B - 1) * ldl + V) * sizeof(float);
         const uintptr_t s0 = (uintptr_t)scores_out, s1 = s0 + ((size_t)(B - 1) * lds + V) * sizeof(float);
-        if (s0 < z1 && z0 < s1) return fail(RGN_E_BADARG, "lm_pick_rows: scores_out may not overlap the logits");
+        if (rows && s0 < z1 && z0 < s1) return bad(who, "scores_out may not overlap the logits");
+        if (s0 == z0) return bad(who, "scores_out may not be the logits");  // all rgn_lm_pick ever refused: its accepted set stays
     }
-    if (workspace_bytes < (size_t)B * rgn_lm_pick_workspace_bytes(V))
-        return fail(RGN_E_BADARG, "lm_pick_rows: workspace smaller than B rgn_lm_pick_workspace_bytes(V)");
-    static bool attr[64] = {};          // per device (one process may drive several GPUs)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr[dev]) {
-        (void)hipFuncSetAttribute((const void*)lm_pick_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PICK_LDS);
-        if (dev >= 0 && dev < 64) attr[dev] = true;
+    if (workspace_bytes < (size_t)B * rgn_lm_pick_workspace_bytes(V)) return bad(who, "workspace smaller than B rgn_lm_pick_workspace_bytes(V)");
+    static bool set_one[64] = {}, set_rows[64] = {};
+    float* s = scores_out ? scores_out : (float*)workspace;
+    if (B == 1) {
+        pick_allow_lds((const void*)lm_pick_kernel, set_one);
+        hipLaunchKernelGGL(lm_pick_kernel, dim3(1), dim3(PICK_T), PICK_LDS, (hipStream_t)stream, logits, V, (uint8_t*)seen, penalty,
+                           sample ? 1 : 0, temperature, top_k, top_p, uniform, (int64_t*)token_out, s);
+        return check_launch("lm_pick_kernel");
     }
+    pick_allow_lds((const void*)lm_pick_rows_kernel, set_rows);
     hipLaunchKernelGGL(lm_pick_rows_kernel, dim3(B), dim3(PICK_T), PICK_LDS, (hipStream_t)stream, logits, ldl, V, (uint8_t*)seen, seen_stride,
-                       penalty, sample ? 1 : 0, temperature, top_k, top_p, uniform, (int64_t*)token_out, token_stride,
-                       scores_out ? scores_out : (float*)workspace, scores_out ? (size_t)lds : (size_t)V);
+                       penalty, sample ? 1 : 0, temperature, top_k, top_p, uniform, (int64_t*)token_out, token_stride, s,
+                       scores_out ? (size_t)lds : (size_t)V);
     return check_launch("lm_pick_rows_kernel");
+}
+
+int rgn_lm_pick(const float* logits, int V, void* seen, float penalty, int sample, float temperature, int top_k, double top_p,
+                const float* uniform, void* token_out, float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return pick("lm_pick", false, logits, 0, 1, V, seen, 0, penalty, sample, temperature, top_k, top_p, uniform, token_out, 0, scores_out, 0, workspace,
+                workspace_bytes, stream);
+}
+int rgn_lm_pick_rows(const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty, int sample, float temperature,
+                     int top_k, double top_p, const float* uniform, void* token_out, int token_stride, float* scores_out, int lds,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    return pick("lm_pick_rows", true, logits, ldl, B, V, seen, seen_stride, penalty, sample, temperature, top_k, top_p, uniform, token_out,
+                token_stride, scores_out, lds, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

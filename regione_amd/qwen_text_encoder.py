@@ -19,32 +19,34 @@ buffer, the `mrope_section` selection applied once, cast to bf16 and copied in o
 `vision=`, a HipQwen25VLVisionTower (regione_amd/qwen_vision.py: the tower on the same kernels; the adapter passes one), or with
 `vision=None` the host's eager module (`get_image_features`); its embeddings are placed at the image-token rows by rgn_scatter_rows.
 
-`generate` is transformers' greedy search for one sequence on the same weights (csrc/decode.hip): the prefill above with the k | v columns of
-every layer appended to a KV cache [layers][cap, 2 Hkv 128] after mRoPE (rgn_lm_kv_append_bf16) and the final norm on the last row only, then
-per new token ONE row through the stack - rgn_lm_gemv_bf16 for the four projections (bias for q|k|v, the two roundings of `h + linear(a)` for
-the residual adds), rgn_lm_decode_attention_bf16 against the cache, the row kernels at M = 1 - and rgn_lm_head_argmax over `lm_head` (fp32
-logits, the lowest index on a tie), which writes the token into the device id buffer the next rgn_text_embed reads.  New token k sits at
-max(prompt positions) + 1 + k on all three axes (`decode_position_ids`).  The loop is a `for` over `max_new_tokens`; the host reads the ids
-every `sync_every` tokens to look for EOS.
+`generate` is transformers' greedy search on the same weights (csrc/decode.hip), ONE decode loop for 1 <= B <= max_batch rows: the prefill
+above, row by row, with the k | v columns of every layer appended to the row's KV cache [layers][B][cap, 2 Hkv 128] after mRoPE
+(rgn_lm_kv_append_bf16) and the final norm on the last row only, then per new token B rows through the stack - rgn_lm_gemv_bf16_rows for the
+four projections (bias for q|k|v, the two roundings of `h + linear(a)` for the residual adds), rgn_lm_decode_attention_bf16_rows against the
+caches, the row kernels at M = B - and rgn_lm_head_argmax_rows over `lm_head` (fp32 logits, the lowest index on a tie), which writes the
+tokens into the device id row the next rgn_text_embed reads.  At B = 1 a `_rows` entry launches the one-row kernels (it is the one-row
+entry), so one sequence decodes on the GEMVs tuned for it.  New token k sits at max(prompt positions) + 1 + k on all three axes
+(`decode_position_ids`).  The loop is a `for` over `max_new_tokens`; the host reads the ids every `sync_every` tokens to look for EOS.
 
 `weights="fp8"` stores the four packed matrices of every layer (q|k|v, o, gate|up, down) as OCP e4m3fn with one fp32 scale per output
 channel (ops.quantize_w8, after the concatenation: the scale is per row, so the concatenation of the parts' quantisations is the
 quantisation of the concatenation), layer by layer on the device; norms, the q|k|v bias, the embedding and `lm_head` stay bf16.  The prefill
 is unchanged (ops.gemm takes the scale from the weight tensor, rgn_gemm_group converts exactly and scales the accumulator); the decode loop
-calls rgn_lm_gemv_w8 instead of rgn_lm_gemv_bf16: half the bytes per token for those matrices.  Opt-in: the default "bf16" is the path above.
+calls rgn_lm_gemv_w8_rows instead of rgn_lm_gemv_bf16_rows: half the bytes per token for those matrices.  Opt-in: the default is "bf16".
 
 `sampling=True` (opt-in; the default refuses what it refused before) lets `generate` honour a decoding configuration: `do_sample`,
 `temperature`, `top_k`, `top_p` and `repetition_penalty`, each taken from the module's generation_config when the argument is None, as
-transformers does.  The pick is then rgn_lm_head_argmax for the fp32 logits followed by ONE rgn_lm_pick on the same stream (penalty over
-a byte map of the ids so far, temperature, top-k, top-p, argmax or the inverse CDF at a uniform read from a device buffer filled before
-the loop), which overwrites the id slot: still no token visits the host inside a step.  The uniforms come from `generator=` /
-`uniforms=`, not from torch.multinomial: a seed gives transformers' distribution, not transformers' tokens.
+transformers does.  The pick is then rgn_lm_head_argmax_rows for the fp32 logits followed by ONE rgn_lm_pick_rows on the same stream (at
+B = 1 the one block of rgn_lm_pick: penalty over a byte map of the ids so far, temperature, top-k, top-p, argmax or the inverse CDF at a
+uniform read from a device buffer filled before the loop), which overwrites the id slot: still no token visits the host inside a step.
+The uniforms come from `generator=` / `uniforms=`, not from torch.multinomial: a seed gives transformers' distribution, not transformers'
+tokens.
 
 `max_batch=N` (opt-in, 1 <= N <= 8; the default 1 refuses what it refused before) lets `generate` take `input_ids [B, L]` with B <= N
 left-padded rows, as transformers' batched greedy search does: rows prefill one after another over their valid tokens into their own
-caches, then every step decodes all B rows from ONE stream of the weights (the `_rows` entries of csrc/decode.hip).  The batch is
-invariant: row b's tokens and fp32 logits are bit for bit those of the B = 1 call on row b's unpadded prompt.  A row is finished after
-its first EOS and holds `pad_token_id` from then on (`assemble_sequences`); B = 1 under such an adoption takes the one-row launches.
+caches, then every step decodes all B rows from ONE stream of the weights (the `_rows` kernels of csrc/decode.hip from B = 2 on).  The
+batch is invariant: row b's tokens and fp32 logits are bit for bit those of the B = 1 call on row b's unpadded prompt.  A row is finished
+after its first EOS and holds `pad_token_id` from then on (`assemble_sequences`); B = 1 under such an adoption keeps the one-row rules.
 Sampling over a batch is refused (rgn_lm_pick is one sequence) unless the adoption also sets `batch_sampling=True`.
 
 `batch_sampling=True` (opt-in; needs `sampling=True` and `max_batch > 1`; without it every refusal is what it was) lets a batch of B >= 2
@@ -55,8 +57,7 @@ time-major like the new ids.  The byte map is [B, V], row b marked over that row
 This is a deliberate difference from transformers, whose RepetitionPenaltyLogitsProcessor gathers at the pad positions too and so, for
 Qwen (the pad id is also an EOS id), penalises an EOS in padded rows only; not marking it is what keeps the batch invariant: for given
 `uniforms`, row b's tokens, fp32 logits and scores are bit for bit those of the B = 1 sampled call on row b's unpadded prompt with
-`uniforms[:, b]`.  B = 1 keeps the one-sequence path; a configuration that is greedy as before runs the batched greedy launches
-unchanged.  Not measured: real checkpoints.
+`uniforms[:, b]`.  A configuration that is greedy as before runs the greedy launches unchanged.  Not measured: real checkpoints.
 
 There is no eager fallback inside: what the kernels do not implement raises RegionEHipError before any launch, and the adapter
 (regione_amd.adapters, components.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
@@ -64,6 +65,8 @@ only; every call returns freshly allocated outputs.
 """
 from __future__ import annotations
 
+import ctypes
+import functools
 from typing import Dict, Optional
 
 import torch
@@ -330,6 +333,13 @@ def assemble_sequences(prompt_ids: torch.Tensor, new_ids: torch.Tensor, eos, pad
     return torch.cat([prompt_ids.to(torch.int64), new.to(torch.int64)], dim=1), n_new
 
 
+def _bound(fn, name, *args):
+    """(`fn` with `args` bound, `name`): the arguments are converted to their ctypes objects once, a host array to a pointer to its
+    memory (what is written into the array later is what the call reads), so that calling the result marshals nothing."""
+    conv = [ctypes.cast(a, t) if isinstance(a, ctypes.Array) else t(a) for t, a in zip(fn.argtypes, args, strict=True)]
+    return functools.partial(fn, *conv), name
+
+
 class HipQwen25VLTextEncoder(_HipTextEncoder):
     """`Qwen2_5_VLForConditionalGeneration(input_ids, attention_mask, pixel_values, image_grid_thw, output_hidden_states=True)` with the
     language model on the HIP kernels.  Returns an object with `.last_hidden_state` [B, L, d] bf16 and `.hidden_states`, a ONE-element
@@ -535,7 +545,7 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         res = QwenTextEncoderOutput(out, bool(output_hidden_states))
         return res if return_dict else res.to_tuple()
 
-    # ---- greedy generate: the prefill above with a KV cache, then one-row decode steps (csrc/decode.hip) -----------------------------
+    # ---- greedy generate: the prefill above with a KV cache per row, then decode steps over the B rows (csrc/decode.hip) ------------
     def _generate_args(self, input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw):
         """Every refusal of `generate`, before any launch; returns the eos ids (a possibly empty list)."""
         gc = getattr(self.module, "generation_config", None)
@@ -664,25 +674,32 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
     def generate(self, input_ids, attention_mask=None, pixel_values=None, image_grid_thw=None, max_new_tokens=None, eos_token_id=None,
                  do_sample=None, return_dict_in_generate=False, output_logits=False, mm_token_type_ids=None, image_embeds=None,
                  position_ids=None, sync_every=8, **kw):
-        """transformers' greedy `generate` for one sequence: LongTensor [1, L + n_new], the prompt followed by the new tokens, cut after the
-        first `eos_token_id` (an int or a list; EOS included; None: the module's generation_config.eos_token_id, []: no EOS).  The prefill is the layer loop of `__call__` with the k | v rows of every
-        layer appended to a cache; each further token is one row through rgn_lm_gemv_bf16 (rgn_lm_gemv_w8 under weights="fp8") /
-        rgn_lm_decode_attention_bf16, picked by
-        rgn_lm_head_argmax INTO the device id buffer the next rgn_text_embed reads: no token visits the host inside a step.  The host reads
-        the ids back every `sync_every` tokens to look for EOS (never without one); the result does not depend on `sync_every`.
+        """transformers' greedy `generate` for B rows, 1 <= B <= max_batch: LongTensor [B, L + n_new], the prompts followed by the new
+        tokens.  A row is cut after its first `eos_token_id` (an int or a list; EOS included; None: the module's
+        generation_config.eos_token_id, []: no EOS); n_new is the largest cut (max_new_tokens if a row never finished) and a row that
+        finished earlier holds the pad id from its cut on (`assemble_sequences`) - one row is cut, never padded.
+        Each row is prefilled over its valid tokens by `_prefill_row` into its own cache at rows [0, n_b) - no padded key is ever in a
+        cache, so decode needs no mask - then every step decodes the B rows from ONE stream of the weights through the `_rows` entries of
+        csrc/decode.hip (rgn_lm_gemv_bf16_rows, or rgn_lm_gemv_w8_rows under weights="fp8"; rgn_lm_kv_append_bf16_rows;
+        rgn_lm_decode_attention_bf16_rows; the row kernels at M = B), which launch the one-row kernels at B = 1.  rgn_lm_head_argmax_rows
+        picks INTO the device id row the next rgn_text_embed reads (new ids [T, B] and decode RoPE tables [T, B, 128] time-major, so a
+        step's rows are contiguous): no token visits the host inside a step.  The host reads the ids back every `sync_every` tokens to
+        look for EOS (never without one); the result does not depend on `sync_every`.  The device keeps decoding finished rows (a fixed
+        launch count, no dependence on device data).  Row b's tokens and fp32 logits are bit for bit those of the B = 1 call on row b's
+        unpadded prompt.  `.logits` (output_logits=True) is a tuple of n_new fp32 [B, V] tensors; rows past a sequence's EOS are not
+        meaningful.
+        Under `max_batch=N` the call takes 2 <= B <= N rows with a left-padded `attention_mask` (zeros, then ones) and `pad_token_id`
+        (None: generation_config.pad_token_id, else the first EOS id); one row takes an all-ones mask under every adoption.
         Under `sampling=True` the call also takes do_sample, temperature, top_k, top_p, repetition_penalty (None: the module's
-        generation_config value, else off), generator= or uniforms= (fp32 [max_new_tokens] on the device) and output_scores=True; the pick
-        is then rgn_lm_head_argmax for the logits and one rgn_lm_pick per token, still without a host read inside a step.
-        Under `max_batch=N` the call also takes `input_ids [B, L]`, 2 <= B <= N, with a left-padded `attention_mask` (zeros, then ones)
-        and `pad_token_id` (None: generation_config.pad_token_id, else the first EOS id): LongTensor [B, L + n_new], each row cut after
-        its first EOS and filled with the pad id, n_new the largest cut (max_new_tokens if a row never finished); `.logits` is then a
-        tuple of n_new fp32 [B, V] tensors whose rows past a sequence's EOS are not meaningful (`_generate_rows`).
-        Under `batch_sampling=True` such a batch also takes the arguments of `sampling=True`, one configuration for all rows: uniforms= is
-        then a contiguous fp32 [max_new_tokens, B] on the device (time-major, like the new ids), generator= fills torch.rand(T, B) once
-        before the loop - so with a generator a row's stream of uniforms depends on B and on the row's place in the batch - and
-        output_scores=True gives `.scores`, a tuple of n_new fp32 [B, V] tensors.  For given `uniforms`, row b is bit for bit the B = 1
-        call on its unpadded prompt with uniforms[:, b].  The repetition penalty of row b sees that row's valid prompt ids and its own
-        new tokens; the left padding is NOT marked (transformers gathers at the pad positions too)."""
+        generation_config value, else off), generator= or uniforms= (fp32 [max_new_tokens] on the device) and output_scores=True: unless
+        that configuration is greedy as before, the head writes the fp32 [B, V] logits and ONE rgn_lm_pick_rows per step turns them into
+        the step's id row, still without a host read inside a step; `.scores` is a tuple of n_new fp32 [B, V] tensors.
+        Under `batch_sampling=True` a batch takes those arguments too, one configuration for all rows: uniforms= is then a contiguous
+        fp32 [max_new_tokens, B] on the device (time-major, like the new ids), generator= fills torch.rand(T, B) once before the loop -
+        so with a generator a row's stream of uniforms depends on B and on the row's place in the batch.  For given `uniforms`, row b is
+        bit for bit the B = 1 call on its unpadded prompt with uniforms[:, b].  The byte map of the repetition penalty is [B, V], zeroed
+        once; row b sees that row's valid prompt ids and its own new tokens, the left padding is NOT marked (transformers gathers at the
+        pad positions too).  Finished rows keep being picked; scores past a row's EOS are not meaningful."""
         plan = None
         pad_arg = kw.pop("pad_token_id", None) if self.max_batch > 1 else None    # a default adoption refuses the argument as before
         if self.sampling:                                                         # opt-in: without it every refusal below is what it was
@@ -693,128 +710,9 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
                 plan = None
         else:
             eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
-        if input_ids.shape[0] > 1:                                                # only a max_batch > 1 adoption gets here; B = 1 stays below
-            return self._generate_rows(input_ids, attention_mask, pixel_values, image_grid_thw, int(max_new_tokens), eos, pad_arg,
-                                       return_dict_in_generate, output_logits, mm_token_type_ids, image_embeds, position_ids, sync_every, plan)
-        ids_cpu, lengths, tables, pos = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids,
-                                                      mm_token_type_ids, image_embeds, {})
-        L, T = ids_cpu.shape[1], int(max_new_tokens)
-        new_tables = mrope_tables(self.inv_freq, decode_position_ids(pos, T), self.mrope_section)        # [2, 1, T, 128]
-        head = self._adopt_lm_head()                                               # may refuse: nothing has been launched yet
-        emb = self._image_embeds(pixel_values, image_grid_thw, image_embeds)
-        idx = None
-        if emb is not None:
-            if self.image_token_id is None:
-                _refuse(self.what, "the config has no image_token_id")
-            idx = image_rows(ids_cpu, lengths, int(self.image_token_id), emb.shape[0], self.what)[0].to(self.device)
-        lib, dev, d, V = _lib.lib(), self.device, self.d, self.tok.shape[0]
-        cap, kvw, nl = L + T, 2 * self.Hkv * HEAD_DIM, len(self.layers)
-        ws_a, ws_h = lib.rgn_lm_decode_attention_workspace_bytes(self.Hq, cap), lib.rgn_lm_head_workspace_bytes(V)
-        c = self.kv.get(cap, dict(cache=(nl, cap, kvw), h=(1, d), n=(1, d), qkv=(1, self.qkv_cols), a=(1, self.Hq * HEAD_DIM), ff=(1, 2 * self.F),
-                                  g=(1, self.F), ws_a=((ws_a + 1) // 2,), ws_h=((ws_h + 1) // 2,)))
-        t = self.buf.get(L, dict(h=(L, d), n=(L, d), qkv=(L, self.qkv_cols), a=(L, self.Hq * HEAD_DIM), ff=(L, 2 * self.F), g=(L, self.F)))
-        ids = torch.empty(cap, dtype=torch.int64, device=dev)
-        ids[:L] = input_ids[0].to(dev, torch.int64)
-        logits = torch.empty(T, V, dtype=torch.float32, device=dev) if output_logits else None
-        tab, ntab = tables.to(dev), new_tables.to(dev)                            # one host-to-device copy each
-        st = _stream()
-        ck = _lib.check
-
-        if plan is None:
-            def pick(k):                                                          # token k from the normalised row in c["n"]
-                ck(lib.rgn_lm_head_argmax(_p(head), _p(c["n"]), V, d, ids.data_ptr() + 8 * (L + k), None if logits is None else _p(logits[k]),
-                                          _p(c["ws_h"]), ws_h, st), "rgn_lm_head_argmax")
-        else:
-            # the pick of this generate, chosen once: lm_head writes the fp32 row, ONE rgn_lm_pick turns it into the token in the id slot
-            ws_p = lib.rgn_lm_pick_workspace_bytes(V)
-            seen = torch.empty(V, dtype=torch.uint8, device=dev)
-            zrow = torch.empty(V, dtype=torch.float32, device=dev) if logits is None else None
-            pick_ws = torch.empty((ws_p + 3) // 4, dtype=torch.float32, device=dev)
-            scores = torch.empty(T, V, dtype=torch.float32, device=dev) if plan.output_scores else None
-            uni = plan.uniforms
-            if plan.sample and uni is None:                                       # filled before the loop; the kernel has no generator
-                g = plan.generator
-                uni = torch.rand(T, dtype=torch.float32, generator=g, device=dev if g is None else g.device).to(dev)
-            ck(lib.rgn_fill_zero(_p(seen), V, st), "rgn_fill_zero")
-            ck(lib.rgn_lm_seen_mark(_p(ids), L, _p(seen), V, st), "rgn_lm_seen_mark")
-            pen, smp, tmp, tk, tp = plan.penalty, int(plan.sample), plan.temperature, plan.top_k, plan.top_p
-            pu = uni.data_ptr() if plan.sample else None
-
-            def pick(k):
-                z = logits[k] if logits is not None else zrow
-                ck(lib.rgn_lm_head_argmax(_p(head), _p(c["n"]), V, d, ids.data_ptr() + 8 * (L + k), _p(z), _p(c["ws_h"]), ws_h, st),
-                   "rgn_lm_head_argmax")
-                ck(lib.rgn_lm_pick(_p(z), V, _p(seen), pen, smp, tmp, tk, tp, None if pu is None else pu + 4 * k, ids.data_ptr() + 8 * (L + k),
-                                   None if scores is None else _p(scores[k]), _p(pick_ws), ws_p, st), "rgn_lm_pick")
-
-        h, _ = self._prefill_row(t, ids[:L], L, tab[0, 0], tab[1, 0], emb if emb is not None and emb.shape[0] else None, idx, cache=c["cache"])
-        self._rms(h[L - 1:L], self.final_ln, c["n"])                              # the final norm on the last row only
-        pick(0)
-        ph, pn, pqkv, pa, pff, pg, pws = (c[k].data_ptr() for k in ("h", "n", "qkv", "a", "ff", "g", "ws_a"))
-        # the one-row linear layer of this adoption, picked once: a weight is the leading argument(s) of its entry, (W,) or (W8, scale)
-        if self.weights == "fp8":
-            gemv, gemv_name = lib.rgn_lm_gemv_w8, "rgn_lm_gemv_w8"
-            wp = lambda t: (t.data_ptr(), ops._wscale(t).data_ptr())
-        else:
-            gemv, gemv_name = lib.rgn_lm_gemv_bf16, "rgn_lm_gemv_bf16"
-            wp = lambda t: (t.data_ptr(),)
-        lp = [(p["ln1"].data_ptr(), wp(p["wqkv"]), p["bqkv"].data_ptr(), wp(p["wo"]), p["ln2"].data_ptr(), wp(p["wgu"]),
-               wp(p["wdown"]), c["cache"][i].data_ptr()) for i, p in enumerate(self.layers)]
-        ptok, pfin, pcos, psin, pids = self.tok.data_ptr(), self.final_ln.data_ptr(), ntab[0, 0].data_ptr(), ntab[1, 0].data_ptr(), ids.data_ptr()
-        Hq, Hkv, F, eps, scale, qc, ad = self.Hq, self.Hkv, self.F, self.eps, float(self.scale), self.qkv_cols, self.Hq * HEAD_DIM
-        n_new = T
-
-        def first_eos(upto):                                                      # the host's look at the ids: the only synchronisation
-            got = ids[L:L + upto].cpu()
-            hit = torch.zeros(upto, dtype=torch.bool)
-            for e in eos:
-                hit |= got == e
-            return int(torch.nonzero(hit)[0]) + 1 if bool(hit.any()) else None
-        for k in range(1, T + 1):                                                 # bounded by max_new_tokens, never by device data
-            if eos and (k % sync_every == 0 or k == T):
-                cut = first_eos(k)
-                if cut is not None:
-                    n_new = cut
-                    break
-            if k == T:
-                break
-            row = L + k - 1                                                       # the token picked last: embed it, append it, attend over row + 1
-            ck(lib.rgn_text_embed(pids + 8 * row, 1, ptok, V, None, 0, ph, d, st), "rgn_text_embed")
-            for ln1, wqkv, bqkv, wo, ln2, wgu, wdown, pc in lp:
-                ck(lib.rgn_rms_norm_rows(ph, d, ln1, pn, d, 1, d, eps, st), "rgn_rms_norm_rows")
-                ck(gemv(*wqkv, pn, bqkv, None, pqkv, qc, d, st), gemv_name)
-                ck(lib.rgn_mrope_bf16(pqkv, qc, pcos + 256 * (k - 1), psin + 256 * (k - 1), 1, Hq, Hkv, st), "rgn_mrope_bf16")
-                ck(lib.rgn_lm_kv_append_bf16(pqkv, qc, pc, cap, row, 1, Hq, Hkv, st), "rgn_lm_kv_append_bf16")
-                ck(lib.rgn_lm_decode_attention_bf16(pqkv, pc, pa, row + 1, Hq, Hkv, scale, pws, ws_a, st), "rgn_lm_decode_attention_bf16")
-                ck(gemv(*wo, pa, None, ph, ph, d, ad, st), gemv_name)
-                ck(lib.rgn_rms_norm_rows(ph, d, ln2, pn, d, 1, d, eps, st), "rgn_rms_norm_rows")
-                ck(gemv(*wgu, pn, None, None, pff, 2 * F, d, st), gemv_name)
-                ck(lib.rgn_swiglu_bf16(pff, 2 * F, pg, F, 1, F, st), "rgn_swiglu_bf16")
-                ck(gemv(*wdown, pg, None, ph, ph, d, F, st), gemv_name)
-            ck(lib.rgn_rms_norm_rows(ph, d, pfin, pn, d, 1, d, eps, st), "rgn_rms_norm_rows")
-            pick(k)
-        seq = ids[:L + n_new].to(input_ids.device)[None]
-        if not return_dict_in_generate:
-            return seq
-        return QwenGenerateOutput(seq, tuple(logits[k][None] for k in range(n_new)) if logits is not None else None,
-                                  tuple(scores[k][None] for k in range(n_new)) if plan is not None and scores is not None else None)
-
-    def _generate_rows(self, input_ids, attention_mask, pixel_values, image_grid_thw, T, eos, pad_arg, return_dict_in_generate, output_logits,
-                       mm_token_type_ids, image_embeds, position_ids, sync_every, plan=None):
-        """`generate` for 2 <= B <= max_batch left-padded rows (every refusal has been raised): each row is prefilled over its valid tokens
-        by `_prefill_row` into its own cache at rows [0, n_b) - no padded key is ever in a cache, so decode needs no mask - then every step
-        decodes the B rows from ONE stream of the weights (rgn_lm_gemv_bf16_rows / rgn_lm_gemv_w8_rows, rgn_lm_kv_append_bf16_rows,
-        rgn_lm_decode_attention_bf16_rows, rgn_lm_head_argmax_rows, the row kernels at M = B; new ids [T, B] and decode RoPE tables
-        [T, B, 128] time-major, so a step's rows are contiguous).  Row b's tokens and fp32 logits are bit for bit those of the B = 1 call
-        on row b's unpadded prompt.  The device keeps decoding finished rows (a fixed launch count, no dependence on device data); the host
-        overwrites them with the pad id at assembly (`assemble_sequences`).  Logits of a row past its EOS are not meaningful.
-        With `plan` (a `batch_sampling=True` adoption whose configuration is not greedy as before) the head writes the fp32 [B, V] logits
-        and ONE rgn_lm_pick_rows per step turns them into the B tokens of `new[k]`; `seen` [B, V] is zeroed once and row b marked over
-        ids[b, L - n_b:] only (never the padding).  Finished rows keep being picked; scores past a row's EOS are not meaningful."""
-        import ctypes as C
         ids_cpu, lens, tables, pos = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids,
                                                    image_embeds, {}, left=True)
-        B, L = ids_cpu.shape
+        (B, L), T = ids_cpu.shape, int(max_new_tokens)
         pad = resolve_pad_token_id(pad_arg, getattr(self.module, "generation_config", None), eos)
         new_tables = mrope_tables(self.inv_freq, decode_position_ids(pos, T), self.mrope_section)        # [2, B, T, 128]
         head = self._adopt_lm_head()                                               # may refuse: nothing has been launched yet
@@ -878,18 +776,35 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             self._rms(h[n - 1:n], self.final_ln, c["n"][b:b + 1])                 # the final norm on the last row only
         pick(0)
         ph, pqkv, pa, pff, pg, pws = (c[k].data_ptr() for k in ("h", "qkv", "a", "ff", "g", "ws_a"))
+        # the linear layer of this adoption, picked once: a weight is the leading argument(s) of its entry, (W,) or (W8, scale)
         if self.weights == "fp8":
             gemv, gemv_name = lib.rgn_lm_gemv_w8_rows, "rgn_lm_gemv_w8_rows"
             wp = lambda w: (w.data_ptr(), ops._wscale(w).data_ptr())
         else:
             gemv, gemv_name = lib.rgn_lm_gemv_bf16_rows, "rgn_lm_gemv_bf16_rows"
             wp = lambda w: (w.data_ptr(),)
-        lp = [(p["ln1"].data_ptr(), wp(p["wqkv"]), p["bqkv"].data_ptr(), wp(p["wo"]), p["ln2"].data_ptr(), wp(p["wgu"]),
-               wp(p["wdown"]), c["cache"][i].data_ptr()) for i, p in enumerate(self.layers)]
         ptok, pfin, pcos, psin = self.tok.data_ptr(), self.final_ln.data_ptr(), ntab[0].data_ptr(), ntab[1].data_ptr()
         Hq, Hkv, F, eps, scale, qc, ad = self.Hq, self.Hkv, self.F, self.eps, float(self.scale), self.qkv_cols, self.Hq * HEAD_DIM
         cstride = cap * kvw
-        row0, nn = (C.c_int * B)(), (C.c_int * B)()                               # host arrays: the entries copy them into the launch
+        row0, nn = (ctypes.c_int * B)(), (ctypes.c_int * B)()                     # host arrays: the entries copy them into the launch
+        # Every launch of a layer but mRoPE (its table row moves) takes the same arguments at every step: they are converted once here, so
+        # that a step only calls ready objects.  Per layer: the launches before mRoPE, and those after it.
+        rms, swiglu, append, attend = lib.rgn_rms_norm_rows, lib.rgn_swiglu_bf16, lib.rgn_lm_kv_append_bf16_rows, lib.rgn_lm_decode_attention_bf16_rows
+        lp = []
+        for i, p in enumerate(self.layers):
+            pc = c["cache"][i].data_ptr()
+            lp.append(([_bound(rms, "rgn_rms_norm_rows", ph, d, p["ln1"].data_ptr(), pn, d, B, d, eps, st),
+                        _bound(gemv, gemv_name, *wp(p["wqkv"]), pn, d, p["bqkv"].data_ptr(), None, 0, pqkv, qc, B, qc, d, st)],
+                       [_bound(append, "rgn_lm_kv_append_bf16_rows", pqkv, qc, pc, cstride, cap, row0, B, Hq, Hkv, st),
+                        _bound(attend, "rgn_lm_decode_attention_bf16_rows", pqkv, qc, pc, cstride, pa, ad, nn, B, Hq, Hkv, scale, pws, ws_a, st),
+                        _bound(gemv, gemv_name, *wp(p["wo"]), pa, ad, None, ph, d, ph, d, B, d, ad, st),
+                        _bound(rms, "rgn_rms_norm_rows", ph, d, p["ln2"].data_ptr(), pn, d, B, d, eps, st),
+                        _bound(gemv, gemv_name, *wp(p["wgu"]), pn, d, None, None, 0, pff, 2 * F, B, 2 * F, d, st),
+                        _bound(swiglu, "rgn_swiglu_bf16", pff, 2 * F, pg, F, B, F, st),
+                        _bound(gemv, gemv_name, *wp(p["wdown"]), pg, F, None, ph, d, ph, d, B, d, F, st)]))
+        final_norm, final_name = _bound(rms, "rgn_rms_norm_rows", ph, d, pfin, pn, d, B, d, eps, st)
+        mrope = functools.partial(lib.rgn_mrope_bf16, ctypes.c_void_p(pqkv), ctypes.c_int(qc))
+        mtail = (ctypes.c_int(B), ctypes.c_int(Hq), ctypes.c_int(Hkv), ctypes.c_void_p(st))
         n_new = T
         for k in range(1, T + 1):                                                 # bounded by max_new_tokens, never by device data
             if eos and (k % sync_every == 0 or k == T):                           # the host's look at the ids: the only synchronisation
@@ -902,20 +817,15 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             for b, n in enumerate(lens):                                          # the tokens picked last: row n + k - 1 of each cache
                 row0[b], nn[b] = n + k - 1, n + k
             tb = 256 * B * (k - 1)
+            cos, sin = ctypes.c_void_p(pcos + tb), ctypes.c_void_p(psin + tb)
             ck(lib.rgn_text_embed(pnew + 8 * B * (k - 1), B, ptok, V, None, 0, ph, d, st), "rgn_text_embed")
-            for ln1, wqkv, bqkv, wo, ln2, wgu, wdown, pc in lp:
-                ck(lib.rgn_rms_norm_rows(ph, d, ln1, pn, d, B, d, eps, st), "rgn_rms_norm_rows")
-                ck(gemv(*wqkv, pn, d, bqkv, None, 0, pqkv, qc, B, qc, d, st), gemv_name)
-                ck(lib.rgn_mrope_bf16(pqkv, qc, pcos + tb, psin + tb, B, Hq, Hkv, st), "rgn_mrope_bf16")
-                ck(lib.rgn_lm_kv_append_bf16_rows(pqkv, qc, pc, cstride, cap, row0, B, Hq, Hkv, st), "rgn_lm_kv_append_bf16_rows")
-                ck(lib.rgn_lm_decode_attention_bf16_rows(pqkv, qc, pc, cstride, pa, ad, nn, B, Hq, Hkv, scale, pws, ws_a, st),
-                   "rgn_lm_decode_attention_bf16_rows")
-                ck(gemv(*wo, pa, ad, None, ph, d, ph, d, B, d, ad, st), gemv_name)
-                ck(lib.rgn_rms_norm_rows(ph, d, ln2, pn, d, B, d, eps, st), "rgn_rms_norm_rows")
-                ck(gemv(*wgu, pn, d, None, None, 0, pff, 2 * F, B, 2 * F, d, st), gemv_name)
-                ck(lib.rgn_swiglu_bf16(pff, 2 * F, pg, F, B, F, st), "rgn_swiglu_bf16")
-                ck(gemv(*wdown, pg, F, None, ph, d, ph, d, B, d, F, st), gemv_name)
-            ck(lib.rgn_rms_norm_rows(ph, d, pfin, pn, d, B, d, eps, st), "rgn_rms_norm_rows")
+            for before, after in lp:
+                for launch, name in before:
+                    ck(launch(), name)
+                ck(mrope(cos, sin, *mtail), "rgn_mrope_bf16")
+                for launch, name in after:
+                    ck(launch(), name)
+            ck(final_norm(), final_name)
             pick(k)
         seq, n_new = assemble_sequences(ids_cpu, new[:n_new].cpu(), eos, pad)
         seq = seq.to(input_ids.device)

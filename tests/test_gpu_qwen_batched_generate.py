@@ -374,6 +374,37 @@ def test_one_row_under_max_batch_is_the_default_adoption(weights):
     assert all(torch.equal(a, b) for a, b in zip(got.logits, s["alone"][1].logits))
 
 
+def _kernel_names(fn):
+    from torch.profiler import ProfilerActivity, profile
+    fn()                                                                         # warm: buffers, lm_head, the pick's LDS attribute
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return [e.name for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")]
+
+
+def test_one_row_under_max_batch_launches_the_one_row_kernels():
+    """B = 1 of a `_rows` entry is the one-row entry: a max_batch=8 adoption decodes one unpadded row on the one-row kernels, greedy and
+    sampled, and launches no `_rows` kernel of csrc/decode.hip at all (they are all named lm_*_rows_kernel; rms_norm_rows_kernel is the
+    row norm of csrc/norm.hip, which every decode step runs at M = B)."""
+    s = _run("bf16")
+    kw, T = _cuda(s["singles"][1]), 4
+
+    def batched(names):
+        return [n for n in names if "_rows_kernel" in n and "rms_norm_rows_kernel" not in n]
+    names = _kernel_names(lambda: s["hip"].generate(**kw, max_new_tokens=T, eos_token_id=[]))
+    for k in ("lm_gemv_kernel", "lm_decode_attention_kernel", "lm_decode_merge_kernel", "lm_head_finalize_kernel"):
+        assert any(k in n for n in names), k
+    assert batched(names) == []
+    sampled = QT.HipQwen25VLTextEncoder(s["hip"].module, sampling=True, max_batch=8, batch_sampling=True)
+    uni = torch.rand(T, device="cuda", generator=_gen(5))
+    names = _kernel_names(lambda: sampled.generate(**kw, max_new_tokens=T, eos_token_id=[], do_sample=True, temperature=0.7, top_k=20,
+                                                   top_p=0.8, repetition_penalty=1.05, uniforms=uni))
+    assert sum("lm_pick_kernel" in n for n in names) == T
+    assert batched(names) == []
+
+
 def test_a_warm_batched_generate_dispatches_only_libregione_hip_kernels():
     from torch.profiler import ProfilerActivity, profile
     s = _run("bf16")

@@ -285,7 +285,7 @@ def test_the_greedy_batch_and_the_default_adoption_keep_their_bits(weights):
     assert torch.equal(a.sequences, b.sequences) and all(torch.equal(x, y) for x, y in zip(a.logits, b.logits)) and a.scores is None
     a, b = s["default0"], s["default1"]
     assert torch.equal(a.sequences, b.sequences) and all(torch.equal(x, y) for x, y in zip(a.logits, b.logits))
-    # B = 1 under the opt-in keeps the one-sequence path
+    # B = 1 under the opt-in: rgn_lm_pick_rows at B = 1 is rgn_lm_pick
     got = s["hip"].generate(**s["alone_kw"][1], **FULL, **SAMPLED, uniforms=s["uni"][:, 1].contiguous(), output_scores=True)
     want = s["alone_sampled"][1]
     assert torch.equal(got.sequences, want.sequences) and all(torch.equal(x, y) for x, y in zip(got.scores, want.scores))

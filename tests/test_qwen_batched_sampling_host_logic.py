@@ -103,7 +103,7 @@ def test_a_generation_config_field_the_one_sequence_path_refuses_is_refused_for_
     with pytest.raises(_lib.RegionEHipError, match=f"generation_config.{field}"):
         e.generate(IDS, attention_mask=LEFT, max_new_tokens=T, do_sample=True)
     with pytest.raises(_lib.RegionEHipError, match=f"generation_config.{field}"):
-        e.generate(IDS[:1], max_new_tokens=T, do_sample=True)                    # the one-sequence path of the same adoption
+        e.generate(IDS[:1], max_new_tokens=T, do_sample=True)                    # one row of the same adoption: uniforms [T]   
 
 
 def test_one_row_under_the_opt_in_keeps_the_one_sequence_uniforms(monkeypatch):

@@ -19,7 +19,8 @@ GEMV A/B leg is then rgn_lm_gemv_w8 against rgn_lm_gemv_bf16 on the four layer s
 `--sampling` adopts with `sampling=True` and adds two sampled legs per encoder, alternating with the greedy leg in the one process (a
 sampling adoption asked for plain greedy search takes the default path, launch for launch): `*_s20` = (repetition_penalty 1.05, temperature
 0.7, top_k 20, top_p 0.8) and `*_s0` = (1.1, 1.0, top_k off, 0.9), uniforms from a seeded generator filled before the loop; each step then
-runs one rgn_lm_pick after lm_head.  `*_ms_per_new_token` of a sampled leg against the greedy leg's is the cost of the pick.
+runs one rgn_lm_pick_rows (B = 1: the block of rgn_lm_pick) after lm_head.  `*_ms_per_new_token` of a sampled leg against the greedy
+leg's is the cost of the pick.
 
     python tools/qwen_generate_bench.py [--iters 5] [--out profiles/r14_qwen_generate_bench.json] [--ab-out profiles/r14_lm_gemv_ab.txt]
     python tools/qwen_generate_bench.py --weights both --out profiles/r17_qwen_fp8_generate_bench.json --ab-out profiles/r17_lm_gemv_w8_ab.txt
@@ -27,18 +28,19 @@ runs one rgn_lm_pick after lm_head.  `*_ms_per_new_token` of a sampled leg again
     python tools/qwen_generate_bench.py --weights both --sampling --hip-only --no-ab --out profiles/r19_qwen_sampling_bench.json
 
 `--batch` times a `max_batch=8` adoption (bf16 and fp8 legs) at B = 1, 2, 4, 8 rows of the same length (no padding, no EOS), every leg
-alternating in the one process, beside the B = 1 leg of a default (`max_batch=1`) adoption, which issues the same launches as B = 1 of
-the other.  Per leg: ms per step = (t64 - t1) / 63 of the medians (the B prefills, which run row after row, cancel), tokens per second
-= B / that, the step against B times the B = 1 step, and against the streaming floor of ITS bytes (weights and lm_head once, B caches).
+alternating in the one process, beside the B = 1 leg of a default (`max_batch=1`) adoption, which runs the same decode loop and issues
+the same launches as B = 1 of the other (the one-row kernels: B = 1 of a `_rows` entry is the one-row entry).  Per leg: ms per step =
+(t64 - t1) / 63 of the medians (the B prefills, which run row after row, cancel), tokens per second = B / that, the step against B times the B = 1 step, and against the streaming floor of ITS bytes (weights and lm_head once, B caches).
 
     python tools/qwen_generate_bench.py --batch --no-ab --out profiles/r26_qwen_batched_generate_bench.json
     rocprofv3 --kernel-trace --stats -d DIR -o kt -- python tools/qwen_generate_bench.py --batch --hip-only --no-ab --iters 1
 
 `--batch --sampling` times a `max_batch=8, sampling=True, batch_sampling=True` adoption (bf16 and fp8) at B = 1, 2, 4, 8: a greedy leg and
 the two sampled legs above per B, all alternating in the one process.  Per leg ms per step and tokens per second, and for a sampled leg
-the time the pick adds per step = its step minus the greedy step at that B (B = 1 is the one-sequence path, rgn_lm_pick; B >= 2 runs one
-rgn_lm_pick_rows per step).  Before them `pick_rows_direct`: rgn_lm_pick_rows launched by itself at V = 152064 for B = 1..8 beside
-rgn_lm_pick; `--pick-only` runs only that (no model is built), which is what a kernel trace of the pick needs.
+the time the pick adds per step = its step minus the greedy step at that B (every B runs one rgn_lm_pick_rows per step; at B = 1 that
+entry launches the one block of rgn_lm_pick).  Before them `pick_rows_direct`: rgn_lm_pick_rows launched by itself at V = 152064 for
+B = 1..8 beside rgn_lm_pick, whose launch B = 1 dispatches to (the two arms differ by the dispatch alone); `--pick-only` runs only that
+(no model is built), which is what a kernel trace of the pick needs.
 
     python tools/qwen_generate_bench.py --batch --sampling --no-ab --out profiles/r27_qwen_batched_sampling_bench.json
     rocprofv3 --kernel-trace -d DIR -o kt -- python tools/qwen_generate_bench.py --batch --sampling --pick-only --no-ab
@@ -312,7 +314,7 @@ def batched_sampling(a, res):
     res["batches"], res["weights"], res["sampled_legs"] = list(BATCHES), "both", SAMPLED
     g = torch.Generator().manual_seed(1)
     gu = torch.Generator().manual_seed(2)
-    # B = 1 takes the one-sequence path of the adoption (rgn_lm_pick): its uniforms are [n], a batch's [n, B]
+    # one row's uniforms are [n], a batch's [n, B]
     uni = {(n, B): (torch.rand(n, generator=gu) if B == 1 else torch.rand(n, B, generator=gu)).cuda() for n in (1, NEW) for B in BATCHES}
     legs = {"greedy": dict(do_sample=False), **SAMPLED}
     for L in LENGTHS:
