@@ -81,6 +81,8 @@ def _ulp_close(got, want, frac=0.999):
 
 
 def test_row_kernels_follow_the_eager_bf16_ops():
+    """Against torch's eager ops on the same device.  The independent check - every bf16 input, fp64 intervals, exact probes, the second
+    pass of the grid-stride loops - is tests/test_gpu_encoder_rows.py."""
     from transformers.activations import ACT2FN
     g = torch.Generator(device="cuda").manual_seed(7)
     lib = _lib.lib()
