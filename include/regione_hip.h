@@ -581,6 +581,41 @@ int rgn_lm_kv_append_bf16_rows(const void* QKV, int ld, void* cache, size_t cach
  * cache rows >= n[b] are never read.  workspace_bytes >= B * rgn_lm_decode_attention_workspace_bytes(Hq, max_b n[b]). */
 int rgn_lm_decode_attention_bf16_rows(const void* Q, int ldq, const void* cache, size_t cache_stride, void* O, int ldo, const int* n_host, int B,
                                       int Hq, int Hkv, float scale, void* workspace, size_t workspace_bytes, void* stream);
+/* The WIDE step (opt-in; HipQwen25VLTextEncoder(batch_kernels="mfma")): the three weight-streaming layers for 1 <= B <=
+ * RGN_LM_MAX_WIDE_BATCH rows as a skinny GEMM on v_mfma_f32_16x16x32_bf16 (csrc/decode.hip: lm_gemm_rows_kernel).  Every weight byte is loaded
+ * from HBM once per call for all rows (16-byte non-temporal loads straight into the MFMA B operand); the rows of X are staged once per block
+ * in LDS as bf16 and read as A fragments, rows >= B of a 16-row tile are zero and never written out.
+ * k order: a block owns 16 weight rows and walks K in chunks of 1024; wave w of 4 owns k in [256 w, 256 w + 256) of a chunk, 8 MFMAs; MFMA m
+ * reads, as element j of lane group g = lane / 16, k = 32 m + 8 g + j of those 256 for bf16 weights and k = 64 (m / 2) + 16 g + 8 (m % 2) + j
+ * for fp8 weights (a 16-byte load holds 16 of them), X under the same map.  The four waves' fp32 partial sums are folded in LDS in wave order;
+ * no atomics, a repeated call is bit-identical.  None of this reads B: row b's result depends on (W, scale, bias, X[b], resid[b], N, K)
+ * only - not on B, not on what the other rows hold - and B = 1 runs the same kernel.  The sums differ from the `_rows` entries' in the last
+ * bits (another summation order), which is why this is a path of its own and not a replacement.
+ *
+ * Y[b, n] = bf16(sum_k W[n, k] X[b, k] + bias[n]), or with resid bf16(bf16(sum + bias) + resid[b, n]) (the two roundings of
+ * rgn_lm_gemv_bf16).  W [N, K] bf16 dense row-major, K % 64 == 0, K >= 64, N >= 1; strides as for rgn_lm_gemv_bf16_rows (elements, multiples
+ * of 8, ldx >= K, ldy >= N, ldr >= N, binding from B = 2 on); W and X 16-byte aligned; Y may be resid.  Columns >= N are never written. */
+#define RGN_LM_MAX_WIDE_BATCH 32
+int rgn_lm_gemm_rows_bf16(const void* W, const void* X, int ldx, const void* bias, const void* resid, int ldr, void* Y, int ldy, int B, int N,
+                          int K, void* stream);
+/* The same over ops.quantize_w8 weights (OCP e4m3fn bytes, one fp32 scale per output channel): each byte is converted in registers to the
+ * bf16 that equals it (e4m3fn is a subset of bf16) and goes through the same MFMA; wscale[n] multiplies the folded fp32 sum once:
+ * v = fma(sum, wscale[n], bias[n]). */
+int rgn_lm_gemm_rows_w8(const void* W8, const float* wscale, const void* X, int ldx, const void* bias, const void* resid, int ldr, void* Y,
+                        int ldy, int B, int N, int K, void* stream);
+/* lm_head over B <= 32 rows on the same kernel: fp32 logits, never rounded to bf16; token_out[b * token_stride] (int64) = the argmax of row
+ * b, the LOWEST index among equal values; logits_out != NULL receives fp32 [B, V] with row stride ldl >= V.  One maximum per block of 16
+ * vocabulary rows and sequence goes to the workspace; the finalize step runs one block per row.
+ * workspace_bytes >= rgn_lm_head_wide_workspace_bytes(V, B). */
+int rgn_lm_head_argmax_wide(const void* W, const void* X, int ldx, int B, int V, int K, void* token_out, int token_stride, float* logits_out,
+                            int ldl, void* workspace, size_t workspace_bytes, void* stream);
+size_t rgn_lm_head_wide_workspace_bytes(int V, int B);
+/* rgn_lm_pick_rows for 1 <= B <= RGN_LM_MAX_WIDE_BATCH rows in ONE launch: the same kernel, one block per row, so up to 32 CUs pick side by
+ * side (groups of 8 rows through rgn_lm_pick_rows run one after another: 2.2 ms a step at 32 rows against 0.5).  Row b is bit for bit
+ * rgn_lm_pick on row b alone; every other rule is rgn_lm_pick_rows'.  B = 1 is rgn_lm_pick's one-block launch. */
+int rgn_lm_pick_wide(const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty, int sample, float temperature,
+                     int top_k, double top_p, const float* uniform, void* token_out, int token_stride, float* scores_out, int lds,
+                     void* workspace, size_t workspace_bytes, void* stream);
 /* Repetition penalty and sampling for that decode (transformers' RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper,
  * TopKLogitsWarper, TopPLogitsWarper and the multinomial draw, in the order of _get_logits_processor).
  *

@@ -170,6 +170,15 @@ SIGNATURES = {
     "rgn_lm_kv_append_bf16_rows": [_c_void_p, _c_int, _c_void_p, C.c_size_t, _c_int, C.POINTER(_c_int), _c_int, _c_int, _c_int, _c_void_p],
     "rgn_lm_decode_attention_bf16_rows": [_c_void_p, _c_int, _c_void_p, C.c_size_t, _c_void_p, _c_int, C.POINTER(_c_int), _c_int, _c_int,
                                           _c_int, _c_float, _c_void_p, C.c_size_t, _c_void_p],
+    # the wide step: 1 <= B <= 32 rows on the MFMA row GEMM (batch_kernels="mfma")
+    "rgn_lm_gemm_rows_bf16": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p],
+    "rgn_lm_gemm_rows_w8": [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int,
+                            _c_void_p],
+    "rgn_lm_head_argmax_wide": [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p,
+                                C.c_size_t, _c_void_p],
+    "rgn_lm_head_wide_workspace_bytes": [_c_int, _c_int],
+    "rgn_lm_pick_wide": [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, C.c_size_t, _c_float, _c_int, _c_float, _c_int, C.c_double, _c_void_p,
+                         _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, C.c_size_t, _c_void_p],
     "rgn_lm_seen_mark": [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p],
     "rgn_lm_pick": [_c_void_p, _c_int, _c_void_p, _c_float, _c_int, _c_float, _c_int, C.c_double, _c_void_p, _c_void_p, _c_void_p,
                     _c_void_p, C.c_size_t, _c_void_p],
@@ -201,6 +210,7 @@ _RESTYPE = {"rgn_last_error": C.c_char_p, "rgn_abi_struct_bytes": C.c_size_t, "r
             "rgn_gemm_workspace_bytes": C.c_size_t, "rgn_groupnorm_workspace_bytes": C.c_size_t,
             "rgn_groupnorm_partial_bytes": C.c_size_t, "rgn_lm_decode_attention_workspace_bytes": C.c_size_t,
             "rgn_lm_head_workspace_bytes": C.c_size_t, "rgn_lm_pick_workspace_bytes": C.c_size_t,
+            "rgn_lm_head_wide_workspace_bytes": C.c_size_t,
             "rgn_rowband_side_launches": C.c_longlong, "rgn_mmdit_block_bytes": C.c_size_t}
 
 _lib = None

@@ -222,7 +222,10 @@ def hip_qwen_text_encoder_for(host, dev):
     decodes them from one weight stream); absent, it is 1; a value that is not an int in 1..8 raises ValueError naming the range.
     `pipe._regione_hip_text_batch_sampling = True` before the first call adopts with `batch_sampling=True` (such a batch takes the decoding
     configuration of `sampling=True`); absent, it is False; a value that is not a bool, or True without the two switches above, raises
-    ValueError naming the attribute that is wrong or missing, with nothing adopted or cached."""
+    ValueError naming the attribute that is wrong or missing, with nothing adopted or cached.
+    `pipe._regione_hip_text_batch_kernels = "mfma"` before the first call adopts with `batch_kernels="mfma"` (every decode step on the MFMA
+    row GEMM); with it `_regione_hip_text_batch` is accepted in 1..32.  Absent, it is "fma" and every message is as above; another value
+    raises ValueError naming the two, with nothing adopted or cached."""
     if _memo(host, "_regione_hip_text") is False:
         return None
     cached = _memo(host, "_regione_hip_qwen_text")
@@ -234,16 +237,20 @@ def hip_qwen_text_encoder_for(host, dev):
     sampling = host.__dict__.get("_regione_hip_text_sampling", False)
     if not isinstance(sampling, bool):
         raise ValueError(f"pipe._regione_hip_text_sampling = {sampling!r}: True and False are accepted")
+    kernels = host.__dict__.get("_regione_hip_text_batch_kernels", "fma")
+    if not isinstance(kernels, str) or kernels not in ("fma", "mfma"):
+        raise ValueError(f"pipe._regione_hip_text_batch_kernels = {kernels!r}: \"fma\" and \"mfma\" are accepted")
     batch = host.__dict__.get("_regione_hip_text_batch", 1)
-    if isinstance(batch, bool) or not isinstance(batch, int) or not 1 <= batch <= 8:
-        raise ValueError(f"pipe._regione_hip_text_batch = {batch!r}: an int in 1..8 is accepted")
+    top = 32 if kernels == "mfma" else 8
+    if isinstance(batch, bool) or not isinstance(batch, int) or not 1 <= batch <= top:
+        raise ValueError(f"pipe._regione_hip_text_batch = {batch!r}: an int in 1..{top} is accepted")
     rows_pick = host.__dict__.get("_regione_hip_text_batch_sampling", False)
     if not isinstance(rows_pick, bool):
         raise ValueError(f"pipe._regione_hip_text_batch_sampling = {rows_pick!r}: True and False are accepted")
     if rows_pick and not sampling:
         raise ValueError("pipe._regione_hip_text_batch_sampling = True needs pipe._regione_hip_text_sampling = True")
     if rows_pick and batch < 2:
-        raise ValueError("pipe._regione_hip_text_batch_sampling = True needs pipe._regione_hip_text_batch = N with N in 2..8")
+        raise ValueError(f"pipe._regione_hip_text_batch_sampling = True needs pipe._regione_hip_text_batch = N with N in 2..{top}")
     mod = getattr(host, "text_encoder", None)
     enc = None
     if type(mod).__name__ == "Qwen2_5_VLForConditionalGeneration" and getattr(mod, "config", None) is not None:
@@ -254,7 +261,8 @@ def hip_qwen_text_encoder_for(host, dev):
         enc = _adopt_or_keep("text_encoder", why, stacklevel=3,
                              make=lambda: QT.HipQwen25VLTextEncoder(mod, dev, weights=fmt, **({"sampling": True} if sampling else {}),
                                                                     **({"max_batch": batch} if batch > 1 else {}),
-                                                                    **({"batch_sampling": True} if rows_pick else {})))
+                                                                    **({"batch_sampling": True} if rows_pick else {}),
+                                                                    **({"batch_kernels": "mfma"} if kernels == "mfma" else {})))
         if enc is not None and _memo(host, "_regione_hip_vision") is not False:
             from .. import qwen_vision as QV
             tower = _adopt_or_keep("vision tower", QV.vision_refusal(mod.config), lambda: QV.HipQwen25VLVisionTower(mod, dev), stacklevel=3)

@@ -22,6 +22,10 @@
 //   lm_pick_rows_kernel         the block of lm_pick_kernel once per row (blockIdx.x = b), each on a CU of its own: the same device function
 // That invariant is what the host side rests on: an operation is ONE implementation over 1 <= B <= 8 rows, reached through its `_rows`
 // entry, which launches the one-row kernels at B == 1 and the `_rows` kernels from B = 2 on; the one-row entry is its B = 1 case.
+// and, opt-in (batch_kernels="mfma"), the weight-streaming layers of that step for B <= 32 sequences on the matrix unit:
+//   lm_gemm_rows_kernel         the three products as a skinny GEMM on v_mfma_f32_16x16x32_bf16: weights straight from HBM into the B operand,
+//                               the rows of x in LDS as bf16, K split over the four waves and folded in wave order; row b depends on row b
+//                               alone, but its sums are not the `_rows` kernels' sums in the last bits (described at the kernel)
 // No atomics; every reduction has a fixed order (lanes: the butterfly of wave_sum; k, keys and slices: ascending), so a repeated call is
 // bit-identical.
 #include <math.h>
@@ -811,6 +815,149 @@ __global__ __launch_bounds__(PICK_T) void lm_pick_rows_kernel(const float* __res
                 token_out + b * (size_t)token_stride, s + b * lds);
 }
 
+// ---- the wide step: 1 <= B <= 32 rows per step on the matrix unit (opt-in: batch_kernels="mfma") --------------------------------------
+// Y [B, N] = X [B, K] W^T as a skinny GEMM on v_mfma_f32_16x16x32_bf16: D[b][n] += sum_k A[b][k] B[k][n] with the 16 rows of X as A and
+// 16 weight rows as B, so a weight byte goes HBM -> VGPR -> matrix unit once for all rows and never through LDS.
+//   block   4 waves, ONE tile of 16 weight rows n0 .. n0 + 15 (grid = ceil(N / 16)); a row past N re-reads row N - 1 and writes nothing
+//   K split the block walks K in chunks of GEMM_KC = 1024; wave w owns k in [kb + 256 w, kb + 256 w + 256) of chunk kb (GEMM_KW = 256 k per
+//           wave and chunk = 8 MFMAs), so the split depends on K alone and is uneven whenever K % 1024 != 0; MFMAs past K are skipped
+//   W       lane l = (n = l & 15, g = l >> 4) loads row n0 + n in 16-byte non-temporal vectors, all 8 (bf16) / 4 (fp8) of the wave's next
+//           chunk issued before the products of the current one
+//   k map   bf16: MFMA m of a wave's 256 k reads element j of lane group g at k = 32 m + 8 g + j (vector m of the lane);
+//           fp8:  a 16-byte vector holds 16 k, so MFMA m reads k = 64 (m >> 1) + 16 g + 8 (m & 1) + j (half m & 1 of vector m >> 1);
+//           the A fragment of X is read from LDS at the SAME k, so each product meets its own x (the integer and one-hot probes of
+//           tests/test_gpu_lm_rows_mfma.py change if the two maps differ)
+//   fp8     each e4m3fn byte -> fp32 (v_cvt_pk_f32_fp8, exact) -> its upper 16 bits: e4m3fn is a subset of bf16, so the MFMA multiplies the
+//           very values lm_gemv_w8_kernel multiplies; the per-channel scale multiplies the folded fp32 sum once
+//   X       the chunk's rows b < B are staged once per block in LDS as bf16, [16 TM][1024], 16-byte slot s of row r at slot s ^ (r & 15)
+//           (the 16 rows a ds_read_b128 of an A fragment touches land in 16 different bank groups); rows >= B are zero and never written out
+//   fold    the four waves' accumulators go to LDS and are added in wave order 0, 1, 2, 3 by the thread that owns (b, n): no atomics
+// Row b's result is a function of (W, scale, bias, X[b], resid[b], N, K) alone: the k split and the fold order do not read B, and an MFMA
+// output element is the dot product of its own row and column.  HEAD keeps the logits fp32, writes them if asked and one (value, lowest
+// index) maximum per block and row; lm_head_finalize_rows_kernel folds those per row.
+constexpr int GEMM_KW = 256, GEMM_KC = 4 * GEMM_KW;
+
+__device__ __forceinline__ bf16x8 w8_bf16x8(uint32_t a, uint32_t b) {            // 8 e4m3fn bytes (k ascending) as the 8 bf16 that equal them
+    const uint32_t w[2] = {a, b};
+    uint32_t o[4];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[e], true);
+        o[2 * e] = (__float_as_uint(lo[0]) >> 16) | (__float_as_uint(lo[1]) & 0xffff0000u);
+        o[2 * e + 1] = (__float_as_uint(hi[0]) >> 16) | (__float_as_uint(hi[1]) & 0xffff0000u);
+    }
+    return __builtin_bit_cast(bf16x8, make_uint4(o[0], o[1], o[2], o[3]));
+}
+
+template <int TM, bool W8, bool HEAD>
+__global__ __launch_bounds__(256) void lm_gemm_rows_kernel(const uint8_t* __restrict__ W, const float* __restrict__ wscale,
+                                                           const uint16_t* __restrict__ X, int ldx, const uint16_t* __restrict__ bias,
+                                                           const uint16_t* resid, int ldr, uint16_t* Y, int ldy, float* __restrict__ logits,
+                                                           int ldl, float* __restrict__ part_v, int* __restrict__ part_i, int nparts, int B,
+                                                           int N, int K) {
+    constexpr int ROWS = 16 * TM, ES = W8 ? 1 : 2, U = W8 ? GEMM_KW / 64 : GEMM_KW / 32;   // 16-byte weight loads per lane and chunk
+    constexpr int VR = GEMM_KC / 8, NP = ROWS / 2;                               // staging: 16-byte slots per row; rows per thread
+    extern __shared__ __attribute__((aligned(16))) uint8_t gemm_lds[];
+    uint4* xs = (uint4*)gemm_lds;                                                // [ROWS][VR], swizzled; 16 / 32 KB x 2
+    float* red = (float*)gemm_lds;                                               // after the loop: [4 waves][TM][4][64]
+    float* fin = red + 4 * TM * 256;                                             // HEAD: [ROWS][16] folded logits
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ln = lane & 15, lg = lane >> 4;
+    const int n0 = blockIdx.x * 16;
+    const uint8_t* wr = W + (size_t)(n0 + ln < N ? n0 + ln : N - 1) * (size_t)K * ES;
+    f32x4 acc[TM];
+#pragma unroll
+    for (int t = 0; t < TM; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int sv = tid % VR, sr = tid / VR;                                      // staging: slot sv of rows sr, sr + 2, ...
+    for (int i = tid; i < ROWS * VR; i += 256) xs[i] = make_uint4(0u, 0u, 0u, 0u);   // rows >= B stay zero
+    uint4 xv[NP];
+    u32x4 wv[U];
+    auto issue = [&](int kb) {                                                   // x first: waiting for it leaves W in flight
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            const int b = sr + 2 * j;
+            xv[j] = b < B && kb + sv * 8 < K ? *(const uint4*)(X + (size_t)b * ldx + kb + sv * 8) : make_uint4(0u, 0u, 0u, 0u);
+        }
+        const int kw = kb + wave * GEMM_KW;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int k = kw + (W8 ? 64 * u + 16 * lg : 32 * u + 8 * lg);        // K % 64 == 0: a vector is inside K or past it as a whole
+            wv[u] = k < K ? __builtin_nontemporal_load((const u32x4*)(wr + (size_t)k * ES)) : u32x4{0u, 0u, 0u, 0u};
+        }
+    };
+    issue(0);
+    for (int kb = 0; kb < K; kb += GEMM_KC) {
+        __syncthreads();                                                         // the zero fill / every wave is done with the previous chunk
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            const int b = sr + 2 * j;
+            if (b < B) xs[b * VR + (sv ^ (b & 15))] = xv[j];
+        }
+        __syncthreads();
+        u32x4 wc[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) wc[u] = wv[u];
+        if (kb + GEMM_KC < K) issue(kb + GEMM_KC);                               // the next chunk flies during this one's products
+        const int kw = kb + wave * GEMM_KW;
+#pragma unroll
+        for (int m = 0; m < GEMM_KW / 32; ++m) {
+            if (kw + 32 * m < K) {                                               // wave-uniform; LDS past K is stale
+                bf16x8 bf;
+                int kl;                                                          // this lane's first k inside the chunk
+                if constexpr (W8) {
+                    const u32x4 v = wc[m >> 1];
+                    bf = (m & 1) ? w8_bf16x8(v.z, v.w) : w8_bf16x8(v.x, v.y);
+                    kl = wave * GEMM_KW + 64 * (m >> 1) + 16 * lg + 8 * (m & 1);
+                } else {
+                    bf = __builtin_bit_cast(bf16x8, wc[m]);
+                    kl = wave * GEMM_KW + 32 * m + 8 * lg;
+                }
+#pragma unroll
+                for (int t = 0; t < TM; ++t) {
+                    const int r = 16 * t + ln;
+                    const bf16x8 af = __builtin_bit_cast(bf16x8, xs[r * VR + ((kl >> 3) ^ ln)]);
+                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc[t], 0, 0, 0);
+                }
+            }
+        }
+    }
+    __syncthreads();                                                             // xs is read out: its memory becomes `red`
+#pragma unroll
+    for (int t = 0; t < TM; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[((wave * TM + t) * 4 + r) * 64 + lane] = acc[t][r];
+    __syncthreads();
+    // thread -> (b, n): accumulator element r of lane 16 g + n of tile t is row 16 t + 4 g + r, column n
+#pragma unroll
+    for (int o = tid; o < ROWS * 16; o += 256) {
+        const int b = o >> 4, nl = o & 15, n = n0 + nl, t = b >> 4, g = (b & 15) >> 2, r = b & 3;
+        const int at = (t * 4 + r) * 64 + 16 * g + nl;
+        float s = red[at];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) s += red[w * TM * 256 + at];                // wave order
+        if constexpr (HEAD) {
+            fin[o] = s;
+            if (logits && b < B && n < N) logits[(size_t)b * ldl + n] = s;
+        } else if (b < B && n < N) {
+            const float bs = bias ? bf2f(bias[n]) : 0.f;
+            float v;
+            if constexpr (W8) v = fmaf(s, wscale[n], bs);                        // the scale once, on the folded sum
+            else v = s + bs;
+            Y[(size_t)b * ldy + n] = resid ? f2bf(rbf(v) + bf2f(resid[(size_t)b * ldr + n])) : f2bf(v);   // two roundings
+        }
+    }
+    if constexpr (HEAD) {
+        __syncthreads();
+        if (tid < B) {
+            float best = fin[tid * 16];                                          // row n0 exists in every block
+            int at = n0;
+            for (int i = 1; i < 16; ++i)                                         // ascending index, strict >: the first maximum
+                if (n0 + i < N && fin[tid * 16 + i] > best) { best = fin[tid * 16 + i]; at = n0 + i; }
+            part_v[(size_t)tid * nparts + blockIdx.x] = best;
+            part_i[(size_t)tid * nparts + blockIdx.x] = at;
+        }
+    }
+}
+
 }  // namespace rgn
 
 using namespace rgn;
@@ -831,6 +978,7 @@ static void launch_gemv_rows(int B, int N, hipStream_t st, Args... args) {
 // prefix of its messages).  B == 1 launches the one-row kernels and reads no stride, so stride conditions bind from B = 2 on.
 static inline bool dal16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 static inline bool batch_ok(int B) { return B >= 1 && B <= RGN_LM_MAX_BATCH; }
+static inline bool wide_ok(int B) { return B >= 1 && B <= RGN_LM_MAX_WIDE_BATCH; }      // the wide entries (batch_kernels="mfma")
 static int bad(const char* who, const char* what) { snprintf(g_err, sizeof(g_err), "%s: %s", who, what); return RGN_E_BADARG; }
 
 // The linear layer in either weight format: W8 reads e4m3fn bytes with `wscale`, else W is bf16 and wscale null.
@@ -862,6 +1010,30 @@ static int gemv(const char* who, const void* W, const float* wscale, const void*
                            (float*)nullptr, (float*)nullptr, (int*)nullptr, N, K);
     }
     return check_launch(W8 ? "lm_gemv_w8_kernel" : "lm_gemv_kernel");
+}
+
+// ---- the wide entries: 1 <= B <= RGN_LM_MAX_WIDE_BATCH rows on lm_gemm_rows_kernel, the same kernel at every B ------------------------------
+template <bool W8, bool HEAD, typename... Args>
+static void launch_gemm_rows(int B, int N, hipStream_t st, Args... args) {
+    const dim3 grid((N + 15) / 16), block(256);
+    if (B <= 16) hipLaunchKernelGGL((lm_gemm_rows_kernel<1, W8, HEAD>), grid, block, (size_t)16 * GEMM_KC * 2, st, args...);
+    else hipLaunchKernelGGL((lm_gemm_rows_kernel<2, W8, HEAD>), grid, block, (size_t)32 * GEMM_KC * 2, st, args...);
+}
+
+template <bool W8>
+static int gemm_rows(const char* who, const void* W, const float* wscale, const void* X, int ldx, const void* bias, const void* resid, int ldr,
+                     void* Y, int ldy, int B, int N, int K, void* stream) {
+    if (!W || (W8 && !wscale) || !X || !Y || N < 1 || K < 64)
+        return bad(who, W8 ? "bad argument (W8, wscale, X, Y non-null; N >= 1; K >= 64)" : "bad argument (W, X, Y non-null; N >= 1; K >= 64)");
+    if (!wide_ok(B)) return bad(who, "B outside [1, 32]");
+    if (K % 64) return bad(who, "K must be a multiple of 64");
+    if (B > 1 && (ldx % 8 || ldy % 8 || ldx < K || ldy < N || (resid && (ldr % 8 || ldr < N))))
+        return bad(who, "strides must be multiples of 8, ldx >= K, ldy >= N, ldr >= N");
+    if (!dal16(W) || !dal16(wscale) || !dal16(X)) return bad(who, W8 ? "W8, wscale and X must be 16-byte aligned" : "W and X must be 16-byte aligned");
+    if (((uintptr_t)Y | (uintptr_t)bias | (uintptr_t)resid) & 1u) return bad(who, "Y, bias and resid must be 2-byte aligned");
+    launch_gemm_rows<W8, false>(B, N, (hipStream_t)stream, (const uint8_t*)W, wscale, (const uint16_t*)X, ldx, (const uint16_t*)bias,
+                                (const uint16_t*)resid, ldr, (uint16_t*)Y, ldy, (float*)nullptr, 0, (float*)nullptr, (int*)nullptr, 0, B, N, K);
+    return check_launch("lm_gemm_rows_kernel");
 }
 
 extern "C" {
@@ -922,6 +1094,45 @@ int rgn_lm_head_argmax(const void* W, const void* x, int V, int K, void* token_o
 int rgn_lm_head_argmax_rows(const void* W, const void* X, int ldx, int B, int V, int K, void* token_out, int token_stride, float* logits_out,
                             int ldl, void* workspace, size_t workspace_bytes, void* stream) {
     return head_argmax("lm_head_argmax_rows", W, X, ldx, B, V, K, token_out, token_stride, logits_out, ldl, workspace, workspace_bytes, stream);
+}
+
+int rgn_lm_gemm_rows_bf16(const void* W, const void* X, int ldx, const void* bias, const void* resid, int ldr, void* Y, int ldy, int B, int N,
+                          int K, void* stream) {
+    return gemm_rows<false>("lm_gemm_rows", W, nullptr, X, ldx, bias, resid, ldr, Y, ldy, B, N, K, stream);
+}
+int rgn_lm_gemm_rows_w8(const void* W8, const float* wscale, const void* X, int ldx, const void* bias, const void* resid, int ldr, void* Y,
+                        int ldy, int B, int N, int K, void* stream) {
+    return gemm_rows<true>("lm_gemm_rows_w8", W8, wscale, X, ldx, bias, resid, ldr, Y, ldy, B, N, K, stream);
+}
+
+static inline int wide_parts(int V) { return (V + 15) / 16; }                // lm_gemm_rows_kernel: 16 rows per block
+
+size_t rgn_lm_head_wide_workspace_bytes(int V, int B) {
+    return V < 1 || !wide_ok(B) ? 0 : (size_t)B * wide_parts(V) * (sizeof(float) + sizeof(int));
+}
+
+int rgn_lm_head_argmax_wide(const void* W, const void* X, int ldx, int B, int V, int K, void* token_out, int token_stride, float* logits_out,
+                            int ldl, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "lm_head_argmax_wide";
+    if (!W || !X || !token_out || !workspace || V < 1 || K < 64)
+        return bad(who, "bad argument (W, X, token_out, workspace non-null; V >= 1; K >= 64)");
+    if (!wide_ok(B)) return bad(who, "B outside [1, 32]");
+    if (K % 64) return bad(who, "K must be a multiple of 64");
+    if (B > 1 && (ldx % 8 || ldx < K || token_stride < 1 || (logits_out && ldl < V)))
+        return bad(who, "ldx must be a multiple of 8 and >= K, token_stride >= 1, ldl >= V");
+    if (!dal16(W) || !dal16(X)) return bad(who, "W and X must be 16-byte aligned");
+    if (((uintptr_t)token_out & 7u) || ((uintptr_t)logits_out & 3u) || ((uintptr_t)workspace & 3u))
+        return bad(who, "token_out must be 8-byte, logits_out and workspace 4-byte aligned");
+    if (workspace_bytes < rgn_lm_head_wide_workspace_bytes(V, B)) return bad(who, "workspace smaller than rgn_lm_head_wide_workspace_bytes(V, B)");
+    const int np = wide_parts(V);
+    float* pv = (float*)workspace;
+    int* pi = (int*)(pv + (size_t)B * np);
+    const hipStream_t st = (hipStream_t)stream;
+    launch_gemm_rows<false, true>(B, V, st, (const uint8_t*)W, (const float*)nullptr, (const uint16_t*)X, ldx, (const uint16_t*)nullptr,
+                                  (const uint16_t*)nullptr, 0, (uint16_t*)nullptr, 0, logits_out, ldl, pv, pi, np, B, V, K);
+    hipLaunchKernelGGL(lm_head_finalize_rows_kernel, dim3(B), dim3(1024), 0, st, (const float*)pv, (const int*)pi, np, (int64_t*)token_out,
+                       B > 1 ? token_stride : 1);
+    return check_launch(who);
 }
 
 // L rows of QKV into each of B caches from row row0[b] on.  The two public forms are its two edges: L rows into ONE cache (the prefill;
@@ -1031,12 +1242,12 @@ static void pick_allow_lds(const void* kernel, bool (&done)[64]) {
     }
 }
 
-static int pick(const char* who, bool rows, const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty,
+static int pick(const char* who, bool rows, bool wide, const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty,
                 int sample, float temperature, int top_k, double top_p, const float* uniform, void* token_out, int token_stride,
                 float* scores_out, int lds, void* workspace, size_t workspace_bytes, void* stream) {
     if (!logits || !seen || !token_out || !workspace || V < 1 || V > PICK_MAX_V)
         return bad(who, "bad argument (logits, seen, token_out, workspace non-null; 1 <= V <= 1048576)");
-    if (!batch_ok(B)) return bad(who, "B outside [1, 8]");
+    if (wide ? !wide_ok(B) : !batch_ok(B)) return bad(who, wide ? "B outside [1, 32]" : "B outside [1, 8]");
     if (B > 1 && (ldl < V || (scores_out && lds < V) || seen_stride < (size_t)V || token_stride < 1))
         return bad(who, "ldl >= V, lds >= V, seen_stride >= V, token_stride >= 1");
     if (!(penalty > 0.f) || !(penalty < INFINITY)) return bad(who, "the repetition penalty must be in (0, inf)");
@@ -1070,13 +1281,19 @@ static int pick(const char* who, bool rows, const float* logits, int ldl, int B,
 
 int rgn_lm_pick(const float* logits, int V, void* seen, float penalty, int sample, float temperature, int top_k, double top_p,
                 const float* uniform, void* token_out, float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
-    return pick("lm_pick", false, logits, 0, 1, V, seen, 0, penalty, sample, temperature, top_k, top_p, uniform, token_out, 0, scores_out, 0, workspace,
+    return pick("lm_pick", false, false, logits, 0, 1, V, seen, 0, penalty, sample, temperature, top_k, top_p, uniform, token_out, 0, scores_out, 0, workspace,
                 workspace_bytes, stream);
 }
 int rgn_lm_pick_rows(const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty, int sample, float temperature,
                      int top_k, double top_p, const float* uniform, void* token_out, int token_stride, float* scores_out, int lds,
                      void* workspace, size_t workspace_bytes, void* stream) {
-    return pick("lm_pick_rows", true, logits, ldl, B, V, seen, seen_stride, penalty, sample, temperature, top_k, top_p, uniform, token_out,
+    return pick("lm_pick_rows", true, false, logits, ldl, B, V, seen, seen_stride, penalty, sample, temperature, top_k, top_p, uniform, token_out,
+                token_stride, scores_out, lds, workspace, workspace_bytes, stream);
+}
+int rgn_lm_pick_wide(const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty, int sample, float temperature,
+                     int top_k, double top_p, const float* uniform, void* token_out, int token_stride, float* scores_out, int lds,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    return pick("lm_pick_wide", true, true, logits, ldl, B, V, seen, seen_stride, penalty, sample, temperature, top_k, top_p, uniform, token_out,
                 token_stride, scores_out, lds, workspace, workspace_bytes, stream);
 }
 

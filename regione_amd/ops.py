@@ -715,3 +715,38 @@ def device_info() -> Tuple[int, int, int]:
     cu, clk, mem = C.c_int(), C.c_int(), C.c_size_t()
     _lib.check(_lib.lib().rgn_device_info(C.byref(cu), C.byref(clk), C.byref(mem)), "rgn_device_info")
     return cu.value, clk.value, mem.value
+
+
+# ---- the wide decode step: 1 <= B <= 32 rows on the MFMA row GEMM (csrc/decode.hip: lm_gemm_rows_kernel) -------------------------------
+LM_MAX_WIDE_BATCH = 32                                                           # RGN_LM_MAX_WIDE_BATCH of include/regione_hip.h
+
+
+def lm_gemm_rows(X: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Y [B, N] bf16 = X [B, K] W^T (+ bias) (+ resid: the two roundings of `h + linear(a)`) for 1 <= B <= 32 rows from one stream of
+    W [N, K]: bf16 (rgn_lm_gemm_rows_bf16) or an ops.quantize_w8 weight (rgn_lm_gemm_rows_w8).  Row strides are free (multiples of 8
+    elements); `out` may be `resid`.  The C entry validates everything else."""
+    B, N = X.shape[0], W.shape[0]
+    if out is None:
+        out = torch.empty(B, N, dtype=torch.bfloat16, device=X.device)
+    tail = (_p(X), X.stride(0), _p(bias), _p(resid), resid.stride(0) if resid is not None else 0, _p(out), out.stride(0), B, N, W.shape[1],
+            _stream())
+    if W.dtype == FP8:
+        _lib.check(_lib.lib().rgn_lm_gemm_rows_w8(_p(W), _p(_wscale(W)), *tail), "rgn_lm_gemm_rows_w8")
+    else:
+        _lib.check(_lib.lib().rgn_lm_gemm_rows_bf16(_p(W), *tail), "rgn_lm_gemm_rows_bf16")
+    return out
+
+
+def lm_head_argmax_wide(X: torch.Tensor, W: torch.Tensor, logits: bool = False):
+    """(tokens [B] int64, fp32 logits [B, V] or None) of rgn_lm_head_argmax_wide: the argmax of X [B, K] W^T per row over W [V, K] bf16, the
+    lowest index on a tie, for 1 <= B <= 32 rows."""
+    lib = _lib.lib()
+    B, V = X.shape[0], W.shape[0]
+    nbytes = lib.rgn_lm_head_wide_workspace_bytes(V, B)
+    ws = torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=X.device)
+    tok = torch.empty(B, dtype=torch.int64, device=X.device)
+    z = torch.empty(B, V, dtype=torch.float32, device=X.device) if logits else None
+    rc = lib.rgn_lm_head_argmax_wide(_p(W), _p(X), X.stride(0), B, V, W.shape[1], _p(tok), 1, _p(z), V, _p(ws), nbytes, _stream())
+    _lib.check(rc, "rgn_lm_head_argmax_wide")
+    return tok, z

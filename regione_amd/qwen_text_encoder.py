@@ -59,6 +59,20 @@ Qwen (the pad id is also an EOS id), penalises an EOS in padded rows only; not m
 `uniforms`, row b's tokens, fp32 logits and scores are bit for bit those of the B = 1 sampled call on row b's unpadded prompt with
 `uniforms[:, b]`.  A configuration that is greedy as before runs the greedy launches unchanged.  Not measured: real checkpoints.
 
+`batch_kernels="mfma"` (opt-in; the default "fma" is the object described above in every respect and refuses `max_batch` > 8 as before)
+accepts `max_batch` in 1..32 and runs the weight-streaming layers of EVERY decode step, B = 1 included, on the MFMA row GEMM of
+csrc/decode.hip (lm_gemm_rows_kernel): rgn_lm_gemm_rows_bf16 / rgn_lm_gemm_rows_w8 for the four projections and rgn_lm_head_argmax_wide for
+`lm_head`.  A weight byte is loaded once per step for all rows, straight into the B operand of v_mfma_f32_16x16x32_bf16 (fp8 bytes are
+widened exactly to bf16 in registers; the scale multiplies the folded sum once); the rows sit in LDS as bf16.  The per-row entries
+rgn_lm_kv_append_bf16_rows and rgn_lm_decode_attention_bf16_rows are called in groups of at most 8 rows with offset pointers, and the pick
+is ONE rgn_lm_pick_wide (the kernel of rgn_lm_pick_rows with up to 32 blocks); nothing crosses rows there, so every row keeps its bits.
+The batch stays invariant over the whole range: row b's tokens, fp32 logits and processed scores are bit for bit those of the B = 1 call
+of the SAME adoption on that prompt alone.  Against an "fma" adoption
+the sums differ in their last bits (another summation order), so tokens agree wherever the top-2 logit gap is not within that error.
+`weights="fp8"`, `sampling=True` and `batch_sampling=True` combine with it as before (`uniforms` [T, B], the byte map [B, V]); the prefill,
+the KV layout, EOS / pad assembly and `sync_every` are untouched.  KV memory: 28 layers x cap x 2 x 4 x 128 bf16 = 235 MB per row at
+cap = 4096, so 7.5 GB at 32 rows.  Not measured: real checkpoints.
+
 There is no eager fallback inside: what the kernels do not implement raises RegionEHipError before any launch, and the adapter
 (regione_amd.adapters, components.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
 only; every call returns freshly allocated outputs.
@@ -257,6 +271,8 @@ def image_rows(input_ids: torch.Tensor, lengths, image_token_id: int, n_embeds: 
 
 # ---- generate over a batch (`max_batch=`): the host rules of transformers' greedy search for several rows -----------------------------
 MAX_BATCH = 8                                                                    # RGN_LM_MAX_BATCH of include/regione_hip.h
+MAX_WIDE_BATCH = 32                                                              # RGN_LM_MAX_WIDE_BATCH: the rows of batch_kernels="mfma"
+BATCH_KERNELS = ("fma", "mfma")                                                  # what multiplies the rows of a decode step (`batch_kernels=`)
 
 
 def left_valid_lengths(attention_mask: Optional[torch.Tensor], B: int, L: int, what: str = "HipQwen25VLTextEncoder"):
@@ -336,7 +352,8 @@ def assemble_sequences(prompt_ids: torch.Tensor, new_ids: torch.Tensor, eos, pad
 def _bound(fn, name, *args):
     """(`fn` with `args` bound, `name`): the arguments are converted to their ctypes objects once, a host array to a pointer to its
     memory (what is written into the array later is what the call reads), so that calling the result marshals nothing."""
-    conv = [ctypes.cast(a, t) if isinstance(a, ctypes.Array) else t(a) for t, a in zip(fn.argtypes, args, strict=True)]
+    conv = [a if isinstance(a, ctypes._Pointer) else ctypes.cast(a, t) if isinstance(a, ctypes.Array) else t(a)
+            for t, a in zip(fn.argtypes, args, strict=True)]
     return functools.partial(fn, *conv), name
 
 
@@ -348,12 +365,18 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
     what = "HipQwen25VLTextEncoder"
 
     def __init__(self, module_or_state_dict, device=None, config=None, max_length: int = 4096, vision=None, weights: str = "bf16",
-                 sampling: bool = False, max_batch: int = 1, batch_sampling: bool = False):
+                 sampling: bool = False, max_batch: int = 1, batch_sampling: bool = False, batch_kernels: str = "fma"):
         if weights not in WEIGHT_FORMATS:
             _refuse(self.what, f"weights={weights!r} (the layer matrices are kept as one of {WEIGHT_FORMATS})")
         if not isinstance(sampling, bool):
             _refuse(self.what, f"sampling={sampling!r} (True or False)")
-        if isinstance(max_batch, bool) or not isinstance(max_batch, int) or not 1 <= max_batch <= MAX_BATCH:
+        if not isinstance(batch_kernels, str) or batch_kernels not in BATCH_KERNELS:
+            _refuse(self.what, f"batch_kernels={batch_kernels!r} (one of {BATCH_KERNELS}: the vector-ALU row kernels, or the MFMA row GEMM)")
+        wide = batch_kernels == "mfma"
+        if isinstance(max_batch, bool) or not isinstance(max_batch, int) or not 1 <= max_batch <= (MAX_WIDE_BATCH if wide else MAX_BATCH):
+            if wide:
+                _refuse(self.what, f"max_batch={max_batch!r} under batch_kernels=\"mfma\" (an int in [1, {MAX_WIDE_BATCH}]: the rows one "
+                                   "generate decodes from one weight stream on the MFMA row GEMM)")
             _refuse(self.what, f"max_batch={max_batch!r} (an int in [1, {MAX_BATCH}]: the rows one generate decodes from one weight stream)")
         if not isinstance(batch_sampling, bool):
             _refuse(self.what, f"batch_sampling={batch_sampling!r} (True or False)")
@@ -362,6 +385,7 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         if batch_sampling and max_batch == 1:
             _refuse(self.what, "batch_sampling=True with max_batch=1 (it needs max_batch > 1: one row takes the one-sequence pick)")
         self.weights, self.sampling, self.max_batch, self.batch_sampling = weights, sampling, max_batch, batch_sampling
+        self.batch_kernels = batch_kernels
         sd, cfg, dev, mod = _source(module_or_state_dict, config, device, self.what)
         self.vision = vision                               # a HipQwen25VLVisionTower, or None: the adopted module's eager tower
         why = qwen25vl_refusal(cfg)
@@ -726,7 +750,12 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         lib, dev, d, V = _lib.lib(), self.device, self.d, self.tok.shape[0]
         nmax = max(lens)
         cap, kvw, nl = nmax + T, 2 * self.Hkv * HEAD_DIM, len(self.layers)
-        ws_a, ws_h = B * lib.rgn_lm_decode_attention_workspace_bytes(self.Hq, cap), B * lib.rgn_lm_head_workspace_bytes(V)
+        wide = self.batch_kernels == "mfma"                                       # the MFMA row GEMM at every B; the per-row entries in groups
+        ws_a = B * lib.rgn_lm_decode_attention_workspace_bytes(self.Hq, cap)
+        ws_h = lib.rgn_lm_head_wide_workspace_bytes(V, B) if wide else B * lib.rgn_lm_head_workspace_bytes(V)
+        head_rows, head_name = (lib.rgn_lm_head_argmax_wide, "rgn_lm_head_argmax_wide") if wide else \
+            (lib.rgn_lm_head_argmax_rows, "rgn_lm_head_argmax_rows")
+        groups = [(g0, min(MAX_BATCH, B - g0)) for g0 in range(0, B, MAX_BATCH)]  # at most 8 rows per launch of a per-row entry
         c = self.kv.get((B, cap), dict(cache=(nl, B, cap, kvw), h=(B, d), n=(B, d), qkv=(B, self.qkv_cols), a=(B, self.Hq * HEAD_DIM),
                                        ff=(B, 2 * self.F), g=(B, self.F), ws_a=((ws_a + 1) // 2,), ws_h=((ws_h + 1) // 2,)))
         t = self.buf.get(nmax, dict(h=(nmax, d), n=(nmax, d), qkv=(nmax, self.qkv_cols), a=(nmax, self.Hq * HEAD_DIM), ff=(nmax, 2 * self.F),
@@ -741,11 +770,14 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         scores = None
         if plan is None:
             def pick(k):                                                          # tokens k of the B rows from the normalised rows in c["n"]
-                ck(lib.rgn_lm_head_argmax_rows(_p(head), pn, d, B, V, d, pnew + 8 * B * k, 1, None if logits is None else _p(logits[k]), V,
-                                               _p(c["ws_h"]), ws_h, st), "rgn_lm_head_argmax_rows")
+                ck(head_rows(_p(head), pn, d, B, V, d, pnew + 8 * B * k, 1, None if logits is None else _p(logits[k]), V, _p(c["ws_h"]), ws_h, st),
+                   head_name)
         else:
             # the pick of this generate, chosen once: lm_head writes the fp32 rows, ONE rgn_lm_pick_rows turns them into the step's id row
-            ws_p = B * lib.rgn_lm_pick_workspace_bytes(V)
+            ws_1 = lib.rgn_lm_pick_workspace_bytes(V)
+            pick_rows, pick_name, pick_groups = (lib.rgn_lm_pick_wide, "rgn_lm_pick_wide", [(0, B)]) if wide else \
+                (lib.rgn_lm_pick_rows, "rgn_lm_pick_rows", groups)
+            ws_p = B * ws_1
             seen = torch.empty(B, V, dtype=torch.uint8, device=dev)
             zrows = torch.empty(B, V, dtype=torch.float32, device=dev) if logits is None else None
             pick_ws = torch.empty((ws_p + 3) // 4, dtype=torch.float32, device=dev)
@@ -762,11 +794,12 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
 
             def pick(k):
                 z = logits[k] if logits is not None else zrows
-                ck(lib.rgn_lm_head_argmax_rows(_p(head), pn, d, B, V, d, pnew + 8 * B * k, 1, _p(z), V, _p(c["ws_h"]), ws_h, st),
-                   "rgn_lm_head_argmax_rows")
-                ck(lib.rgn_lm_pick_rows(_p(z), V, B, V, _p(seen), V, pen, smp, tmp, tk, tp, None if pu is None else pu + 4 * B * k,
-                                        pnew + 8 * B * k, 1, None if scores is None else _p(scores[k]), V, _p(pick_ws), ws_p, st),
-                   "rgn_lm_pick_rows")
+                ck(head_rows(_p(head), pn, d, B, V, d, pnew + 8 * B * k, 1, _p(z), V, _p(c["ws_h"]), ws_h, st), head_name)
+                for g0, Bg in pick_groups:                                        # rows never meet: one launch or several, every row keeps its bits
+                    ck(pick_rows(z.data_ptr() + 4 * V * g0, V, Bg, V, seen.data_ptr() + V * g0, V, pen, smp, tmp, tk, tp,
+                                 None if pu is None else pu + 4 * (B * k + g0), pnew + 8 * (B * k + g0), 1,
+                                 None if scores is None else scores[k].data_ptr() + 4 * V * g0, V, pick_ws.data_ptr() + ws_1 * g0, Bg * ws_1, st),
+                       pick_name)
         at = 0
         for b, n in enumerate(lens):                                              # rows prefill one after another on the existing kernels
             k = rows[b].numel() if rows is not None else 0
@@ -778,10 +811,10 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         ph, pqkv, pa, pff, pg, pws = (c[k].data_ptr() for k in ("h", "qkv", "a", "ff", "g", "ws_a"))
         # the linear layer of this adoption, picked once: a weight is the leading argument(s) of its entry, (W,) or (W8, scale)
         if self.weights == "fp8":
-            gemv, gemv_name = lib.rgn_lm_gemv_w8_rows, "rgn_lm_gemv_w8_rows"
+            gemv, gemv_name = (lib.rgn_lm_gemm_rows_w8, "rgn_lm_gemm_rows_w8") if wide else (lib.rgn_lm_gemv_w8_rows, "rgn_lm_gemv_w8_rows")
             wp = lambda w: (w.data_ptr(), ops._wscale(w).data_ptr())
         else:
-            gemv, gemv_name = lib.rgn_lm_gemv_bf16_rows, "rgn_lm_gemv_bf16_rows"
+            gemv, gemv_name = (lib.rgn_lm_gemm_rows_bf16, "rgn_lm_gemm_rows_bf16") if wide else (lib.rgn_lm_gemv_bf16_rows, "rgn_lm_gemv_bf16_rows")
             wp = lambda w: (w.data_ptr(),)
         ptok, pfin, pcos, psin = self.tok.data_ptr(), self.final_ln.data_ptr(), ntab[0].data_ptr(), ntab[1].data_ptr()
         Hq, Hkv, F, eps, scale, qc, ad = self.Hq, self.Hkv, self.F, self.eps, float(self.scale), self.qkv_cols, self.Hq * HEAD_DIM
@@ -791,13 +824,19 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         # that a step only calls ready objects.  Per layer: the launches before mRoPE, and those after it.
         rms, swiglu, append, attend = lib.rgn_rms_norm_rows, lib.rgn_swiglu_bf16, lib.rgn_lm_kv_append_bf16_rows, lib.rgn_lm_decode_attention_bf16_rows
         lp = []
+        ws_1a = ws_a // B                                                         # a row's attention partials: a multiple of 8 x 65 bytes
+        ints = ctypes.POINTER(ctypes.c_int)
+        at_row = lambda arr, g0: ctypes.cast(ctypes.byref(arr, 4 * g0), ints)     # the group's slice of a host int array
         for i, p in enumerate(self.layers):
             pc = c["cache"][i].data_ptr()
+            kv = [_bound(append, "rgn_lm_kv_append_bf16_rows", pqkv + 2 * qc * g0, qc, pc + 2 * cstride * g0, cstride, cap, at_row(row0, g0), Bg,
+                         Hq, Hkv, st) for g0, Bg in groups]
+            kv += [_bound(attend, "rgn_lm_decode_attention_bf16_rows", pqkv + 2 * qc * g0, qc, pc + 2 * cstride * g0, cstride, pa + 2 * ad * g0, ad,
+                          at_row(nn, g0), Bg, Hq, Hkv, scale, pws + ws_1a * g0, Bg * ws_1a, st) for g0, Bg in groups]
             lp.append(([_bound(rms, "rgn_rms_norm_rows", ph, d, p["ln1"].data_ptr(), pn, d, B, d, eps, st),
                         _bound(gemv, gemv_name, *wp(p["wqkv"]), pn, d, p["bqkv"].data_ptr(), None, 0, pqkv, qc, B, qc, d, st)],
-                       [_bound(append, "rgn_lm_kv_append_bf16_rows", pqkv, qc, pc, cstride, cap, row0, B, Hq, Hkv, st),
-                        _bound(attend, "rgn_lm_decode_attention_bf16_rows", pqkv, qc, pc, cstride, pa, ad, nn, B, Hq, Hkv, scale, pws, ws_a, st),
-                        _bound(gemv, gemv_name, *wp(p["wo"]), pa, ad, None, ph, d, ph, d, B, d, ad, st),
+                       kv +
+                       [_bound(gemv, gemv_name, *wp(p["wo"]), pa, ad, None, ph, d, ph, d, B, d, ad, st),
                         _bound(rms, "rgn_rms_norm_rows", ph, d, p["ln2"].data_ptr(), pn, d, B, d, eps, st),
                         _bound(gemv, gemv_name, *wp(p["wgu"]), pn, d, None, None, 0, pff, 2 * F, B, 2 * F, d, st),
                         _bound(swiglu, "rgn_swiglu_bf16", pff, 2 * F, pg, F, B, F, st),

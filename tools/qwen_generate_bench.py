@@ -44,6 +44,16 @@ B = 1..8 beside rgn_lm_pick, whose launch B = 1 dispatches to (the two arms diff
 
     python tools/qwen_generate_bench.py --batch --sampling --no-ab --out profiles/r27_qwen_batched_sampling_bench.json
     rocprofv3 --kernel-trace -d DIR -o kt -- python tools/qwen_generate_bench.py --batch --sampling --pick-only --no-ab
+
+`--batch --wide` times the MFMA row GEMM path: per length and weight format a default-kernel adoption (`max_batch=8`) at B = 1 and 8 beside a
+`batch_kernels="mfma", max_batch=32` adoption at B = 1, 8, 16 and 32, all alternating in the one process; with `--sampling` also the sampled
+"mfma" legs at B = 16 and 32.  Per leg ms per step, tokens per second, the streaming floor (weights + B KV bytes at 6.3 TB/s) and the step in
+units of the "fma" B = 8 step of the same run, which is what the wide path is judged against.  `--wide-kernels` (no model is built) writes
+the kernel table: rgn_lm_gemm_rows_bf16 / _w8 at B = 1, 8, 16, 32 on the four layer shapes beside rgn_lm_gemv_bf16 / _w8 and the B = 8
+`_rows` entries, in one process.
+
+    python tools/qwen_generate_bench.py --batch --wide --sampling --no-ab --out profiles/r30_qwen_wide_batch_bench.json
+    python tools/qwen_generate_bench.py --wide-kernels --no-ab --ab-out profiles/r30_qwen_wide_batch_kernel_stats.txt
 """
 import argparse
 import json
@@ -256,6 +266,124 @@ def batched(a, res):
         print(f"L{L}", json.dumps({k: v for k, v in r.items() if k.endswith("_table")}), flush=True)
 
 
+WIDE_LEGS = (("fma", 1), ("fma", 8), ("mfma", 1), ("mfma", 8), ("mfma", 16), ("mfma", 32))
+WIDE_SAMPLED = (("mfma", 16), ("mfma", 32))
+
+
+def wide(a, res):
+    """The `--batch --wide` legs: per length and weight format, a default-kernel ("fma", max_batch = 8) adoption at B = 1 and 8 and a
+    batch_kernels="mfma" adoption (max_batch = 32) at B = 1, 8, 16 and 32, alternating in one process; with --sampling also the sampled
+    "mfma" legs at B = 16 and 32.  ms per step = (t64 - t1) / 63 of the medians; the streaming floor is weights + B KV bytes at 6.3 TB/s."""
+    from transformers import Qwen2_5_VLForConditionalGeneration
+    from regione_amd import qwen_text_encoder as QT
+    cfg = full_size_config()
+    tc = cfg.text_config
+    torch.manual_seed(0)
+    with torch.device("cuda"):
+        mod = Qwen2_5_VLForConditionalGeneration(cfg).eval()
+    mod = mod.to(torch.bfloat16)
+    torch.cuda.empty_cache()
+    res["legs"], res["weights"] = [f"{k} B={B}" for k, B in WIDE_LEGS], "both"
+    g = torch.Generator().manual_seed(1)
+    for fmt in ("bf16", "fp8"):
+        kw = dict(sampling=True, batch_sampling=True) if a.sampling else {}
+        encs = {"fma": QT.HipQwen25VLTextEncoder(mod, weights=fmt, max_batch=8),
+                "mfma": QT.HipQwen25VLTextEncoder(mod, weights=fmt, max_batch=32, batch_kernels="mfma", **kw)}
+        for L in LENGTHS:
+            ids = torch.randint(0, 151000, (32, L), generator=g).cuda()
+            uni = torch.rand(NEW, 32, generator=g).cuda()
+            arms = {}
+            for n in (1, NEW):
+                for k, B in WIDE_LEGS:
+                    arms[f"{k}_b{B}_{n}"] = lambda k=k, n=n, B=B: encs[k].generate(ids[:B], max_new_tokens=n, eos_token_id=[])
+                if a.sampling:
+                    for k, B in WIDE_SAMPLED:
+                        arms[f"{k}_s20_b{B}_{n}"] = lambda k=k, n=n, B=B: encs[k].generate(
+                            ids[:B], max_new_tokens=n, eos_token_id=[], uniforms=uni[:n, :B].contiguous(), **SAMPLED["s20"])
+            ts = {k: [] for k in arms}
+            with torch.no_grad():
+                for fn in arms.values():
+                    fn()                                                         # warm
+                for _ in range(a.iters):
+                    for k, fn in arms.items():                                   # the legs alternate
+                        ts[k].append(_ms(fn))
+            r = {"L": L, "weights": fmt, **{k: _stat(v) for k, v in ts.items()}}
+            legs = [f"{k}_b{B}" for k, B in WIDE_LEGS] + ([f"{k}_s20_b{B}" for k, B in WIDE_SAMPLED] if a.sampling else [])
+            per = {leg: (r[f"{leg}_{NEW}"]["median_ms"] - r[f"{leg}_1"]["median_ms"]) / (NEW - 1) for leg in legs}
+            sb = step_bytes(tc, L + NEW // 2, fmt)
+            rows = []
+            for leg in legs:
+                B = int(leg.rsplit("_b", 1)[1])
+                by = sb["decoder_weights"] + sb["lm_head"] + B * sb["kv_cache"]
+                floor = by / HBM_BYTES_PER_S * 1e3
+                rows.append(dict(leg=leg, B=B, ms_per_step=per[leg], tokens_per_s=B * 1e3 / per[leg], step_bytes=by, streaming_floor_ms=floor,
+                                 over_its_streaming_floor=per[leg] / floor, fma_b8_steps=per[leg] / per["fma_b8"]))
+            r["table"] = rows
+            r["mfma_b16_under_two_fma_b8_steps"] = bool(per["mfma_b16"] < 2 * per["fma_b8"])
+            r["mfma_b32_under_four_fma_b8_steps"] = bool(per["mfma_b32"] < 4 * per["fma_b8"])
+            res[f"{fmt}_L{L}"] = r
+            print(f"{fmt} L{L}", json.dumps(rows), flush=True)
+        del encs
+        torch.cuda.empty_cache()
+
+
+def wide_kernels(a, res):
+    """The `--wide-kernels` table: achieved TB/s of rgn_lm_gemm_rows_bf16 / _w8 at B = 1, 8, 16, 32 on the four layer shapes beside
+    rgn_lm_gemv_bf16 / _w8 (one row) and the B = 8 `_rows` entries, in one process; every arm walks a ring of weight copies >= 1 GiB."""
+    from regione_amd import _lib, ops
+    lib = _lib.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    rows = []
+    for N, K in LAYER_SHAPES:
+        c16, c8 = max(2, -(-RING_BYTES // (2 * N * K))), max(2, -(-RING_BYTES // (N * K)))
+        g = torch.Generator(device="cuda").manual_seed(N + K)
+        W = torch.stack([(torch.randn(N, K, device="cuda", generator=g) * K ** -0.5).bfloat16() for _ in range(c16)])
+        W8 = torch.empty(c8, N, K, dtype=ops.FP8, device="cuda")
+        scales = []
+        for c in range(c8):
+            q = ops.quantize_w8(W[c % c16])
+            W8[c] = q
+            scales.append(q._rgn_scale)
+        X = torch.randn(32, K, device="cuda", generator=g).bfloat16()
+        Y = torch.empty(32, N, dtype=torch.bfloat16, device="cuda")
+        p16, p8, px, py = [W[c].data_ptr() for c in range(c16)], [(W8[c].data_ptr(), scales[c].data_ptr()) for c in range(c8)], X.data_ptr(), Y.data_ptr()
+        arms = {"gemv_bf16 B=1": (lambda: [lib.rgn_lm_gemv_bf16(p, px, None, None, py, N, K, st) for p in p16], c16, 2),
+                "gemv_w8 B=1": (lambda: [lib.rgn_lm_gemv_w8(p, s, px, None, None, py, N, K, st) for p, s in p8], c8, 1),
+                "gemv_bf16_rows B=8": (lambda: [lib.rgn_lm_gemv_bf16_rows(p, px, K, None, None, 0, py, N, 8, N, K, st) for p in p16], c16, 2),
+                "gemv_w8_rows B=8": (lambda: [lib.rgn_lm_gemv_w8_rows(p, s, px, K, None, None, 0, py, N, 8, N, K, st) for p, s in p8], c8, 1)}
+        for B in (1, 8, 16, 32):
+            arms[f"gemm_rows_bf16 B={B}"] = (lambda B=B: [lib.rgn_lm_gemm_rows_bf16(p, px, K, None, None, 0, py, N, B, N, K, st) for p in p16], c16, 2)
+            arms[f"gemm_rows_w8 B={B}"] = (lambda B=B: [lib.rgn_lm_gemm_rows_w8(p, s, px, K, None, None, 0, py, N, B, N, K, st) for p, s in p8], c8, 1)
+
+        def timed(fn, copies):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) * 1e3 / copies                            # us per call
+        for fn, c, _ in arms.values():
+            timed(fn, c)
+        t = {k: [] for k in arms}
+        for _ in range(7):                                                       # the arms alternate
+            for k, (fn, c, _) in arms.items():
+                t[k].append(timed(fn, c))
+        for k, (_, _, es) in arms.items():
+            med = statistics.median(t[k])
+            rows.append(dict(N=N, K=K, arm=k, us=med, min_us=min(t[k]), max_us=max(t[k]), tb_per_s=es * N * K / med / 1e6))
+        del W, W8
+        torch.cuda.empty_cache()
+    res["wide_kernels"] = rows
+    lines = ["# the MFMA row GEMM (rgn_lm_gemm_rows_*) beside the one-row GEMV and the B = 8 `_rows` entries on the four layer shapes: median us per",
+             f"# call of 7 alternating rounds, each arm over a ring of weight copies >= {RING_BYTES >> 20} MiB; TB/s = weight bytes / time.",
+             f"# csrc_sha16 {res['csrc_sha16']}  {res['device']}", f"{'N':>7} {'K':>6}  {'arm':<22} {'us':>9} {'[min':>9} {'max]':>9} {'TB/s':>6}"]
+    lines += [f"{r['N']:>7} {r['K']:>6}  {r['arm']:<22} {r['us']:>9.2f} {r['min_us']:>9.2f} {r['max_us']:>9.2f} {r['tb_per_s']:>6.2f}" for r in rows]
+    print("\n".join(lines), flush=True)
+    if a.ab_out:
+        with open(a.ab_out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def pick_rows_direct(res, rounds=20):
     """rgn_lm_pick_rows by itself at the real vocabulary, B = 1..8 rows of z = 4 randn with 300 seen ids each, beside rgn_lm_pick on one
     row: median us per launch of `rounds` event-timed launches per arm, the arms alternating.  Under rocprofv3 --kernel-trace the grid
@@ -362,12 +490,23 @@ def main():
     ap.add_argument("--sampling", action="store_true", help="adopt with sampling=True and time two sampled legs beside the greedy one")
     ap.add_argument("--batch", action="store_true", help="time a max_batch=8 adoption at B = 1, 2, 4, 8 beside a default one (bf16 and fp8)")
     ap.add_argument("--pick-only", action="store_true", help="with --batch --sampling: only the direct rgn_lm_pick_rows launches (for a kernel trace)")
+    ap.add_argument("--wide", action="store_true", help="with --batch: batch_kernels=\"mfma\" at B = 1, 8, 16, 32 beside the default kernels at "
+                    "B = 1, 8 (bf16 and fp8); with --sampling also the sampled legs at B = 16, 32")
+    ap.add_argument("--wide-kernels", action="store_true", help="only the kernel table of the MFMA row GEMM beside the GEMV entries (--ab-out)")
     a = ap.parse_args()
     from regione_amd import build
     sha = build.csrc_hash()
     res = {"device": torch.cuda.get_device_name(0), "csrc_sha16": sha, "iters": a.iters, "new_tokens": NEW,
            "stat": "median and min / max of warm, synchronised runs, the two sides alternating; ms per new token = (t64 - t1) / 63 of the medians",
            "model": "Qwen2.5-VL-7B language model, seeded init, text-only ids, no EOS", "hbm_bytes_per_s": HBM_BYTES_PER_S}
+    if a.wide_kernels or (a.batch and a.wide):
+        res["stat"] = ("median and min / max of warm, synchronised runs, every leg alternating; ms per step = (t64 - t1) / 63 of the medians; "
+                       "tokens per second = B / that")
+        wide_kernels(a, res) if a.wide_kernels else wide(a, res)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     if not a.no_ab and a.weights != "bf16":
         rows = gemv_w8_ab()
         res["gemv_w8_ab"] = rows
