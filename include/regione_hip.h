@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 122
+#define RGN_ABI_VERSION 123
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -581,6 +581,30 @@ int rgn_lm_kv_append_bf16_rows(const void* QKV, int ld, void* cache, size_t cach
  * cache rows >= n[b] are never read.  workspace_bytes >= B * rgn_lm_decode_attention_workspace_bytes(Hq, max_b n[b]). */
 int rgn_lm_decode_attention_bf16_rows(const void* Q, int ldq, const void* cache, size_t cache_stride, void* O, int ldo, const int* n_host, int B,
                                       int Hq, int Hkv, float scale, void* workspace, size_t workspace_bytes, void* stream);
+/* R query tokens of ONE sequence against ONE cache (a step that verifies R - 1 drafted tokens; HipQwen25VLTextEncoder(lookup=True)):
+ * query r (row r of Q [R, ldq]) sees cache rows [0, n0 + r); O [R, ldo].  1 <= R <= RGN_LM_MAX_BATCH, n0 >= 1, n0 + R - 1 <= 4096.  Row r
+ * is BIT FOR BIT rgn_lm_decode_attention_bf16(Q + r ldq, cache, ..., n = n0 + r): the same 64-key slices, per-thread fmaf chains, quad and
+ * wave folds and wave order; the merge runs over that row's own ceil((n0 + r) / 64) slices in slice order; a key at or past a row's length
+ * has score -inf, p = 0 and v = 0.  One block per (slice, KV head) loads its K and V once and walks the queries that own the slice, so the
+ * cache is read once, in two launches.  Cache rows >= n0 + R - 1 are never read.  ldq, ldo multiples of 8 and >= Hq 128; Q, cache, O,
+ * workspace 16-byte aligned; workspace_bytes >= R * rgn_lm_decode_attention_workspace_bytes(Hq, n0 + R - 1). */
+int rgn_lm_verify_attention_bf16(const void* Q, int ldq, const void* cache, void* O, int ldo, int n0, int R, int Hq, int Hkv, float scale,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+/* The end of such a step, ONE block: accept, then propose.  seq: int64 ids of one sequence in one run (prompt, then new tokens);
+ * seq[0, n) settled, seq[n - 1] was row 0 of the step, seq[n, n + R - 1) the drafts that were rows 1..R-1; head[r * head_stride] (int64)
+ * the argmax after row r.
+ *   accept   a = the largest a <= R - 1 with seq[n + i] == head[i] for all i < a (the first mismatch decides); seq[n + a] = head[a];
+ *            n' = n + a + 1.
+ *   propose  kcap = max(0, min(K, limit - n' - 1)), `limit` the end of the new-token run.  guess == NULL: the rule of transformers'
+ *            PromptLookupCandidateGenerator over seq[0, n'): n-gram sizes from min(max_ngram, n' - 1) down to 1; per size the LOWEST
+ *            window index idx whose window equals the trailing n-gram and whose continuation [idx + size, min(idx + size + kcap, n')) is
+ *            not empty; those k' ids go to seq[n', n' + k'); no match: k' = 0.  guess != NULL (int64 [guess_len], a guess of the whole
+ *            continuation, L the prompt length): draft i = guess[(n' - L) + i] while that index is < guess_len, at most kcap.
+ *   result   int64 [2 + R]: a, k', then the a + 1 accepted tokens.
+ * Nothing outside seq[n, limit) and result[0, 2 + R) is written; no atomics, plain vector stores.  1 <= R <= 32, 0 <= K <= 31,
+ * 1 <= max_ngram <= 8, 0 <= L <= n, n >= 1, n + R <= limit; pointers 8-byte aligned. */
+int rgn_lm_lookup_step(void* seq, int n, int R, const void* head, int head_stride, int limit, int K, int max_ngram, const void* guess,
+                       int guess_len, int L, void* result, void* stream);
 /* The WIDE step (opt-in; HipQwen25VLTextEncoder(batch_kernels="mfma")): the three weight-streaming layers for 1 <= B <=
  * RGN_LM_MAX_WIDE_BATCH rows as a skinny GEMM on v_mfma_f32_16x16x32_bf16 (csrc/decode.hip: lm_gemm_rows_kernel).  Every weight byte is loaded
  * from HBM once per call for all rows (16-byte non-temporal loads straight into the MFMA B operand); the rows of X are staged once per block

@@ -170,6 +170,11 @@ SIGNATURES = {
     "rgn_lm_kv_append_bf16_rows": [_c_void_p, _c_int, _c_void_p, C.c_size_t, _c_int, C.POINTER(_c_int), _c_int, _c_int, _c_int, _c_void_p],
     "rgn_lm_decode_attention_bf16_rows": [_c_void_p, _c_int, _c_void_p, C.c_size_t, _c_void_p, _c_int, C.POINTER(_c_int), _c_int, _c_int,
                                           _c_int, _c_float, _c_void_p, C.c_size_t, _c_void_p],
+    # drafts of one sequence verified in one step (lookup=True)
+    "rgn_lm_verify_attention_bf16": [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_void_p,
+                                     C.c_size_t, _c_void_p],
+    "rgn_lm_lookup_step": [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p,
+                           _c_void_p],
     # the wide step: 1 <= B <= 32 rows on the MFMA row GEMM (batch_kernels="mfma")
     "rgn_lm_gemm_rows_bf16": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p],
     "rgn_lm_gemm_rows_w8": [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int,

@@ -225,7 +225,10 @@ def hip_qwen_text_encoder_for(host, dev):
     ValueError naming the attribute that is wrong or missing, with nothing adopted or cached.
     `pipe._regione_hip_text_batch_kernels = "mfma"` before the first call adopts with `batch_kernels="mfma"` (every decode step on the MFMA
     row GEMM); with it `_regione_hip_text_batch` is accepted in 1..32.  Absent, it is "fma" and every message is as above; another value
-    raises ValueError naming the two, with nothing adopted or cached."""
+    raises ValueError naming the two, with nothing adopted or cached.
+    `pipe._regione_hip_text_lookup = True` before the first call adopts with `lookup=True` (generate takes prompt_lookup_num_tokens,
+    max_matching_ngram_size and draft_tokens and verifies the drafts in one step); absent, it is False; a value that is not a bool raises
+    ValueError, with nothing adopted or cached."""
     if _memo(host, "_regione_hip_text") is False:
         return None
     cached = _memo(host, "_regione_hip_qwen_text")
@@ -251,6 +254,9 @@ def hip_qwen_text_encoder_for(host, dev):
         raise ValueError("pipe._regione_hip_text_batch_sampling = True needs pipe._regione_hip_text_sampling = True")
     if rows_pick and batch < 2:
         raise ValueError(f"pipe._regione_hip_text_batch_sampling = True needs pipe._regione_hip_text_batch = N with N in 2..{top}")
+    lookup = host.__dict__.get("_regione_hip_text_lookup", False)
+    if not isinstance(lookup, bool):
+        raise ValueError(f"pipe._regione_hip_text_lookup = {lookup!r}: True and False are accepted")
     mod = getattr(host, "text_encoder", None)
     enc = None
     if type(mod).__name__ == "Qwen2_5_VLForConditionalGeneration" and getattr(mod, "config", None) is not None:
@@ -262,7 +268,8 @@ def hip_qwen_text_encoder_for(host, dev):
                              make=lambda: QT.HipQwen25VLTextEncoder(mod, dev, weights=fmt, **({"sampling": True} if sampling else {}),
                                                                     **({"max_batch": batch} if batch > 1 else {}),
                                                                     **({"batch_sampling": True} if rows_pick else {}),
-                                                                    **({"batch_kernels": "mfma"} if kernels == "mfma" else {})))
+                                                                    **({"batch_kernels": "mfma"} if kernels == "mfma" else {}),
+                                                                    **({"lookup": True} if lookup else {})))
         if enc is not None and _memo(host, "_regione_hip_vision") is not False:
             from .. import qwen_vision as QV
             tower = _adopt_or_keep("vision tower", QV.vision_refusal(mod.config), lambda: QV.HipQwen25VLVisionTower(mod, dev), stacklevel=3)

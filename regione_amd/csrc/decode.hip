@@ -26,6 +26,11 @@
 //   lm_gemm_rows_kernel         the three products as a skinny GEMM on v_mfma_f32_16x16x32_bf16: weights straight from HBM into the B operand,
 //                               the rows of x in LDS as bf16, K split over the four waves and folded in wave order; row b depends on row b
 //                               alone, but its sums are not the `_rows` kernels' sums in the last bits (described at the kernel)
+// and, opt-in (lookup=True), a step that carries drafted tokens of ONE sequence as extra rows and keeps the prefix greedy search gives:
+//   lm_verify_attention_kernel  R <= 8 queries against one cache, query r over n0 + r rows: K and V of a slice loaded once for all of
+//                               them, row r bit-identical to lm_decode_attention_kernel at n0 + r
+//   lm_lookup_step_kernel       one block after the head: accepts the drafts the argmaxes confirm, writes the token after them and
+//                               proposes the next drafts (an n-gram match in the sequence so far, or a caller's guess)
 // No atomics; every reduction has a fixed order (lanes: the butterfly of wave_sum; k, keys and slices: ascending), so a repeated call is
 // bit-identical.
 #include <math.h>
@@ -535,6 +540,207 @@ __global__ __launch_bounds__(128) void lm_decode_merge_rows_kernel(const float* 
                                                                    uint16_t* __restrict__ O, int ldo) {
     const int b = blockIdx.y;
     decode_merge_head(part + b * part_stride, (nb.v[b] + DEC_SLICE - 1) / DEC_SLICE, O + (size_t)b * ldo);
+}
+
+// ---- R queries of ONE sequence against ONE cache: a step that verifies R - 1 drafted tokens -------------------------------------------
+// Query r (row r of Q) sees cache rows [0, n0 + r).  Block = (slice of 64 cache rows, KV head) as in decode_attention_block, but K and V
+// of the slice are loaded ONCE, masked by the LONGEST row (n0 + R - 1), and stay in registers (16 + 16 VGPRs) while the block walks the
+// queries that own the slice: slice s exists for row r iff 64 s < n0 + r, so the rows from max(0, 64 s + 1 - n0) on.  Per query the
+// arithmetic is decode_attention_block's at n = n0 + r, statement for statement - the same fmaf chain per (key, quarter), the same quad
+// and wave folds, the same wave order in P V - so row r has the bits of the one-row kernel.  What differs is how a key in
+// [n0 + r, n0 + R - 1) is kept out: it IS in registers here, so its score is replaced by -inf (as the one-row kernel does for a key it
+// did not load) and its V is replaced by 0 in the product (the one-row kernel multiplies p = 0 by v = 0; p = 0 times a loaded v would
+// differ in the sign of a zero sum, and in more for a non-finite v).  The LDS is reused from query to query: every array is last read
+// before a barrier that precedes its next write (ql: scores phase / top of the next query; sl: P V / after the next query's first
+// barrier; ol: the fold of wave 0 / four barriers later).  Partials of row r go to part + r part_stride, indexed by that row's own
+// slice count, and lm_decode_merge_rows_kernel folds them per row.
+__global__ __launch_bounds__(256) void lm_verify_attention_kernel(const uint16_t* __restrict__ Q, int ldq, const uint16_t* __restrict__ cache,
+                                                                  int n0, int R, int Hq, int Hkv, float scale, float* __restrict__ part,
+                                                                  size_t part_stride) {
+    __shared__ __attribute__((aligned(16))) float ql[DEC_MAX_GROUP * 128];
+    __shared__ float sl[DEC_MAX_GROUP * DEC_SLICE];                              // scores, then p
+    __shared__ __attribute__((aligned(8))) float ol[3 * DEC_MAX_GROUP * 128];    // the P V sums of waves 1..3
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, slice = blockIdx.x, hk = blockIdx.y, G = Hq / Hkv;
+    const size_t width = (size_t)2 * Hkv * 128;
+    const int row0 = slice * DEC_SLICE, nmax = n0 + R - 1;
+    const int kj = tid >> 2, kc = tid & 3;
+    uint4 kv[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) kv[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (row0 + kj < nmax) {
+        const uint16_t* kr = cache + (size_t)(row0 + kj) * width + (size_t)hk * 128 + kc * 32;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) kv[i] = *(const uint4*)(kr + i * 8);
+    }
+    uint32_t vv[16];
+    const uint16_t* vr = cache + (size_t)(row0 + wave * 16) * width + (size_t)(Hkv + hk) * 128 + 2 * lane;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) vv[k] = row0 + wave * 16 + k < nmax ? *(const uint32_t*)(vr + (size_t)k * width) : 0u;
+    const int rfirst = row0 + 1 - n0 > 0 ? row0 + 1 - n0 : 0;                    // < R: the grid has ceil(nmax / 64) slices
+#pragma unroll 1
+    for (int r = rfirst; r < R; ++r) {
+        const int n = n0 + r, nslices = (n + DEC_SLICE - 1) / DEC_SLICE;
+        const bool kok = row0 + kj < n;
+        const uint16_t* q = Q + (size_t)r * ldq;
+        for (int i = tid; i < G * 128; i += 256) ql[i] = bf2f(q[(size_t)hk * G * 128 + i]);
+        __syncthreads();
+        float s[DEC_MAX_GROUP];
+#pragma unroll
+        for (int g = 0; g < DEC_MAX_GROUP; ++g) s[g] = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t w[4] = {kv[i].x, kv[i].y, kv[i].z, kv[i].w};
+            float kf[8];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { kf[2 * e] = __uint_as_float(w[e] << 16); kf[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u); }
+#pragma unroll
+            for (int g = 0; g < DEC_MAX_GROUP; ++g) {
+                if (g < G) {
+                    const float* qp = ql + g * 128 + kc * 32 + i * 8;
+                    const float4 qa = *(const float4*)qp, qb = *(const float4*)(qp + 4);
+                    float a = s[g];
+                    a = fmaf(qa.x, kf[0], a); a = fmaf(qa.y, kf[1], a); a = fmaf(qa.z, kf[2], a); a = fmaf(qa.w, kf[3], a);
+                    a = fmaf(qb.x, kf[4], a); a = fmaf(qb.y, kf[5], a); a = fmaf(qb.z, kf[6], a); a = fmaf(qb.w, kf[7], a);
+                    s[g] = a;
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < DEC_MAX_GROUP; ++g) {
+            if (g < G) {
+                float a = s[g];
+                a += __shfl_xor(a, 1, 64);
+                a += __shfl_xor(a, 2, 64);
+                if (kc == 0) sl[g * DEC_SLICE + kj] = kok ? a * scale : -INFINITY;
+            }
+        }
+        __syncthreads();
+        float m[DEC_MAX_GROUP], l[DEC_MAX_GROUP], p[DEC_MAX_GROUP];
+#pragma unroll
+        for (int g = 0; g < DEC_MAX_GROUP; ++g) {
+            if (g < G) {
+                const float t = sl[g * DEC_SLICE + lane];
+                float mx = t;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+                p[g] = expf(t - mx);                                             // key row0 is valid for this row: mx is finite
+                m[g] = mx;
+                l[g] = wave_sum(p[g]);
+            }
+        }
+        __syncthreads();                                                         // every wave has read the scores
+        if (wave == 0) {
+#pragma unroll
+            for (int g = 0; g < DEC_MAX_GROUP; ++g)
+                if (g < G) sl[g * DEC_SLICE + lane] = p[g];
+        }
+        __syncthreads();
+        float o0[DEC_MAX_GROUP], o1[DEC_MAX_GROUP];
+#pragma unroll
+        for (int g = 0; g < DEC_MAX_GROUP; ++g) o0[g] = o1[g] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const uint32_t vk = row0 + wave * 16 + k < n ? vv[k] : 0u;           // a key this row does not see: v = 0, as if never loaded
+            const float v0 = __uint_as_float(vk << 16), v1 = __uint_as_float(vk & 0xffff0000u);
+#pragma unroll
+            for (int g = 0; g < DEC_MAX_GROUP; ++g) {
+                if (g < G) {
+                    const float pk = sl[g * DEC_SLICE + wave * 16 + k];
+                    o0[g] = fmaf(pk, v0, o0[g]);
+                    o1[g] = fmaf(pk, v1, o1[g]);
+                }
+            }
+        }
+        if (wave > 0) {
+#pragma unroll
+            for (int g = 0; g < DEC_MAX_GROUP; ++g)
+                if (g < G) *(float2*)(ol + ((wave - 1) * DEC_MAX_GROUP + g) * 128 + 2 * lane) = make_float2(o0[g], o1[g]);
+        }
+        __syncthreads();
+        if (wave == 0) {
+            float* prow = part + (size_t)r * part_stride;
+#pragma unroll
+            for (int g = 0; g < DEC_MAX_GROUP; ++g) {
+                if (g < G) {
+                    float a0 = o0[g], a1 = o1[g];
+#pragma unroll
+                    for (int w = 0; w < 3; ++w) {                                // wave order
+                        const float2 t = *(const float2*)(ol + (w * DEC_MAX_GROUP + g) * 128 + 2 * lane);
+                        a0 += t.x;
+                        a1 += t.y;
+                    }
+                    float* pr = prow + ((size_t)(hk * G + g) * nslices + slice) * DEC_PART;
+                    if (lane == 0) { pr[0] = m[g]; pr[1] = l[g]; }
+                    *(float2*)(pr + 2 + 2 * lane) = make_float2(a0, a1);
+                }
+            }
+        }
+    }
+}
+
+// ---- accept the verified drafts and propose the next ones: ONE block after the head of a verify step -----------------------------------
+// seq is one run of int64 ids (prompt, then new tokens); seq[0, n) is settled, seq[n - 1] was row 0 of the step, seq[n, n + R - 1) are the
+// drafts that were rows 1..R-1 and head[r hs] is the argmax after row r.
+//   accept   a = the number of leading drafts that equal the heads before them (the FIRST mismatch ends the run); seq[n + a] = head[a],
+//            the token the model gives after the last accepted row; n' = n + a + 1.  Every thread walks the <= 31 pairs itself.
+//   propose  kcap = max(0, min(K, limit - n' - 1)) drafts at most.  With `guess`: draft i is guess[(n' - L) + i] while that index is inside
+//            the guess.  Without: transformers' PromptLookupCandidateGenerator over seq[0, n') - n-gram sizes from min(max_ngram, n' - 1)
+//            down to 1, per size the LOWEST window index idx whose window equals the trailing n-gram and whose continuation
+//            [idx + size, min(idx + size + kcap, n')) is not empty (which excludes the trailing n-gram itself); thread t tries windows
+//            t, t + 256, ... in ascending order, the block takes the minimum through the wave butterfly and four LDS slots.
+//   result   int64 [2 + R]: a, k', then the a + 1 accepted tokens.  Plain stores, no atomics; the drafts go to seq[n', n' + k').
+constexpr int LOOKUP_T = 256, LOOKUP_MAX_R = RGN_LM_MAX_WIDE_BATCH, LOOKUP_MAX_NGRAM = 8, LOOKUP_NONE = 0x7fffffff;
+
+__global__ __launch_bounds__(LOOKUP_T) void lm_lookup_step_kernel(int64_t* __restrict__ seq, int n, int R, const int64_t* __restrict__ head,
+                                                                  int hs, int limit, int K, int max_ngram, const int64_t* __restrict__ guess,
+                                                                  int guess_len, int L, int64_t* __restrict__ result) {
+    __shared__ int best[LOOKUP_T / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int a = 0;
+    while (a < R - 1 && seq[n + a] == head[(size_t)a * hs]) ++a;
+    const int n1 = n + a + 1;
+    __syncthreads();                                                             // every thread has read the drafts
+    if (tid <= a) result[2 + tid] = head[(size_t)tid * hs];
+    if (tid == 0) seq[n + a] = head[(size_t)a * hs];
+    __syncthreads();                                                             // the bonus token is in seq for the whole block
+    int kcap = limit - n1 - 1 < K ? limit - n1 - 1 : K;
+    kcap = kcap > 0 ? kcap : 0;
+    int kn = 0;
+    if (guess) {
+        const int at = n1 - L;                                                   // the new-token position of draft 0
+        kn = guess_len - at < kcap ? guess_len - at : kcap;
+        kn = kn > 0 ? kn : 0;
+        if (tid < kn) seq[n1 + tid] = guess[at + tid];
+    } else if (kcap > 0) {
+        for (int size = max_ngram < n1 - 1 ? max_ngram : n1 - 1; size >= 1; --size) {
+            int64_t tail[LOOKUP_MAX_NGRAM];
+#pragma unroll
+            for (int j = 0; j < LOOKUP_MAX_NGRAM; ++j) tail[j] = j < size ? seq[n1 - size + j] : 0;
+            int mine = LOOKUP_NONE;
+            for (int idx = tid; idx + size < n1; idx += LOOKUP_T) {              // idx + size < n1: the continuation is not empty
+                bool eq = true;
+#pragma unroll
+                for (int j = 0; j < LOOKUP_MAX_NGRAM; ++j)
+                    if (j < size) eq = eq && seq[idx + j] == tail[j];
+                if (eq) { mine = idx; break; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(mine, o, 64); mine = t < mine ? t : mine; }
+            if (lane == 0) best[wave] = mine;
+            __syncthreads();
+            int idx = best[0];
+#pragma unroll
+            for (int w = 1; w < LOOKUP_T / 64; ++w) idx = best[w] < idx ? best[w] : idx;
+            __syncthreads();                                                     // best[] is free for the next size
+            if (idx != LOOKUP_NONE) {                                                // the same for every thread
+                const int start = idx + size, end = start + kcap < n1 ? start + kcap : n1;
+                kn = end - start;
+                if (tid < kn) seq[n1 + tid] = seq[start + tid];                  // source below n1, destination from n1 on
+                break;
+            }
+        }
+    }
+    if (tid == 0) { result[0] = a; result[1] = kn; }
 }
 
 // ---- repetition penalty and sampling: the pick between lm_head and the next embedding -------------------------------------------------
@@ -1219,6 +1425,44 @@ int rgn_lm_decode_attention_bf16_rows(const void* Q, int ldq, const void* cache,
                                       int Hq, int Hkv, float scale, void* workspace, size_t workspace_bytes, void* stream) {
     return decode_attention("lm_decode_attention_rows", Q, ldq, cache, cache_stride, O, ldo, n_host, B, Hq, Hkv, scale, workspace,
                             workspace_bytes, stream);
+}
+
+int rgn_lm_verify_attention_bf16(const void* Q, int ldq, const void* cache, void* O, int ldo, int n0, int R, int Hq, int Hkv, float scale,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "lm_verify_attention";
+    if (!Q || !cache || !O || !workspace || Hkv < 1 || Hq < Hkv || Hq > 1024 || !(scale > 0.f) || !(scale < INFINITY))
+        return bad(who, "bad argument (Q, cache, O, workspace non-null; 1 <= Hkv <= Hq <= 1024; 0 < scale < inf)");
+    if (Hq % Hkv || Hq / Hkv > DEC_MAX_GROUP) return bad(who, "Hq % Hkv != 0 or Hq / Hkv > 8");
+    if (R < 1 || R > RGN_LM_MAX_BATCH) return bad(who, "R outside [1, 8]");
+    if (n0 < 1 || n0 > DEC_MAX_N - (R - 1)) return bad(who, "rows [n0, n0 + R) must lie in [1, 4096]: query r sees n0 + r cache rows");
+    if (ldq % 8 || ldo % 8 || ldq < Hq * 128 || ldo < Hq * 128) return bad(who, "ldq and ldo must be multiples of 8 and >= Hq 128");
+    if (!dal16(Q) || !dal16(cache) || !dal16(O) || !dal16(workspace)) return bad(who, "Q, cache, O and workspace must be 16-byte aligned");
+    const int nmax = n0 + R - 1, ns = (nmax + DEC_SLICE - 1) / DEC_SLICE;
+    const size_t one = rgn_lm_decode_attention_workspace_bytes(Hq, nmax);
+    if (workspace_bytes < (size_t)R * one) return bad(who, "workspace smaller than R rgn_lm_decode_attention_workspace_bytes(Hq, n0 + R - 1)");
+    LmRows nb{};
+    for (int r = 0; r < R; ++r) nb.v[r] = n0 + r;
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(lm_verify_attention_kernel, dim3(ns, Hkv), dim3(256), 0, st, (const uint16_t*)Q, ldq, (const uint16_t*)cache, n0, R, Hq, Hkv,
+                       scale, (float*)workspace, one / sizeof(float));
+    hipLaunchKernelGGL(lm_decode_merge_rows_kernel, dim3(Hq, R), dim3(128), 0, st, (const float*)workspace, one / sizeof(float), nb, (uint16_t*)O,
+                       ldo);
+    return check_launch(who);
+}
+
+int rgn_lm_lookup_step(void* seq, int n, int R, const void* head, int head_stride, int limit, int K, int max_ngram, const void* guess,
+                       int guess_len, int L, void* result, void* stream) {
+    const char* who = "lm_lookup_step";
+    if (!seq || !head || !result || head_stride < 1) return bad(who, "bad argument (seq, head, result non-null; head_stride >= 1)");
+    if (R < 1 || R > LOOKUP_MAX_R) return bad(who, "R outside [1, 32]");
+    if (K < 0 || K > LOOKUP_MAX_R - 1) return bad(who, "K outside [0, 31]");
+    if (max_ngram < 1 || max_ngram > LOOKUP_MAX_NGRAM) return bad(who, "max_ngram outside [1, 8]");
+    if (n < 1 || L < 0 || L > n || limit < n + R) return bad(who, "0 <= L <= n, n >= 1 and n + R <= limit: the step's R tokens end inside the run");
+    if (guess ? guess_len < 0 : guess_len != 0) return bad(who, "guess_len >= 0 with a guess, 0 without");
+    if (((uintptr_t)seq | (uintptr_t)head | (uintptr_t)result | (uintptr_t)guess) & 7u) return bad(who, "seq, head, guess and result must be 8-byte aligned");
+    hipLaunchKernelGGL(lm_lookup_step_kernel, dim3(1), dim3(LOOKUP_T), 0, (hipStream_t)stream, (int64_t*)seq, n, R, (const int64_t*)head, head_stride,
+                       limit, K, max_ngram, (const int64_t*)guess, guess_len, L, (int64_t*)result);
+    return check_launch("lm_lookup_step_kernel");
 }
 
 int rgn_lm_seen_mark(const void* ids, int n, void* seen, int V, void* stream) {

@@ -73,6 +73,22 @@ the sums differ in their last bits (another summation order), so tokens agree wh
 the KV layout, EOS / pad assembly and `sync_every` are untouched.  KV memory: 28 layers x cap x 2 x 4 x 128 bf16 = 235 MB per row at
 cap = 4096, so 7.5 GB at 32 rows.  Not measured: real checkpoints.
 
+`lookup=True` (opt-in; the default refuses `prompt_lookup_num_tokens` as before, word for word) lets a one-sequence greedy `generate`
+take transformers' `prompt_lookup_num_tokens=K` and `max_matching_ngram_size` (default 2) and the extension `draft_tokens=` (a 1-D int64
+guess of the whole continuation, new token 0 first; alone it takes the family's largest K).  The speculative loop (`_generate_lookup`;
+the plain loop is untouched and runs when neither argument is given) keeps prompt and new ids in ONE device run and carries up to K
+drafted tokens as extra rows of a step: the `_rows` / `_wide` entries at B = R = drafts + 1 (row b of those is bit for bit the one-row
+call), rgn_mrope_bf16 over R consecutive table rows, ONE rgn_lm_kv_append_bf16 of R rows, and rgn_lm_verify_attention_bf16 - R <= 8
+queries against the one cache, query r over n + r rows, K and V of a 64-key slice loaded once for all of them, row r bit for bit
+rgn_lm_decode_attention_bf16 at n + r (groups of 8 queries under "mfma").  rgn_lm_lookup_step, one block after the head, accepts the
+drafts that equal the argmax before them (the first mismatch ends the run), writes the token after them and drafts the next step's
+rows: the rule of transformers' PromptLookupCandidateGenerator over the run so far (n-gram sizes from the largest down, the lowest
+matching window with a non-empty continuation), or the caller's guess; never past max_new_tokens.  The host reads that kernel's small
+result once per step (the accepted tokens: its look for EOS).  Every kept token and its fp32 logits row are bit for bit what the plain
+loop of the SAME adoption gives; rejected cache rows and logits rows are overwritten by later steps.  K <= 7 under "fma", <= 31 under
+"mfma"; B > 1, sampling, a penalty and output_scores are refused by name.  `last_lookup_stats` = steps, drafted, accepted, tokens.
+Not measured: the acceptance rate on a real checkpoint (a seeded model's rate means nothing).
+
 There is no eager fallback inside: what the kernels do not implement raises RegionEHipError before any launch, and the adapter
 (regione_amd.adapters, components.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
 only; every call returns freshly allocated outputs.
@@ -217,6 +233,34 @@ CONFIG_OFF = dict(min_p=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0,
                   bad_words_ids=None, force_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, sequence_bias=None,
                   min_new_tokens=0, min_length=0, guidance_scale=1.0, exponential_decay_length_penalty=None, renormalize_logits=False,
                   constraints=None)
+
+
+# what a `lookup=True` adoption's generate takes besides: transformers' two prompt-lookup arguments and a caller's guess of the continuation
+LOOKUP_ARGS = ("prompt_lookup_num_tokens", "max_matching_ngram_size", "draft_tokens")
+MAX_NGRAM = 8                                                                    # rgn_lm_lookup_step: 1 <= max_ngram <= 8
+
+
+def lookup_plan(what, look, wide):
+    """(K, max_ngram, guess) of one speculative generate from its LOOKUP_ARGS, every refusal by name: K drafts at most per step (1..7 on
+    the "fma" row kernels, 1..31 on "mfma": a step carries K + 1 rows), the largest n-gram tried (transformers' default 2), and the
+    guess (a 1-D int64 tensor) or None.  `draft_tokens` alone takes the family's largest K."""
+    top = (MAX_WIDE_BATCH if wide else MAX_BATCH) - 1
+    K, ngram, guess = look.get("prompt_lookup_num_tokens"), look.get("max_matching_ngram_size"), look.get("draft_tokens")
+    if K is None and guess is None:
+        _refuse(what, "max_matching_ngram_size without prompt_lookup_num_tokens (it sizes the n-grams of the prompt lookup)")
+    if K is None:
+        K = top
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= top:
+        _refuse(what, f"prompt_lookup_num_tokens={K!r} (an int in [1, {top}] under batch_kernels=\"{'mfma' if wide else 'fma'}\": a step "
+                      f"verifies K drafts as K + 1 rows)")
+    if ngram is None:
+        ngram = 2
+    if isinstance(ngram, bool) or not isinstance(ngram, int) or not 1 <= ngram <= MAX_NGRAM:
+        _refuse(what, f"max_matching_ngram_size={ngram!r} (an int in [1, {MAX_NGRAM}])")
+    if guess is not None:
+        if not isinstance(guess, torch.Tensor) or guess.dtype != torch.int64 or guess.dim() != 1 or guess.numel() < 1:
+            _refuse(what, "draft_tokens must be a 1-D int64 tensor with at least one id (a guess of the continuation, new token 0 first)")
+    return K, ngram, guess
 
 
 class PickPlan:
@@ -365,13 +409,15 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
     what = "HipQwen25VLTextEncoder"
 
     def __init__(self, module_or_state_dict, device=None, config=None, max_length: int = 4096, vision=None, weights: str = "bf16",
-                 sampling: bool = False, max_batch: int = 1, batch_sampling: bool = False, batch_kernels: str = "fma"):
+                 sampling: bool = False, max_batch: int = 1, batch_sampling: bool = False, batch_kernels: str = "fma", lookup: bool = False):
         if weights not in WEIGHT_FORMATS:
             _refuse(self.what, f"weights={weights!r} (the layer matrices are kept as one of {WEIGHT_FORMATS})")
         if not isinstance(sampling, bool):
             _refuse(self.what, f"sampling={sampling!r} (True or False)")
         if not isinstance(batch_kernels, str) or batch_kernels not in BATCH_KERNELS:
             _refuse(self.what, f"batch_kernels={batch_kernels!r} (one of {BATCH_KERNELS}: the vector-ALU row kernels, or the MFMA row GEMM)")
+        if not isinstance(lookup, bool):
+            _refuse(self.what, f"lookup={lookup!r} (True or False)")
         wide = batch_kernels == "mfma"
         if isinstance(max_batch, bool) or not isinstance(max_batch, int) or not 1 <= max_batch <= (MAX_WIDE_BATCH if wide else MAX_BATCH):
             if wide:
@@ -385,7 +431,7 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         if batch_sampling and max_batch == 1:
             _refuse(self.what, "batch_sampling=True with max_batch=1 (it needs max_batch > 1: one row takes the one-sequence pick)")
         self.weights, self.sampling, self.max_batch, self.batch_sampling = weights, sampling, max_batch, batch_sampling
-        self.batch_kernels = batch_kernels
+        self.batch_kernels, self.lookup, self.last_lookup_stats = batch_kernels, lookup, None
         sd, cfg, dev, mod = _source(module_or_state_dict, config, device, self.what)
         self.vision = vision                               # a HipQwen25VLVisionTower, or None: the adopted module's eager tower
         why = qwen25vl_refusal(cfg)
@@ -433,6 +479,7 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         self._lm_head_src = None if self._tied else sd.get("lm_head.weight")      # a reference, not a copy
         self.lm_head = None
         self.kv = _Buffers(dev)
+        self.kv_lookup = _Buffers(dev)                                              # the speculative loop's own set (lookup=True)
 
     # ---- host-side preparation (no kernel) -----------------------------------------------------------------------------------------
     def position_ids_for(self, input_ids, attention_mask=None, image_grid_thw=None, position_ids=None, mm_token_type_ids=None,
@@ -723,8 +770,16 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         so with a generator a row's stream of uniforms depends on B and on the row's place in the batch.  For given `uniforms`, row b is
         bit for bit the B = 1 call on its unpadded prompt with uniforms[:, b].  The byte map of the repetition penalty is [B, V], zeroed
         once; row b sees that row's valid prompt ids and its own new tokens, the left padding is NOT marked (transformers gathers at the
-        pad positions too).  Finished rows keep being picked; scores past a row's EOS are not meaningful."""
+        pad positions too).  Finished rows keep being picked; scores past a row's EOS are not meaningful.
+        Under `lookup=True` one sequence also takes prompt_lookup_num_tokens=, max_matching_ngram_size= and draft_tokens=: with one of
+        them the call is `_generate_lookup` (drafted tokens verified as extra rows of a step; the same sequences and logits, bit for bit),
+        without them it is this loop unchanged."""
         plan = None
+        look = {k: kw.pop(k) for k in LOOKUP_ARGS if k in kw} if self.lookup else {}   # without lookup=True they are refused as before
+        self.last_lookup_stats = None                                             # of the last generate: None after a plain one
+        if any(v is not None for v in look.values()):
+            return self._generate_lookup(look, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, do_sample,
+                                         return_dict_in_generate, output_logits, mm_token_type_ids, image_embeds, position_ids, sync_every, kw)
         pad_arg = kw.pop("pad_token_id", None) if self.max_batch > 1 else None    # a default adoption refuses the argument as before
         if self.sampling:                                                         # opt-in: without it every refusal below is what it was
             mine = {k: kw.pop(k) for k in PICK_ARGS + PICK_EXTRA if k in kw}
@@ -872,3 +927,140 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             return seq
         return QwenGenerateOutput(seq, tuple(logits[k] for k in range(n_new)) if logits is not None else None,
                                   tuple(scores[k] for k in range(n_new)) if scores is not None else None)
+
+    # ---- greedy generate with drafted tokens verified in one step (lookup=True; csrc/decode.hip: lm_verify_attention_kernel) ----------
+    def _generate_lookup(self, look, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, do_sample,
+                         return_dict_in_generate, output_logits, mm_token_type_ids, image_embeds, position_ids, sync_every, kw):
+        """Greedy `generate` for ONE sequence whose steps carry drafted tokens: the sequences and fp32 `logits` of the plain loop of the
+        same adoption, bit for bit, in fewer steps when drafts are accepted.  A step at settled length n with k' drafts runs R = k' + 1
+        rows - the last settled token and the drafts, contiguous in the device id run `seq` (prompt, then new tokens) - through the
+        entries of the batched loop at B = R (row b of those has the bits of the one-row call), with two differences: rgn_mrope_bf16
+        over R consecutive table rows, and ONE rgn_lm_kv_append_bf16 of R rows at cache row n - 1 followed by
+        rgn_lm_verify_attention_bf16 (query r over n + r cache rows; groups of 8 queries under "mfma").  The head writes R argmaxes (and,
+        with output_logits, the fp32 rows straight into logits[k : k + R]); rgn_lm_lookup_step keeps the drafts the argmaxes confirm,
+        writes the token after them and drafts for the next step (`prompt_lookup_num_tokens`: transformers' n-gram lookup in the
+        sequence so far; `draft_tokens`: the caller's guess); the host reads its (a, k', tokens) buffer, the one copy of a step, and
+        looks for EOS there.  Cache rows and logits rows of rejected drafts are overwritten by later steps.  The prefill's pick is the
+        first such step with R = 1.  `last_lookup_stats`: steps (decode steps after the prefill), drafted and accepted (drafts over
+        those steps) and tokens (new tokens decoded before the EOS cut: 1 + steps + accepted)."""
+        wide = self.batch_kernels == "mfma"
+        pad_arg = kw.pop("pad_token_id", None) if self.max_batch > 1 else None
+        if self.sampling:
+            mine = {k: kw.pop(k) for k in PICK_ARGS + PICK_EXTRA if k in kw}
+            eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, False, sync_every, kw)
+            if input_ids.shape[0] == 1 and not self._pick_plan(do_sample, max_new_tokens, mine, 1).greedy_as_before:
+                _refuse(self.what, "prompt_lookup_num_tokens / draft_tokens with sampling, a repetition penalty or output_scores: drafts are "
+                                   "verified against greedy search only")
+        else:
+            eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
+        if input_ids.shape[0] != 1:
+            _refuse(self.what, f"prompt_lookup_num_tokens / draft_tokens with B = {input_ids.shape[0]}: drafts are verified for one sequence (B == 1)")
+        K, max_ngram, guess = lookup_plan(self.what, look, wide)
+        ids_cpu, lens, tables, pos = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids,
+                                                   image_embeds, {}, left=True)
+        L, T = ids_cpu.shape[1], int(max_new_tokens)
+        if lens[0] != L:
+            _refuse(self.what, "prompt_lookup_num_tokens / draft_tokens with a padded row: the id run of the lookup is the unpadded prompt")
+        pad = resolve_pad_token_id(pad_arg, getattr(self.module, "generation_config", None), eos)
+        new_tables = mrope_tables(self.inv_freq, decode_position_ids(pos, T), self.mrope_section)        # [2, 1, T, 128]
+        head = self._adopt_lm_head()                                               # may refuse: nothing has been launched yet
+        emb = self._image_embeds(pixel_values, image_grid_thw, image_embeds)
+        idx = None
+        if emb is not None:
+            if self.image_token_id is None:
+                _refuse(self.what, "the config has no image_token_id")
+            idx = image_rows_left(ids_cpu, lens, int(self.image_token_id), emb.shape[0], self.what)[0].to(self.device)
+        lib, dev, d, V = _lib.lib(), self.device, self.d, self.tok.shape[0]
+        Rm, cap, kvw, nl = K + 1, L + T, 2 * self.Hkv * HEAD_DIM, len(self.layers)
+        groups = {R: [(g0, min(MAX_BATCH, R - g0)) for g0 in range(0, R, MAX_BATCH)] for R in range(1, Rm + 1)}
+        ws_a = min(Rm, MAX_BATCH) * lib.rgn_lm_decode_attention_workspace_bytes(self.Hq, cap)          # the groups run one after another
+        ws_h = lib.rgn_lm_head_wide_workspace_bytes(V, Rm) if wide else Rm * lib.rgn_lm_head_workspace_bytes(V)
+        head_rows, head_name = (lib.rgn_lm_head_argmax_wide, "rgn_lm_head_argmax_wide") if wide else \
+            (lib.rgn_lm_head_argmax_rows, "rgn_lm_head_argmax_rows")
+        c = self.kv_lookup.get((Rm, cap), dict(cache=(nl, cap, kvw), h=(Rm, d), n=(Rm, d), qkv=(Rm, self.qkv_cols), a=(Rm, self.Hq * HEAD_DIM),
+                                               ff=(Rm, 2 * self.F), g=(Rm, self.F), ws_a=((ws_a + 1) // 2,), ws_h=((ws_h + 1) // 2,)))
+        t = self.buf.get(L, dict(h=(L, d), n=(L, d), qkv=(L, self.qkv_cols), a=(L, self.Hq * HEAD_DIM), ff=(L, 2 * self.F), g=(L, self.F)))
+        ids = input_ids.to(dev, torch.int64).contiguous()
+        seq = torch.empty(L + T, dtype=torch.int64, device=dev)                   # ONE run: the prompt ids, then the new tokens
+        seq[:L].copy_(ids[0])
+        heads = torch.empty(MAX_WIDE_BATCH, dtype=torch.int64, device=dev)        # the argmax after each row of a step
+        res = torch.empty(2 + MAX_WIDE_BATCH, dtype=torch.int64, device=dev)      # a, k', the accepted tokens
+        logits = torch.empty(T, 1, V, dtype=torch.float32, device=dev) if output_logits else None
+        gdev = guess.detach().to(dev).contiguous() if guess is not None else None
+        pguess, nguess = (gdev.data_ptr(), gdev.numel()) if gdev is not None else (None, 0)
+        tab, ntab = tables.to(dev), new_tables.transpose(1, 2).contiguous().to(dev)                       # [2, 1, L, 128], [2, T, 1, 128]
+        st, ck = _stream(), _lib.check
+        ph, pn, pqkv, pa, pff, pg, pws = (c[k].data_ptr() for k in ("h", "n", "qkv", "a", "ff", "g", "ws_a"))
+        pseq, pheads, pres, pwh = seq.data_ptr(), heads.data_ptr(), res.data_ptr(), c["ws_h"].data_ptr()
+        plog = logits.data_ptr() if logits is not None else None
+        limit = L + T
+
+        def settle(n, R, k):
+            """The head over the R normalised rows of c["n"] (logits rows k..k + R - 1), accept + propose, the step's one host read."""
+            ck(head_rows(_p(head), pn, d, R, V, d, pheads, 1, None if plog is None else plog + 4 * V * k, V, pwh, ws_h, st), head_name)
+            ck(lib.rgn_lm_lookup_step(pseq, n, R, pheads, 1, limit, K, max_ngram, pguess, nguess, L, pres, st), "rgn_lm_lookup_step")
+            out = res[:2 + R].tolist()
+            return out[0], out[1], out[2:3 + out[0]]
+
+        h, _ = self._prefill_row(t, ids[0], L, tab[0, 0], tab[1, 0], emb, idx, cache=c["cache"])
+        self._rms(h[L - 1:L], self.final_ln, c["n"][0:1])                         # the final norm on the last row only
+        _, kd, new = settle(L, 1, 0)                                              # the prefill's pick: a step of one row, nothing to accept
+        if self.weights == "fp8":
+            gemv, gemv_name = (lib.rgn_lm_gemm_rows_w8, "rgn_lm_gemm_rows_w8") if wide else (lib.rgn_lm_gemv_w8_rows, "rgn_lm_gemv_w8_rows")
+            wp = lambda w: (w.data_ptr(), ops._wscale(w).data_ptr())
+        else:
+            gemv, gemv_name = (lib.rgn_lm_gemm_rows_bf16, "rgn_lm_gemm_rows_bf16") if wide else (lib.rgn_lm_gemv_bf16_rows, "rgn_lm_gemv_bf16_rows")
+            wp = lambda w: (w.data_ptr(),)
+        ptok, pfin, pcos, psin = self.tok.data_ptr(), self.final_ln.data_ptr(), ntab[0].data_ptr(), ntab[1].data_ptr()
+        Hq, Hkv, F, eps, scale, qc, ad = self.Hq, self.Hkv, self.F, self.eps, float(self.scale), self.qkv_cols, self.Hq * HEAD_DIM
+        rms, swiglu = lib.rgn_rms_norm_rows, lib.rgn_swiglu_bf16
+        I, P, Fl = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
+        plans = {}
+
+        def plan_for(R):
+            """The launches of a step of R rows, built once: per layer those before mRoPE, the three whose arguments move with the step
+            (mRoPE's table rows, the append's cache row, each verify group's n0: leading arguments bound, the tail ready) and the rest."""
+            lp = []
+            for i, p in enumerate(self.layers):
+                pc = c["cache"][i].data_ptr()
+                lp.append((
+                    [_bound(rms, "rgn_rms_norm_rows", ph, d, p["ln1"].data_ptr(), pn, d, R, d, eps, st),
+                     _bound(gemv, gemv_name, *wp(p["wqkv"]), pn, d, p["bqkv"].data_ptr(), None, 0, pqkv, qc, R, qc, d, st)],
+                    functools.partial(lib.rgn_lm_kv_append_bf16, P(pqkv), I(qc), P(pc), I(cap)),
+                    [(functools.partial(lib.rgn_lm_verify_attention_bf16, P(pqkv + 2 * qc * g0), I(qc), P(pc), P(pa + 2 * ad * g0), I(ad)), g0,
+                      (I(Rg), I(Hq), I(Hkv), Fl(scale), P(pws), ctypes.c_size_t(ws_a), P(st))) for g0, Rg in groups[R]],
+                    [_bound(gemv, gemv_name, *wp(p["wo"]), pa, ad, None, ph, d, ph, d, R, d, ad, st),
+                     _bound(rms, "rgn_rms_norm_rows", ph, d, p["ln2"].data_ptr(), pn, d, R, d, eps, st),
+                     _bound(gemv, gemv_name, *wp(p["wgu"]), pn, d, None, None, 0, pff, 2 * F, R, 2 * F, d, st),
+                     _bound(swiglu, "rgn_swiglu_bf16", pff, 2 * F, pg, F, R, F, st),
+                     _bound(gemv, gemv_name, *wp(p["wdown"]), pg, F, None, ph, d, ph, d, R, d, F, st)]))
+            return lp, _bound(rms, "rgn_rms_norm_rows", ph, d, pfin, pn, d, R, d, eps, st), (I(R), I(Hq), I(Hkv), P(st))
+
+        mrope = functools.partial(lib.rgn_mrope_bf16, P(pqkv), I(qc))
+        k, steps, drafted, accepted = 1, 0, 0, 0                                   # k new tokens are settled
+        while k < T and not (eos and any(tok in eos for tok in new)):             # bounded by max_new_tokens: every step settles >= 1
+            R, n = kd + 1, L + k                                                  # rows: new token k - 1 and the kd drafts after it
+            if R not in plans:
+                plans[R] = plan_for(R)
+            lp, (final_norm, final_name), tail = plans[R]
+            cos, sin, row0 = P(pcos + 256 * (k - 1)), P(psin + 256 * (k - 1)), I(n - 1)
+            ck(lib.rgn_text_embed(pseq + 8 * (n - 1), R, ptok, V, None, 0, ph, d, st), "rgn_text_embed")
+            for before, append, verify, after in lp:
+                for launch, name in before:
+                    ck(launch(), name)
+                ck(mrope(cos, sin, *tail), "rgn_mrope_bf16")
+                ck(append(row0, *tail), "rgn_lm_kv_append_bf16")
+                for attend, g0, vtail in verify:
+                    ck(attend(I(n + g0), *vtail), "rgn_lm_verify_attention_bf16")
+                for launch, name in after:
+                    ck(launch(), name)
+            ck(final_norm(), final_name)
+            a, kn, toks = settle(n, R, k)
+            steps, drafted, accepted, k, kd = steps + 1, drafted + kd, accepted + a, k + a + 1, kn
+            new += toks
+        self.last_lookup_stats = dict(steps=steps, drafted=drafted, accepted=accepted, tokens=len(new))
+        out, n_new = assemble_sequences(ids_cpu, torch.tensor(new, dtype=torch.int64).view(-1, 1), eos, pad)
+        out = out.to(input_ids.device)
+        if not return_dict_in_generate:
+            return out
+        return QwenGenerateOutput(out, tuple(logits[j] for j in range(n_new)) if logits is not None else None, None)

@@ -54,6 +54,15 @@ the kernel table: rgn_lm_gemm_rows_bf16 / _w8 at B = 1, 8, 16, 32 on the four la
 
     python tools/qwen_generate_bench.py --batch --wide --sampling --no-ab --out profiles/r30_qwen_wide_batch_bench.json
     python tools/qwen_generate_bench.py --wide-kernels --no-ab --ab-out profiles/r30_qwen_wide_batch_kernel_stats.txt
+
+`--lookup` times `lookup=True` adoptions ("fma" and "mfma", bf16 and fp8) whose steps carry drafted tokens, every leg alternating in the one
+process with the SAME adoption's plain greedy generate.  The drafts are forced through `draft_tokens`, built from the greedy output: all
+wrong (every step carries R = K + 1 rows and settles one token: ms per step at R = 2, 4, 8, and 16, 32 under "mfma"), half of each step's
+drafts right, and all right (ms per new token at 0 %, 50 % and 100 % accepted, with the measured rate); a one-id guess gives R = 1 steps
+through the speculative loop, whose distance from the plain step is the cost of the per-step host read.  ms per step = (t64 - t1) over the
+steps `last_lookup_stats` counts.  The seeded model's own acceptance rate under prompt lookup means nothing and is not reported.
+
+    python tools/qwen_generate_bench.py --lookup --no-ab --out profiles/r31_qwen_lookup_bench.json
 """
 import argparse
 import json
@@ -477,6 +486,85 @@ def batched_sampling(a, res):
         res[f"L{L}"] = r
         print(f"L{L}", json.dumps({k: v for k, v in r.items() if k.endswith("_table")}), flush=True)
 
+LOOKUP_ROWS = {"fma": (2, 4, 8), "mfma": (2, 4, 8, 16, 32)}
+
+
+def half_guess(G, K, T):
+    """A guess of the T greedy tokens G of which every step accepts half of its drafts (rounded down and up in turn): the loop is
+    simulated and the draft after the accepted ones is made wrong."""
+    g, k, up = G.clone(), 1, False
+    while k < T:
+        kd = max(0, min(K, T - k - 1))
+        a = (kd + up) // 2
+        up = not up
+        if a < kd:
+            g[k + a] = (g[k + a] + 1) % 151000
+        k += a + 1
+    return g
+
+
+def lookup(a, res):
+    """The `--lookup` legs: per kernel family, weight format and length, the plain greedy generate and the speculative loop under forced
+    drafts, alternating in one process."""
+    from transformers import Qwen2_5_VLForConditionalGeneration
+    from regione_amd import qwen_text_encoder as QT
+    cfg = full_size_config()
+    torch.manual_seed(0)
+    with torch.device("cuda"):
+        mod = Qwen2_5_VLForConditionalGeneration(cfg).eval()
+    mod = mod.to(torch.bfloat16)
+    torch.cuda.empty_cache()
+    res["weights"] = "both"
+    g = torch.Generator().manual_seed(1)
+    prompts = {L: torch.randint(0, 151000, (1, L), generator=g).cuda() for L in LENGTHS}
+    for fmt in ("bf16", "fp8"):
+        for fam in ("fma", "mfma"):
+            enc = QT.HipQwen25VLTextEncoder(mod, weights=fmt, batch_kernels=fam, lookup=True)
+            for L in LENGTHS:
+                ids = prompts[L]
+                G = enc.generate(ids, max_new_tokens=NEW, eos_token_id=[])[0, L:]
+                wrong = (G + 1) % 151000
+                top = LOOKUP_ROWS[fam][-1]
+                arms = {"plain_1": lambda: enc.generate(ids, max_new_tokens=1, eos_token_id=[]),
+                        "plain_64": lambda: enc.generate(ids, max_new_tokens=NEW, eos_token_id=[]),
+                        "look_1": lambda: enc.generate(ids, max_new_tokens=1, eos_token_id=[], draft_tokens=G[:1]),
+                        "r1_64": lambda: enc.generate(ids, max_new_tokens=NEW, eos_token_id=[], draft_tokens=G[:1])}
+                for R in LOOKUP_ROWS[fam]:
+                    arms[f"r{R}_acc0_64"] = lambda R=R: enc.generate(ids, max_new_tokens=NEW, eos_token_id=[], prompt_lookup_num_tokens=R - 1,
+                                                                     draft_tokens=wrong)
+                for R in sorted({8, top}):
+                    half = half_guess(G, R - 1, NEW)
+                    arms[f"r{R}_acc50_64"] = lambda R=R, half=half: enc.generate(ids, max_new_tokens=NEW, eos_token_id=[],
+                                                                                 prompt_lookup_num_tokens=R - 1, draft_tokens=half)
+                    arms[f"r{R}_acc100_64"] = lambda R=R: enc.generate(ids, max_new_tokens=NEW, eos_token_id=[], prompt_lookup_num_tokens=R - 1,
+                                                                       draft_tokens=G)
+                ts, stats = {k: [] for k in arms}, {}
+                with torch.no_grad():
+                    for k, fn in arms.items():                                   # warm; every leg must give the greedy tokens
+                        out = fn()
+                        assert torch.equal(out[0, L:], G[:out.shape[1] - L]), k
+                        stats[k] = enc.last_lookup_stats
+                    for _ in range(a.iters):
+                        for k, fn in arms.items():                               # the legs alternate
+                            ts[k].append(_ms(fn))
+                r = {"L": L, "weights": fmt, "batch_kernels": fam, **{k: _stat(v) for k, v in ts.items()}}
+                med = {k: r[k]["median_ms"] for k in arms}
+                plain = (med["plain_64"] - med["plain_1"]) / (NEW - 1)
+                rows = [dict(leg="plain", ms_per_step=plain, ms_per_token=plain)]
+                for k in arms:
+                    if k.endswith("_64") and k != "plain_64":
+                        st = stats[k]
+                        dt = med[k] - med["look_1"]
+                        rows.append(dict(leg=k[:-3], steps=st["steps"], drafted=st["drafted"], accepted=st["accepted"],
+                                         accepted_share=st["accepted"] / st["drafted"] if st["drafted"] else None,
+                                         ms_per_step=dt / st["steps"], ms_per_token=dt / (NEW - 1), plain_steps=dt / (NEW - 1) / plain))
+                r["table"] = rows
+                r["host_read_ms_per_step"] = rows[1]["ms_per_step"] - plain      # the R = 1 step of the speculative loop against the plain step
+                res[f"{fmt}_{fam}_L{L}"] = r
+                print(f"{fmt} {fam} L{L}", json.dumps(rows), flush=True)
+            del enc
+            torch.cuda.empty_cache()
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -493,12 +581,21 @@ def main():
     ap.add_argument("--wide", action="store_true", help="with --batch: batch_kernels=\"mfma\" at B = 1, 8, 16, 32 beside the default kernels at "
                     "B = 1, 8 (bf16 and fp8); with --sampling also the sampled legs at B = 16, 32")
     ap.add_argument("--wide-kernels", action="store_true", help="only the kernel table of the MFMA row GEMM beside the GEMV entries (--ab-out)")
+    ap.add_argument("--lookup", action="store_true", help="lookup=True adoptions under forced drafts beside their own plain greedy generate")
     a = ap.parse_args()
     from regione_amd import build
     sha = build.csrc_hash()
     res = {"device": torch.cuda.get_device_name(0), "csrc_sha16": sha, "iters": a.iters, "new_tokens": NEW,
            "stat": "median and min / max of warm, synchronised runs, the two sides alternating; ms per new token = (t64 - t1) / 63 of the medians",
            "model": "Qwen2.5-VL-7B language model, seeded init, text-only ids, no EOS", "hbm_bytes_per_s": HBM_BYTES_PER_S}
+    if a.lookup:
+        res["stat"] = ("median and min / max of warm, synchronised runs, every leg alternating with the same adoption's plain greedy generate; "
+                       "ms per step = (t64 - t1) / steps, ms per token = (t64 - t1) / 63 of the medians")
+        lookup(a, res)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     if a.wide_kernels or (a.batch and a.wide):
         res["stat"] = ("median and min / max of warm, synchronised runs, every leg alternating; ms per step = (t64 - t1) / 63 of the medians; "
                        "tokens per second = B / that")
