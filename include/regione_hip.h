@@ -391,8 +391,24 @@ int rgn_attention_plan_query(int Sq, int Skv, int H, size_t workspace_bytes);
  * the same call) for the [EXT] AutoencoderKL of the public FLUX.1 / Step1X-Edit checkpoints (16 latent channels, block widths
  * 128-256-512-512, 3 ResNet blocks per up level, one mid-block attention head of width 512, GroupNorm(32, eps 1e-6) + SiLU).
  * Activation layout of every entry: a ZERO-BORDERED pixel-major image [Hp * Wp, C] bf16, Hp = H + 2, Wp = W + 2, row = y * Wp + x of
- * the PADDED image, channels contiguous.  The caller allocates >= Wp + 1 rows of readable memory in front of row 0 and behind the
- * last row (guard rows: a 3 x 3 window reads them for border outputs, which are then written as zeros).
+ * the PADDED image, channels contiguous.  The caller allocates >= Wp + 1 + group rows of readable memory in front of row 0 and behind
+ * the last row (guard rows: a 3 x 3 window reads them for border outputs, which are then written as zeros).
+ * What a launch reads WITH AN EFFECT on what it stores (tests/test_gpu_conv_probes.py, probe f, holds this with NaN everywhere else):
+ *   - the image X itself, border rows included: they must be zero (they are the convolution's padding);
+ *   - group = 1, 1 x 1, rgn_conv_s2_bf16 and rgn_conv_up2_bf16: nothing outside the image - guard rows of X may hold anything, NaN
+ *     included (the stride-2 launch carries them into its scratch row only);
+ *   - 3 x 3 with group > 1: the block-Toeplitz matrix multiplies the whole window of group + 2 pixels per kernel row, its zeros
+ *     included, so the up to group - 1 guard rows of X directly in front of row 0 and the up to group - 1 directly behind the last
+ *     row are added into INTERIOR outputs of the first / last image row through zero weights: they must hold FINITE values (0 x NaN
+ *     is NaN).  Zero-initialised guard rows, the zeros a pixel-group launch writes behind its image and the zeroed scratch row of
+ *     rgn_conv_up2_bf16 satisfy this; the scratch row of rgn_conv_s2_bf16 (the first guard row behind ITS output, real convolution
+ *     values, racing stores) is finite whenever its input and that input's guard rows are, but is no defined value: do not feed a
+ *     stride-2 output to a 3 x 3 pixel-group launch without clearing that row;
+ *   - resid: interior pixels only (border and guard rows of the skip image may hold anything);
+ *   - Wt / bias: N rows of K values / N values, nothing behind them.
+ * What a launch writes: rgn_conv_bf16 every row of the image (border rows as zeros), columns [0, Cout) of each - columns [Cout, ldy)
+ * are left untouched for group = 1 and written as zeros for group > 1 - plus, for group > 1, zeros to the rows up to group - 1 behind
+ * the image; the table launches only the rows their tables name.
  *
  * rgn_conv_bf16: Y = conv(X, Wt) + bias (+ resid), border rows of Y written as ZEROS.  taps = 9: 3 x 3, stride 1, zero padding 1, as an
  * implicit GEMM on the hand-scheduled MFMA loop (K = 9 Cin in (ky, kx, c) order: inside one kernel row the three taps' channels are

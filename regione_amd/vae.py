@@ -61,13 +61,18 @@ def attention_path(mode: str, rows: int) -> str:
 
 class PaddedImage:
     """A zero-bordered pixel-major activation image [Hp * Wp, C] bf16 inside a storage tensor with guard rows on both sides.
-    `border_zero`: the border rows are known to be zero - true from creation, then whatever the last writer left (`_wrote`)."""
+    `border_zero`: the border rows are known to be zero - true from creation, then whatever the last writer left (`_wrote`).
+    Guard rows (include/regione_hip.h; tests/test_gpu_conv_probes.py probe f): most launches read them only for outputs they then mask,
+    but a 3 x 3 pixel-group convolution adds the up to group - 1 rows next to the image, on either side, into interior outputs through the
+    zero entries of its Toeplitz matrix - those rows must stay FINITE.  They are zero from creation; the writers that touch them keep them
+    finite: a pixel-group launch writes zeros to the group - 1 rows behind its output, conv_up2 a zeroed scratch row, conv_s2 a scratch row
+    of real (finite, but undefined: racing stores) convolution values - no pipeline here feeds a conv_s2 output to a pixel-group launch."""
 
     def __init__(self, H: int, W: int, C: int, device):
         self.H, self.W, self.C = H, W, C
         self.Hp, self.Wp = H + 2, W + 2
         self.rows = self.Hp * self.Wp
-        g = self.Wp + 72                     # guard rows: a window reads up to Wp + 1 + group rows outside the image, pixel groups write group - 1
+        g = self.Wp + 72                     # guard rows: a window reads up to Wp + 1 + group rows outside the image (group <= 64), pixel groups write group - 1
         self.storage = torch.zeros((self.rows + 2 * g, C), dtype=torch.bfloat16, device=device)
         self.t = self.storage[g:g + self.rows]
         self.border_zero = True
@@ -367,7 +372,10 @@ def conv_up2(x: PaddedImage, uw: UpConvWeights, out: PaddedImage, rows_table: to
 def downsample_rows(H: int, W: int, device) -> torch.Tensor:
     """rgn_conv_s2_bf16's row table for an H x W input (padded pitch W + 2): GEMM row m = yo * (W + 2) + xo -> padded row of output pixel
     (yo, xo) in the (H / 2 + 2) x (W / 2 + 2) image, or - for the unused columns xo >= W / 2 of the wide grid - the first guard row behind
-    the output image (written, never read).  Built once per size (setup, not on the decode / encode path)."""
+    the output image: the scratch row.  It receives real convolution values from many GEMM rows (the last store wins) and is never read by
+    a group = 1, 1 x 1, stride-2 or upsampling launch; a 3 x 3 PIXEL-GROUP launch on that image would add it, times zero, into the last
+    image row (PaddedImage), which is harmless while it is finite and the reason not to chain the two without clearing it.  Built once per
+    size (setup, not on the decode / encode path)."""
     Wp, Ho, Wo = W + 2, H // 2, W // 2
     m = torch.arange(Ho * Wp, dtype=torch.int64, device=device)
     yo, xo = m // Wp, m % Wp

@@ -51,8 +51,8 @@ MUTANTS = ("piece_last_tile_dropped", "piece_boundary_tile_twice", "reduce_skips
 #                        <GATE_RESID>   pc256_av1_gate pc256_long grp256_pieces
 #   tile_offset != 0 (whole rounds plus remainder): r257_plain (one launch), r257_pieces, r257_quarter - probes (a), (b) only.
 # Left out: the 128 geometry with whole rounds AND a split remainder (513 tiles x K >= 1024 with a cost-model split needs a 2 GB
-# operand); a gemm_pieces value that leaves a piece without a K tile (not a production plan: nk / S >= 6); rgn_conv_*, rgn_gemv_bf16 and
-# the row-band launcher (pinned elsewhere).
+# operand); a gemm_pieces value that leaves a piece without a K tile (not a production plan: nk / S >= 6); rgn_conv_* (pinned by
+# tests/conv_model.py / tests/test_gpu_conv_probes.py), rgn_gemv_bf16 and the row-band launcher (pinned elsewhere).
 G128, G256C, G256 = dict(gemm_geometry=128), dict(gemm_geometry=256, gemm_asm=0), dict(gemm_geometry=256)
 
 

@@ -1,7 +1,11 @@
 """-m gpu: the HIP VAE decode (regione_amd/vae.py, csrc/vae.hip, rgn_conv_bf16) against an fp32 PyTorch
 module of the public AutoencoderKL decoder with seeded weights (tests/host_vae.py).  [EXT] / unpinned: nothing of the VAE lives in
 /root/reference (the reference calls `self.vae.decode`, FluxKontext/inplace.py:396-402).  Tolerance: PSNR >= 40 dB on the decoded
-image tensor (BASELINE.json north_star's figure for latents, applied to the image), peak = the reference tensor's value range."""
+image tensor (BASELINE.json north_star's figure for latents, applied to the image), peak = the reference tensor's value range.
+The PSNR bars of this file (45 / 44 dB on single convolutions, 40 dB on whole decodes and encodes) are end-to-end sanity checks on random
+images: a convolution that is wrong on one border column, one tile boundary or one K tile clears them.  What pins rgn_conv_bf16,
+rgn_conv_s2_bf16 and rgn_conv_up2_bf16 to the mathematics - bit-exact probes and element-wise fp64 bounds on every launch path - is
+tests/test_gpu_conv_probes.py (model: tests/conv_model.py)."""
 import math
 
 import pytest
