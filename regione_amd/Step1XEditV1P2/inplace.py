@@ -7,8 +7,8 @@ forward :546-690, processor :806-945).  Family deltas:
     (`k_cache_even/odd`, :800-888);
   * the two branches have different text lengths (`txt_length` / `neg_txt_length`, selection :833,:868);
   * norm-rescaled CFG (:421-430) -> rgn_cfg_combine(mode 1); v1p2 gamma table (:48-50).
-Out of scope (VLM prompting, not the hot path): the thinking / reflection retry loop (:192-212,470-486)
-and `text_token_mapping` ([EXT] extra text projection, :606-609) - the harness consumes the connector /
+Not in this file: the thinking / reflection retry loop (:192-212,470-543), which runs around the hosted edit
+(regione_amd/adapters/thinking.py), and `text_token_mapping` ([EXT] extra text projection, :606-609) - the harness consumes the connector /
 mapping OUTPUTS as prompt embeddings.
 """
 from __future__ import annotations

@@ -24,11 +24,13 @@ diffusers is not installed in the build image: the call sequence follows the ref
 LoRA adapters loaded into the host transformer (PEFT layers: `load_lora_weights` without `fuse_lora`) are merged into the engine's weights
 on the device at adoption and re-merged when the adapter state changes (`lora_sync`, the LoRA section of trunk.py): no per-step side path.
 
-Four modules, each importing only from the ones before it; this file re-exports their names and holds no logic:
+Five modules, each importing only from the ones before it; this file re-exports their names and holds no logic:
     trunk.py        the transformer's weights onto the engine: name maps, layout check, LoRA merge and `lora_sync`, `adopt_engine`
     components.py   VAE, text encoders, Qwen2.5-VL language model / vision tower, image ops: adoption (`hip_*_for`), binders, refusals
     connector.py    Step1X-Edit's per-step connector: the host-module and the HIP object behind the engine's `connector` hook
     hosted.py       the three hosted `__call__`s, `HostedPipeline`, `adopt`, `attach`, `swap_host_class`
+    thinking.py     Step1X-Edit v1p2's thinking / reflection retry loop in plain Python, the thinker a host brings (`thinker_for`), and the
+                    `Retry` that hosted.py's Step1X call runs through the slot it keeps for it
 """
 from .trunk import (_FAMILY_OF, _KEYMAPS, _lora_active, _lora_checked, _lora_fingerprint, _lora_plan,  # noqa: F401
                     adopt_engine, infer_config, lora_layers, lora_sync, map_key)
@@ -41,3 +43,4 @@ from .connector import _HipConnector, _HostConnector, hip_step1x_connector_for  
 from .hosted import (PREFERRED_KONTEXT_RESOLUTIONS, QWEN_CONDITION_IMAGE_SIZE, QWEN_VAE_IMAGE_SIZE, STEP1X_DEFAULT_NEGATIVE,  # noqa: F401
                      HostedFluxKontextPipeline, HostedOutput, HostedPipeline, _host_name, _hosted_flux, _hosted_qwen, _hosted_step1x,
                      _lora_call, _refuse_unused, adopt, attach, is_engine_pipeline, restore_host_class, swap_host_class)
+from .thinking import LoopResult, Retry, TimedThinker, best_index, reflection_loop, thinker_for  # noqa: F401

@@ -47,6 +47,11 @@ def _bound(obj, attr, value):
             d[attr] = prev
 
 
+def _host_name(pipe) -> str:
+    cls = getattr(pipe, "_regione_host_class", None) or pipe.__class__
+    return cls.__name__
+
+
 def _bf(t, dev):
     return t.to(device=dev, dtype=torch.bfloat16) if t is not None else None
 
@@ -203,9 +208,17 @@ def _hip_text_encoders(host, dev):
 
 
 _QWEN_TEXT_HOSTS = ("QwenImageEditPipeline", "QwenImageEditPlusPipeline")
+# Step1X-Edit's prompt encoder is the same module; v1p2's thinker also calls its `generate`, under the module's own generation_config
+_STEP1X_TEXT_HOSTS = ("Step1XEditPipeline", "Step1XEditPipelineV1P2")
 
 
-def hip_qwen_text_encoder_for(host, dev):
+def _step1x_text_sampling_default(host) -> bool:
+    """What an absent `_regione_hip_text_sampling` means for this host: True for Step1XEditPipelineV1P2 (Qwen2.5-VL's generation_config
+    samples with a repetition penalty, and the thinker passes no decoding argument), False for every other host."""
+    return _host_name(host) == "Step1XEditPipelineV1P2"
+
+
+def hip_qwen_text_encoder_for(host, dev, sampling_default: bool = False):
     """The host's Qwen2.5-VL prompt encoder with its language model adopted onto the HIP kernels (regione_amd/qwen_text_encoder.py;
     SURVEY.md section 8 row f4), once per host pipeline and kept on it as `_regione_hip_qwen_text`.  A module the kernels do not cover
     (`qwen25vl_refusal`: sliding-window layers, another head dim, ...; non-bf16 weights; PEFT / LoRA layers) stays the host's, with one
@@ -218,6 +231,7 @@ def hip_qwen_text_encoder_for(host, dev):
     scales (HipQwen25VLTextEncoder(weights="fp8")); absent, the adoption is "bf16"; another value raises ValueError naming the two.
     `pipe._regione_hip_text_sampling = True` before the first call adopts with `sampling=True` (generate honours do_sample, temperature,
     top_k, top_p and repetition_penalty); absent, it is False; a value that is not a bool raises ValueError.
+    (`sampling_default=True`, what the hosted Step1X-Edit v1p2 call passes, makes an ABSENT switch mean True; an explicit False is honoured.)
     `pipe._regione_hip_text_batch = N` before the first call adopts with `max_batch=N` (generate takes up to N left-padded rows and
     decodes them from one weight stream); absent, it is 1; a value that is not an int in 1..8 raises ValueError naming the range.
     `pipe._regione_hip_text_batch_sampling = True` before the first call adopts with `batch_sampling=True` (such a batch takes the decoding
@@ -237,7 +251,7 @@ def hip_qwen_text_encoder_for(host, dev):
     fmt = host.__dict__.get("_regione_hip_text_weights", "bf16")
     if fmt not in ("bf16", "fp8"):
         raise ValueError(f"pipe._regione_hip_text_weights = {fmt!r}: \"bf16\" and \"fp8\" are accepted")
-    sampling = host.__dict__.get("_regione_hip_text_sampling", False)
+    sampling = host.__dict__.get("_regione_hip_text_sampling", sampling_default)
     if not isinstance(sampling, bool):
         raise ValueError(f"pipe._regione_hip_text_sampling = {sampling!r}: True and False are accepted")
     kernels = host.__dict__.get("_regione_hip_text_batch_kernels", "fma")

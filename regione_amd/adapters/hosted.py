@@ -6,7 +6,7 @@ import warnings
 
 import torch
 
-from .components import (_QWEN_TEXT_HOSTS, _bf, _bound, _hip_qwen_image_processor, _hip_qwen_text_encoder, _hip_text_encoders, _hip_vae_encode,
+from .components import (_QWEN_TEXT_HOSTS, _STEP1X_TEXT_HOSTS, _bf, _bound, _host_name, _step1x_text_sampling_default, _hip_qwen_image_processor, _hip_qwen_text_encoder, _hip_text_encoders, _hip_vae_encode,
                          _image_inputs_on_device, _postprocess_image, _postprocess_qwen_image, hip_qwen_text_encoder_for,
                          hip_text_encoders_for, hip_vae_encoder_for, hip_vae_for)
 from .connector import _HipConnector, _HostConnector, hip_step1x_connector_for
@@ -26,10 +26,16 @@ STEP1X_DEFAULT_NEGATIVE = ("worst quality, wrong limbs, unreasonable limbs, norm
 QWEN_CONDITION_IMAGE_SIZE, QWEN_VAE_IMAGE_SIZE = 384 * 384, 1024 * 1024                                # QwenImageEditPlus/inplace.py:53-54
 
 
+# Step1X-Edit v1p2's thinking / reflection retry loop is the module AFTER this one (adapters/thinking.py; a module of this package imports
+# only from the ones before it): importing the package puts its `Retry` here, `_hosted_step1x` calls it when a v1p2 switch is on
+_STEP1X_RETRY = []
+
+
 class HostedOutput(dict):
-    def __init__(self, images, timing=None):
-        super().__init__(images=images)
+    def __init__(self, images, timing=None, **extra):
+        super().__init__(images=images, **extra)      # extra: what a family's output carries besides (Step1X v1p2: final_images, ...)
         self.images = images
+        self.__dict__.update(extra)
         self.timing = timing or {}           # wall-clock seconds of the three stages: encode / loop / decode
 
 
@@ -208,19 +214,26 @@ def _hosted_step1x(host, eng, image=None, prompt=None, negative_prompt=None, tru
                    callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), enable_thinking_mode=None,
                    enable_reflection_mode=None, max_try_cnt=None, **unused):
     """Step1XEditPipeline / Step1XEditPipelineV1P2 `__call__` around the engine loop (Step1XEdit/inplace.py:185-330,:437-455;
-    Step1XEditV1P2/inplace.py:214-300).  Not hosted: v1p2's thinking / reflection retry loop (VLM prompting, :192-212) - the
-    v1p2 switches `enable_thinking_mode` / `enable_reflection_mode` / `max_try_cnt` (Step1XEditV1P2/inplace.py:107-109) are
-    accepted when they switch that loop OFF (the reference driver's own call, src/Step1X-Edit-v1p2/main.py:42-43,:69-77),
-    True raises NotImplementedError; left unspecified the hosted call runs ONE attempt without reflection (the reference's
-    signature default is reflection on: stated deviation)."""
+    Step1XEditV1P2/inplace.py:192-300, :470-543).  One edit - `encode_image` to `_output_process_image` - is `edit_once`; the host's own
+    `encode_prompt` runs with `text_encoder` bound to the adopted HIP Qwen2.5-VL encoder and the VLM image processor on the device.
+    v1p2's switches `enable_thinking_mode` / `enable_reflection_mode` / `max_try_cnt` (:107-109) run `reflection_loop` (adapters/thinking.py)
+    around `edit_once` with the host's thinker (`thinker_for`; a host without one raises NotImplementedError) and return a HostedOutput
+    with `images`, `final_images`, `think_info`, `best_info` (and `reformat_prompt` with thinking on) whatever `return_dict` says, as the
+    reference does.  `enable_reflection_mode` left unspecified runs ONE attempt without reflection, with a warning (the reference's
+    signature default is reflection on: stated deviation).  `timing`: encode_s / loop_s / decode_s summed over the tries,
+    `think_s`, `reflect_s`, and `tries` (one dict per try)."""
     unused = _lora_call(host, eng, unused, "joint_attention_kwargs")
     v1p2 = _host_name(host).endswith("V1P2")
     think = dict(enable_thinking_mode=enable_thinking_mode, enable_reflection_mode=enable_reflection_mode, max_try_cnt=max_try_cnt)
+    dev = eng.transformer.device
+    retry = None
     if v1p2:
         for k in ("enable_thinking_mode", "enable_reflection_mode"):
-            if think[k]:
-                raise NotImplementedError(f"{_host_name(host)}.__call__: {k}=True (the VLM thinking / reflection retry loop, "
-                                          "Step1XEditV1P2/inplace.py:192-212) is not hosted by the HIP loop; pass False")
+            if think[k] and retry is None:
+                retry = _STEP1X_RETRY[0](host, dev, k)        # finds the host's thinker, or raises the NotImplementedError naming `k`
+        if enable_reflection_mode and output_type == "latent":
+            raise ValueError(f"{_host_name(host)}.__call__: enable_reflection_mode=True with output_type=\"latent\": reflection shows the "
+                             "edited IMAGE to the VLM, latents cannot be reflected on")
         if enable_reflection_mode is None:
             # the reference's signature default is reflection ON (Step1XEditV1P2/inplace.py:108): a caller that leaves it unspecified
             # gets ONE attempt here - say so instead of deviating silently (advisor finding, round 4)
@@ -230,68 +243,96 @@ def _hosted_step1x(host, eng, image=None, prompt=None, negative_prompt=None, tru
     else:                                   # v1p1 has no such arguments: a caller passing them gets the usual refusal
         unused = dict(unused, **{k: v for k, v in think.items() if v is not None})
     _refuse_unused(_host_name(host) + ".__call__", unused)
-    dev = eng.transformer.device
-    clk = _Clock(dev)
     exec_dev = getattr(host, "_execution_device", dev)
     _one_image_only(prompt, num_images_per_prompt)
-    # 1. image (host.encode_image resizes, keeps the reference image for the VLM, remembers how to undo the resize)
-    args = (image, width, height, size_level, exec_dev, 1) if v1p2 else (image, width, height, exec_dev, 1)
-    image, ref_image, img_info, width, height = host.encode_image(*args)
-    # 2./3. prompts through the host's VLM encoder
-    has_neg = negative_prompt is not None or (negative_prompt_embeds is not None and negative_prompt_embeds_mask is not None)
-    if not has_neg:
-        negative_prompt = "" if image is not None else STEP1X_DEFAULT_NEGATIVE
-    if v1p2:          # encode_prompt returns a record: embedding / mask / txt_ids / text_embeds / text_masks (:241-254)
-        pos = host.encode_prompt(ref_image=ref_image, prompt=prompt, device=exec_dev, num_images_per_prompt=1)
-        neg = host.encode_prompt(ref_image=ref_image, prompt=negative_prompt, device=exec_dev, num_images_per_prompt=1)
-        prompt_embeds, prompt_embeds_mask = pos.embedding, pos.mask
-        negative_prompt_embeds, negative_prompt_embeds_mask = neg.embedding, neg.mask
-        text = [(pos.text_embeds, pos.text_masks), (neg.text_embeds, neg.text_masks)]
-        dtype = pos.embedding.dtype
+    # the prompt encoder of this host (adopted at attach(); here for a caller that came another way), before anything binds it
+    hip_qwen_text_encoder_for(host, dev, sampling_default=_step1x_text_sampling_default(host))
+    embeds_in = (prompt_embeds, prompt_embeds_mask, negative_prompt_embeds, negative_prompt_embeds_mask)
+    tries = []
+
+    def edit_once(image, prompt):
+        nonlocal width, height                                # carried from try to try (Step1XEditV1P2/inplace.py:214 reassigns them)
+        clk = _Clock(dev)
+        prompt_embeds, prompt_embeds_mask, negative_prompt_embeds, negative_prompt_embeds_mask = embeds_in
+        neg_prompt = negative_prompt
+        # 1. image (host.encode_image resizes, keeps the reference image for the VLM, remembers how to undo the resize)
+        args = (image, width, height, size_level, exec_dev, 1) if v1p2 else (image, width, height, exec_dev, 1)
+        image, ref_image, img_info, width, height = host.encode_image(*args)
+        # 2./3. prompts through the host's VLM encoder: its language model and vision tower on the HIP kernels, its image processor on
+        # the device
+        has_neg = neg_prompt is not None or (negative_prompt_embeds is not None and negative_prompt_embeds_mask is not None)
+        if not has_neg:
+            neg_prompt = "" if image is not None else STEP1X_DEFAULT_NEGATIVE
+        with _hip_qwen_text_encoder(host, dev), _hip_qwen_image_processor(host, dev):
+            if v1p2:      # encode_prompt returns a record: embedding / mask / txt_ids / text_embeds / text_masks (:241-254)
+                pos = host.encode_prompt(ref_image=ref_image, prompt=prompt, device=exec_dev, num_images_per_prompt=1)
+                neg = host.encode_prompt(ref_image=ref_image, prompt=neg_prompt, device=exec_dev, num_images_per_prompt=1)
+                prompt_embeds, prompt_embeds_mask = pos.embedding, pos.mask
+                negative_prompt_embeds, negative_prompt_embeds_mask = neg.embedding, neg.mask
+                text = [(pos.text_embeds, pos.text_masks), (neg.text_embeds, neg.text_masks)]
+                dtype = pos.embedding.dtype
+            else:
+                prompt_embeds, prompt_embeds_mask, _ = host.encode_prompt(
+                    ref_image=ref_image, prompt=prompt, prompt_embeds=prompt_embeds, prompt_embeds_mask=prompt_embeds_mask,
+                    device=exec_dev, num_images_per_prompt=1)
+                negative_prompt_embeds, negative_prompt_embeds_mask, _ = host.encode_prompt(
+                    ref_image=ref_image, prompt=neg_prompt, prompt_embeds=negative_prompt_embeds,
+                    prompt_embeds_mask=negative_prompt_embeds_mask, device=exec_dev, num_images_per_prompt=1)
+                text, dtype = None, prompt_embeds.dtype
+        # 4. latents
+        pl = (image, 1, eng.transformer.cfg_model.in_channels // 4, height, width, dtype, exec_dev, generator)
+        with _hip_vae_encode(host, dev):
+            lat, image_latents, _, _ = host.prepare_latents(*pl) if v1p2 else host.prepare_latents(*pl, latents)
+        # the connector: the adopted HIP one (prepared once per edit, advanced per computed step), or the host module per branch per step
+        masks, embeds = [prompt_embeds_mask, negative_prompt_embeds_mask], [prompt_embeds, negative_prompt_embeds]
+        hip = hip_step1x_connector_for(host, dev)
+        if hip is not None:
+            why, n_valid = _HipConnector.parse(masks, embeds)
+            if why is not None:
+                warnings.warn(f"connector kept on the host module for this call: {why}", RuntimeWarning, stacklevel=5)
+                hip = None
+        if hip is not None:
+            connector = _HipConnector(hip, host.transformer, dev, n_valid, embeds, text)
+            connector.bind_text()
+        else:
+            connector = _HostConnector(host.transformer, dev, masks, text)
+        clk.mark("encode_s")
+        # 5.-6. loop on the engine; the connector feeds it per computed step
+        kw = dict(image=_bf(image_latents, dev), prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
+                  pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None, height=height, width=width,
+                  num_inference_steps=num_inference_steps, true_cfg_scale=true_cfg_scale, guidance_scale=guidance_scale,
+                  latents=_bf(lat, dev), return_dict=False, timesteps_truncate=timesteps_truncate,
+                  process_norm_power=process_norm_power)
+        with _bound(eng.transformer, "connector", connector):
+            lat = _run_loop(eng, clk, kw, trace, sigmas, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        # 7. decode (:437-446)
+        if output_type == "latent":
+            out = lat
+        else:
+            vae = host.vae
+            lat = host._unpack_latents(lat.to(getattr(vae, "dtype", lat.dtype)), height, width, host.vae_scale_factor)
+            lat = lat / vae.config.scaling_factor + vae.config.shift_factor
+            out = _postprocess_image(host, vae, lat, dev, output_type)
+            out = host._output_process_image(out, img_info)
+        clk.mark("decode_s")
+        tries.append(clk.out)
+        return out
+
+    if retry is None:                                         # one attempt, no VLM prompting: the call as it always was
+        out = edit_once(image, prompt)
     else:
-        prompt_embeds, prompt_embeds_mask, _ = host.encode_prompt(
-            ref_image=ref_image, prompt=prompt, prompt_embeds=prompt_embeds, prompt_embeds_mask=prompt_embeds_mask,
-            device=exec_dev, num_images_per_prompt=1)
-        negative_prompt_embeds, negative_prompt_embeds_mask, _ = host.encode_prompt(
-            ref_image=ref_image, prompt=negative_prompt, prompt_embeds=negative_prompt_embeds,
-            prompt_embeds_mask=negative_prompt_embeds_mask, device=exec_dev, num_images_per_prompt=1)
-        text, dtype = None, prompt_embeds.dtype
-    # 4. latents
-    pl = (image, 1, eng.transformer.cfg_model.in_channels // 4, height, width, dtype, exec_dev, generator)
-    with _hip_vae_encode(host, dev):
-        latents, image_latents, _, _ = host.prepare_latents(*pl) if v1p2 else host.prepare_latents(*pl, latents)
-    # the connector: the adopted HIP one (prepared once per edit, advanced per computed step), or the host module per branch per step
-    masks, embeds = [prompt_embeds_mask, negative_prompt_embeds_mask], [prompt_embeds, negative_prompt_embeds]
-    hip = hip_step1x_connector_for(host, dev)
-    if hip is not None:
-        why, n_valid = _HipConnector.parse(masks, embeds)
-        if why is not None:
-            warnings.warn(f"connector kept on the host module for this call: {why}", RuntimeWarning, stacklevel=3)
-            hip = None
-    if hip is not None:
-        connector = _HipConnector(hip, host.transformer, dev, n_valid, embeds, text)
-        connector.bind_text()
-    else:
-        connector = _HostConnector(host.transformer, dev, masks, text)
-    clk.mark("encode_s")
-    # 5.-6. loop on the engine; the connector feeds it per computed step
-    kw = dict(image=_bf(image_latents, dev), prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
-              pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None, height=height, width=width,
-              num_inference_steps=num_inference_steps, true_cfg_scale=true_cfg_scale, guidance_scale=guidance_scale,
-              latents=_bf(latents, dev), return_dict=False, timesteps_truncate=timesteps_truncate,
-              process_norm_power=process_norm_power)
-    with _bound(eng.transformer, "connector", connector):
-        latents = _run_loop(eng, clk, kw, trace, sigmas, callback_on_step_end, callback_on_step_end_tensor_inputs)
-    # 7. decode (:437-446)
-    if output_type == "latent":
-        out = latents
-    else:
-        vae = host.vae
-        lat = host._unpack_latents(latents.to(getattr(vae, "dtype", latents.dtype)), height, width, host.vae_scale_factor)
-        lat = lat / vae.config.scaling_factor + vae.config.shift_factor
-        out = _postprocess_image(host, vae, lat, dev, output_type)
-        out = host._output_process_image(out, img_info)
-    return _finish(host, clk, out, return_dict)
+        res = retry(edit_once, image, prompt, enable_thinking_mode, enable_reflection_mode, 3 if max_try_cnt is None else max_try_cnt)
+        out = res.images
+    if hasattr(host, "maybe_free_model_hooks"):               # once, after the last try (:488-489)
+        host.maybe_free_model_hooks()
+    timing = {k: sum(t[k] for t in tries) for k in ("encode_s", "loop_s", "decode_s")}
+    if retry is None:
+        return HostedOutput(out, timing) if return_dict else (out,)
+    timing.update(retry.thinker.seconds, tries=tries)
+    extra = dict(final_images=res.final_images, think_info=res.think_info, best_info=res.best_info)
+    if enable_thinking_mode:
+        extra["reformat_prompt"] = res.reformat_prompt
+    return HostedOutput(out, timing, **extra)
 
 
 def _qwen_dims(target_area, ratio):
@@ -417,11 +458,6 @@ class HostedPipeline:
 HostedFluxKontextPipeline = HostedPipeline          # round-1 name
 
 
-def _host_name(pipe) -> str:
-    cls = getattr(pipe, "_regione_host_class", None) or pipe.__class__
-    return cls.__name__
-
-
 def adopt(pipe, device="cuda"):
     """Hosted wrapper (image + prompt in, image out) for any of the five pipeline classes."""
     if _host_name(pipe) not in _HOSTED:
@@ -447,6 +483,8 @@ def attach(pipe, device="cuda"):
             hip_text_encoders_for(pipe, eng.transformer.device)
         if _host_name(pipe) in _QWEN_TEXT_HOSTS:              # Qwen-Image-Edit's prompt encoder: the Qwen2.5-VL language model
             hip_qwen_text_encoder_for(pipe, eng.transformer.device)
+        if _host_name(pipe) in _STEP1X_TEXT_HOSTS:            # Step1X-Edit's prompt encoder and v1p2's thinker: the same module
+            hip_qwen_text_encoder_for(pipe, eng.transformer.device, sampling_default=_step1x_text_sampling_default(pipe))
     return eng
 
 

@@ -481,6 +481,12 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         self.kv = _Buffers(dev)
         self.kv_lookup = _Buffers(dev)                                              # the speculative loop's own set (lookup=True)
 
+    @property
+    def generation_config(self):
+        """The adopted module's own `generation_config` (the object `generate` reads its defaults from; None when adopted from a state
+        dict): what a caller written against the module - Step1X-Edit's thinker - finds where it looks for it."""
+        return getattr(self.module, "generation_config", None)
+
     # ---- host-side preparation (no kernel) -----------------------------------------------------------------------------------------
     def position_ids_for(self, input_ids, attention_mask=None, image_grid_thw=None, position_ids=None, mm_token_type_ids=None,
                          text_from_mask=False):
