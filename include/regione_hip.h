@@ -36,7 +36,7 @@ extern "C" {
  * with, rgn_abi_struct_bytes() = sizeof(rgn_qkv_epilogue) * 1000 + sizeof(rgn_gemm_problem) as the library sees them: a binding
  * compiled against another header (a stale libregione_torch.so next to a rebuilt libregione_hip.so) compares both at load time
  * and refuses to run instead of misreading structs passed by pointer. */
-#define RGN_ABI_VERSION 123
+#define RGN_ABI_VERSION 124
 int rgn_version(void);
 size_t rgn_abi_struct_bytes(void);
 const char* rgn_last_error(void);
@@ -621,6 +621,12 @@ int rgn_lm_verify_attention_bf16(const void* Q, int ldq, const void* cache, void
  * 1 <= max_ngram <= 8, 0 <= L <= n, n >= 1, n + R <= limit; pointers 8-byte aligned. */
 int rgn_lm_lookup_step(void* seq, int n, int R, const void* head, int head_stride, int limit, int K, int max_ngram, const void* guess,
                        int guess_len, int L, void* result, void* stream);
+/* rgn_lm_lookup_step for a step whose head[r] is the PICK after row r (rgn_lm_pick_verify) instead of the argmax: the same accept, propose
+ * and `result`, and then seen[seq[n + i]] = 1 for 0 <= i <= a with the id inside [0, V) - the a accepted drafts and the step's own token,
+ * i.e. what the plain sampled loop's picks would have marked.  A rejected draft marks nothing, an id outside [0, V) marks nothing.  Still
+ * ONE block, plain byte stores.  seen == NULL is rgn_lm_lookup_step exactly (V is not read); with a map 1 <= V <= 1048576. */
+int rgn_lm_lookup_step_mark(void* seq, int n, int R, const void* head, int head_stride, int limit, int K, int max_ngram, const void* guess,
+                            int guess_len, int L, void* result, void* seen, int V, void* stream);
 /* The WIDE step (opt-in; HipQwen25VLTextEncoder(batch_kernels="mfma")): the three weight-streaming layers for 1 <= B <=
  * RGN_LM_MAX_WIDE_BATCH rows as a skinny GEMM on v_mfma_f32_16x16x32_bf16 (csrc/decode.hip: lm_gemm_rows_kernel).  Every weight byte is loaded
  * from HBM once per call for all rows (16-byte non-temporal loads straight into the MFMA B operand); the rows of X are staged once per block
@@ -696,6 +702,21 @@ size_t rgn_lm_pick_workspace_bytes(int V);
 int rgn_lm_pick_rows(const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty, int sample, float temperature,
                      int top_k, double top_p, const float* uniform, void* token_out, int token_stride, float* scores_out, int lds,
                      void* workspace, size_t workspace_bytes, void* stream);
+/* The picks of a VERIFICATION step (HipQwen25VLTextEncoder(lookup=True, sampling=True, lookup_sampling=True)): the R rows are the last
+ * settled token and R - 1 drafted tokens of ONE sequence, drafts int64 [R - 1].  Row r reads logits + r * ldl and uniform[r] and picks
+ * under the byte map  seen U {drafts[i] : i < r, 0 <= drafts[i] < V}  - the map the plain loop has at that position exactly when drafts
+ * 0..r-1 were accepted, which is when row r counts at all; it is known before the step runs, so the R picks are independent.  Row r's
+ * token (token_out[r * token_stride]) and processed scores (row r of scores_out [R, lds]) are BIT FOR BIT what rgn_lm_pick gives on that
+ * row with a map holding exactly those marks: the block runs the device function of rgn_lm_pick with this membership test in its first
+ * pass and without its final store.  A membership: an id is penalised once however often it occurs (in `seen` and drafted, or drafted
+ * twice).  `seen` is NEVER written (rgn_lm_lookup_step_mark marks what the step settles), the logits never, rows >= R and columns >= V of
+ * no buffer.  ONE launch, one block per row (the 16-wave block with its 128 KB of LDS, a CU each), plain vector stores, no atomics, blocks
+ * never communicate.  1 <= R <= RGN_LM_MAX_WIDE_BATCH; R = 1 reads no draft (drafts may be NULL).  Every refusal is rgn_lm_pick_rows'
+ * (ranges, alignments, scores_out may not overlap the logits, workspace_bytes >= R * rgn_lm_pick_workspace_bytes(V)) plus drafts non-null
+ * and 8-byte aligned when R > 1, raised before the launch. */
+int rgn_lm_pick_verify(const float* logits, int ldl, int R, int V, const void* seen, const void* drafts, float penalty, int sample,
+                       float temperature, int top_k, double top_p, const float* uniform, void* token_out, int token_stride, float* scores_out,
+                       int lds, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * f4  vision tower of the Qwen2.5-VL prompt encoder ([EXT] transformers Qwen2_5_VisionTransformerPretrainedModel: `get_image_features`

@@ -175,6 +175,11 @@ SIGNATURES = {
                                      C.c_size_t, _c_void_p],
     "rgn_lm_lookup_step": [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p,
                            _c_void_p],
+    # the same step under sampling and a penalty (lookup_sampling=True): the step's picks, then accept + propose + marks
+    "rgn_lm_lookup_step_mark": [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p,
+                                _c_void_p, _c_int, _c_void_p],
+    "rgn_lm_pick_verify": [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_float, _c_int, _c_float, _c_int, C.c_double, _c_void_p,
+                           _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, C.c_size_t, _c_void_p],
     # the wide step: 1 <= B <= 32 rows on the MFMA row GEMM (batch_kernels="mfma")
     "rgn_lm_gemm_rows_bf16": [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p],
     "rgn_lm_gemm_rows_w8": [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int,

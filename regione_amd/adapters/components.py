@@ -242,7 +242,11 @@ def hip_qwen_text_encoder_for(host, dev, sampling_default: bool = False):
     raises ValueError naming the two, with nothing adopted or cached.
     `pipe._regione_hip_text_lookup = True` before the first call adopts with `lookup=True` (generate takes prompt_lookup_num_tokens,
     max_matching_ngram_size and draft_tokens and verifies the drafts in one step); absent, it is False; a value that is not a bool raises
-    ValueError, with nothing adopted or cached."""
+    ValueError, with nothing adopted or cached.
+    `pipe._regione_hip_text_lookup_sampling = True` before the first call, beside `_regione_hip_text_lookup` and the sampling switch (on by
+    default for Step1X-Edit v1p2), adopts with `lookup_sampling=True` (the drafted steps run under the sampled pick, and generate takes
+    the module's generation_config.prompt_lookup_num_tokens); absent, it is False; a value that is not a bool, or True without the two
+    switches it needs, raises ValueError, with nothing adopted or cached."""
     if _memo(host, "_regione_hip_text") is False:
         return None
     cached = _memo(host, "_regione_hip_qwen_text")
@@ -271,6 +275,13 @@ def hip_qwen_text_encoder_for(host, dev, sampling_default: bool = False):
     lookup = host.__dict__.get("_regione_hip_text_lookup", False)
     if not isinstance(lookup, bool):
         raise ValueError(f"pipe._regione_hip_text_lookup = {lookup!r}: True and False are accepted")
+    look_pick = host.__dict__.get("_regione_hip_text_lookup_sampling", False)
+    if not isinstance(look_pick, bool):
+        raise ValueError(f"pipe._regione_hip_text_lookup_sampling = {look_pick!r}: True and False are accepted")
+    if look_pick and not lookup:
+        raise ValueError("pipe._regione_hip_text_lookup_sampling = True needs pipe._regione_hip_text_lookup = True")
+    if look_pick and not sampling:
+        raise ValueError("pipe._regione_hip_text_lookup_sampling = True needs pipe._regione_hip_text_sampling = True")
     mod = getattr(host, "text_encoder", None)
     enc = None
     if type(mod).__name__ == "Qwen2_5_VLForConditionalGeneration" and getattr(mod, "config", None) is not None:
@@ -283,7 +294,8 @@ def hip_qwen_text_encoder_for(host, dev, sampling_default: bool = False):
                                                                     **({"max_batch": batch} if batch > 1 else {}),
                                                                     **({"batch_sampling": True} if rows_pick else {}),
                                                                     **({"batch_kernels": "mfma"} if kernels == "mfma" else {}),
-                                                                    **({"lookup": True} if lookup else {})))
+                                                                    **({"lookup": True} if lookup else {}),
+                                                                    **({"lookup_sampling": True} if look_pick else {})))
         if enc is not None and _memo(host, "_regione_hip_vision") is not False:
             from .. import qwen_vision as QV
             tower = _adopt_or_keep("vision tower", QV.vision_refusal(mod.config), lambda: QV.HipQwen25VLVisionTower(mod, dev), stacklevel=3)

@@ -31,6 +31,10 @@
 //                               them, row r bit-identical to lm_decode_attention_kernel at n0 + r
 //   lm_lookup_step_kernel       one block after the head: accepts the drafts the argmaxes confirm, writes the token after them and
 //                               proposes the next drafts (an n-gram match in the sequence so far, or a caller's guess)
+// and, opt-in (lookup_sampling=True), that step under sampling and a repetition penalty, keeping the prefix the plain sampled loop gives:
+//   lm_pick_verify_kernel       the block of lm_pick_kernel once per row of the step; row r picks under the map seen U drafts[0, r) and
+//                               stores nothing to the map
+//   lm_lookup_step_mark_kernel  lm_lookup_step_kernel over the picks; marks the tokens the step settles in the byte map
 // No atomics; every reduction has a fixed order (lanes: the butterfly of wave_sum; k, keys and slices: ascending), so a repeated call is
 // bit-identical.
 #include <math.h>
@@ -691,9 +695,13 @@ __global__ __launch_bounds__(256) void lm_verify_attention_kernel(const uint16_t
 //   result   int64 [2 + R]: a, k', then the a + 1 accepted tokens.  Plain stores, no atomics; the drafts go to seq[n', n' + k').
 constexpr int LOOKUP_T = 256, LOOKUP_MAX_R = RGN_LM_MAX_WIDE_BATCH, LOOKUP_MAX_NGRAM = 8, LOOKUP_NONE = 0x7fffffff;
 
-__global__ __launch_bounds__(LOOKUP_T) void lm_lookup_step_kernel(int64_t* __restrict__ seq, int n, int R, const int64_t* __restrict__ head,
-                                                                  int hs, int limit, int K, int max_ngram, const int64_t* __restrict__ guess,
-                                                                  int guess_len, int L, int64_t* __restrict__ result) {
+// MARK: the step of a sampled or penalised generate - head[r] is then the PICK after row r - also sets seen[t] = 1 for the a + 1 tokens it
+// settles (the accepted drafts equal the picks before them, so these are head[0..a]); a rejected draft marks nothing, nor does an id
+// outside [0, V).  Plain byte stores of the same value.
+template <bool MARK>
+__device__ __forceinline__ void lm_lookup_step_body(int64_t* __restrict__ seq, int n, int R, const int64_t* __restrict__ head, int hs, int limit,
+                                                    int K, int max_ngram, const int64_t* __restrict__ guess, int guess_len, int L,
+                                                    int64_t* __restrict__ result, uint8_t* __restrict__ seen, int V) {
     __shared__ int best[LOOKUP_T / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int a = 0;
@@ -702,6 +710,12 @@ __global__ __launch_bounds__(LOOKUP_T) void lm_lookup_step_kernel(int64_t* __res
     __syncthreads();                                                             // every thread has read the drafts
     if (tid <= a) result[2 + tid] = head[(size_t)tid * hs];
     if (tid == 0) seq[n + a] = head[(size_t)a * hs];
+    if constexpr (MARK) {
+        if (tid <= a) {
+            const int64_t t = head[(size_t)tid * hs];
+            if (t >= 0 && t < (int64_t)V) seen[t] = 1;
+        }
+    }
     __syncthreads();                                                             // the bonus token is in seq for the whole block
     int kcap = limit - n1 - 1 < K ? limit - n1 - 1 : K;
     kcap = kcap > 0 ? kcap : 0;
@@ -741,6 +755,19 @@ __global__ __launch_bounds__(LOOKUP_T) void lm_lookup_step_kernel(int64_t* __res
         }
     }
     if (tid == 0) { result[0] = a; result[1] = kn; }
+}
+
+__global__ __launch_bounds__(LOOKUP_T) void lm_lookup_step_kernel(int64_t* __restrict__ seq, int n, int R, const int64_t* __restrict__ head,
+                                                                  int hs, int limit, int K, int max_ngram, const int64_t* __restrict__ guess,
+                                                                  int guess_len, int L, int64_t* __restrict__ result) {
+    lm_lookup_step_body<false>(seq, n, R, head, hs, limit, K, max_ngram, guess, guess_len, L, result, nullptr, 0);
+}
+
+__global__ __launch_bounds__(LOOKUP_T) void lm_lookup_step_mark_kernel(int64_t* __restrict__ seq, int n, int R, const int64_t* __restrict__ head,
+                                                                       int hs, int limit, int K, int max_ngram,
+                                                                       const int64_t* __restrict__ guess, int guess_len, int L,
+                                                                       int64_t* __restrict__ result, uint8_t* __restrict__ seen, int V) {
+    lm_lookup_step_body<true>(seq, n, R, head, hs, limit, K, max_ngram, guess, guess_len, L, result, seen, V);
 }
 
 // ---- repetition penalty and sampling: the pick between lm_head and the next embedding -------------------------------------------------
@@ -800,7 +827,7 @@ __device__ __forceinline__ void pick_pass(const float* s, int V, F&& f) {
 // walked from the top).  MASS = true: the smallest value x with sum_{s <= x} expf(s - smax) > target * Z, Z the mass of all of them
 // (digits walked from the bottom).  Every thread returns the same value.
 template <bool MASS>
-__device__ float pick_select(const float* s, int V, double* bins, double* tot, float lo, float smax, double target) {
+__device__ __forceinline__ float pick_select(const float* s, int V, double* bins, double* tot, float lo, float smax, double target) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint32_t prefix = 0;
     double passed = 0.0;                                                         // the weight of the buckets already walked past
@@ -850,10 +877,14 @@ __device__ float pick_select(const float* s, int V, double* bins, double* tot, f
 }
 
 // The pick of ONE row by the whole block: z [V] the row's logits, `seen` its byte map, uniform[0] its uniform, token_out[0] its id slot,
-// s [V] its scores (scores_out or workspace).  Both kernels below are this body, so a row's result does not depend on which one ran it.
+// s [V] its scores (scores_out or workspace).  The kernels below are this body, so a row's result does not depend on which one ran it.
+// VERIFY (a row of a verification step, lm_pick_verify_kernel): an id is a member when seen[v] is set OR it is one of the nd ids of
+// `drafts` (LDS; -1 where the caller's id lay outside [0, V)) - a membership, so an id is penalised once however often it occurs - and
+// the picked token is NOT stored to the map, which is only read.
+template <bool VERIFY>
 __device__ __forceinline__ void lm_pick_row(const float* __restrict__ z, int V, uint8_t* __restrict__ seen, float penalty, int sample,
                                             float temperature, int top_k, double top_p, const float* __restrict__ uniform,
-                                            int64_t* __restrict__ token_out, float* s) {
+                                            int64_t* __restrict__ token_out, float* s, const int* drafts = nullptr, int nd = 0) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     double* bins = (double*)smem;
     __shared__ double tot[PICK_BINS];
@@ -873,6 +904,14 @@ __device__ __forceinline__ void lm_pick_row(const float* __restrict__ z, int V, 
             const int v = v0 + u * PICK_T;
             x[u] = v < V ? z[v] : 0.f;
             m[u] = pen && v < V ? seen[v] : (uint8_t)0;
+        }
+        if constexpr (VERIFY) {
+            if (pen)
+                for (int i = 0; i < nd; ++i) {                                   // nd <= 31, the same for the whole block
+                    const int t = drafts[i];                                     // -1 equals no v
+#pragma unroll
+                    for (int u = 0; u < PICK_U; ++u) m[u] |= (uint8_t)(t == v0 + u * PICK_T);   // t < V: no element past the row matches
+                }
         }
 #pragma unroll
         for (int u = 0; u < PICK_U; ++u) {
@@ -901,7 +940,10 @@ __device__ __forceinline__ void lm_pick_row(const float* __restrict__ z, int V, 
     if (at == PICK_NONE) at = 0;
     __syncthreads();
     if (!sample) {                                                               // greedy: the argmax of the penalised scores
-        if (tid == 0) { token_out[0] = (int64_t)at; seen[at] = 1; }
+        if (tid == 0) {
+            token_out[0] = (int64_t)at;
+            if constexpr (!VERIFY) seen[at] = 1;
+        }
         return;
     }
     const float smax = best;
@@ -995,7 +1037,10 @@ __device__ __forceinline__ void lm_pick_row(const float* __restrict__ z, int V, 
             if (hit) tok = base + (int)__ffsll((long long)hit) - 1;
             else if (any) tok = base + 63 - (int)__clzll((long long)any);
         }
-        if (lane == 0) { token_out[0] = (int64_t)tok; seen[tok] = 1; }
+        if (lane == 0) {
+            token_out[0] = (int64_t)tok;
+            if constexpr (!VERIFY) seen[tok] = 1;
+        }
     }
     __syncthreads();
     if (lo > -INFINITY)                                                          // the processed scores: -inf where filtered
@@ -1007,7 +1052,7 @@ __device__ __forceinline__ void lm_pick_row(const float* __restrict__ z, int V, 
 __global__ __launch_bounds__(PICK_T) void lm_pick_kernel(const float* __restrict__ z, int V, uint8_t* __restrict__ seen, float penalty,
                                                           int sample, float temperature, int top_k, double top_p,
                                                           const float* __restrict__ uniform, int64_t* __restrict__ token_out, float* s) {
-    lm_pick_row(z, V, seen, penalty, sample, temperature, top_k, top_p, uniform, token_out, s);
+    lm_pick_row<false>(z, V, seen, penalty, sample, temperature, top_k, top_p, uniform, token_out, s);
 }
 
 // One block per row (blockIdx.x = b < B), each the block of lm_pick_kernel with its own 128 KB of LDS, i.e. a CU to itself: the rows run
@@ -1017,8 +1062,27 @@ __global__ __launch_bounds__(PICK_T) void lm_pick_rows_kernel(const float* __res
                                                                double top_p, const float* __restrict__ uniform,
                                                                int64_t* __restrict__ token_out, int token_stride, float* s, size_t lds) {
     const size_t b = blockIdx.x;
-    lm_pick_row(z + b * (size_t)ldl, V, seen + b * seen_stride, penalty, sample, temperature, top_k, top_p, sample ? uniform + b : uniform,
-                token_out + b * (size_t)token_stride, s + b * lds);
+    lm_pick_row<false>(z + b * (size_t)ldl, V, seen + b * seen_stride, penalty, sample, temperature, top_k, top_p,
+                       sample ? uniform + b : uniform, token_out + b * (size_t)token_stride, s + b * lds);
+}
+
+// The picks of a verification step: block r (one CU, like a row of lm_pick_rows_kernel) picks for row r under the map seen U drafts[0, r) -
+// the map row r has in the plain loop exactly when drafts 0..r-1 were accepted, known before the step runs, so the R picks run side by
+// side.  ONE map for all rows, only read: the step's marks are lm_lookup_step_mark_kernel's.  Row 0 reads no draft.
+__global__ __launch_bounds__(PICK_T) void lm_pick_verify_kernel(const float* __restrict__ z, int ldl, int V, const uint8_t* __restrict__ seen,
+                                                                 const int64_t* __restrict__ drafts, float penalty, int sample,
+                                                                 float temperature, int top_k, double top_p,
+                                                                 const float* __restrict__ uniform, int64_t* __restrict__ token_out,
+                                                                 int token_stride, float* s, size_t lds) {
+    __shared__ int dr[LOOKUP_MAX_R];
+    const int r = blockIdx.x;                                                    // < LOOKUP_MAX_R: the entry's range
+    if ((int)threadIdx.x < r) {
+        const int64_t t = drafts[threadIdx.x];
+        dr[threadIdx.x] = t >= 0 && t < (int64_t)V ? (int)t : -1;
+    }
+    __syncthreads();
+    lm_pick_row<true>(z + r * (size_t)ldl, V, const_cast<uint8_t*>(seen), penalty, sample, temperature, top_k, top_p,
+                      sample ? uniform + r : uniform, token_out + r * (size_t)token_stride, s + r * lds, dr, r);
 }
 
 // ---- the wide step: 1 <= B <= 32 rows per step on the matrix unit (opt-in: batch_kernels="mfma") --------------------------------------
@@ -1450,9 +1514,8 @@ int rgn_lm_verify_attention_bf16(const void* Q, int ldq, const void* cache, void
     return check_launch(who);
 }
 
-int rgn_lm_lookup_step(void* seq, int n, int R, const void* head, int head_stride, int limit, int K, int max_ngram, const void* guess,
-                       int guess_len, int L, void* result, void* stream) {
-    const char* who = "lm_lookup_step";
+static int lookup_step(const char* who, void* seq, int n, int R, const void* head, int head_stride, int limit, int K, int max_ngram,
+                       const void* guess, int guess_len, int L, void* result, void* seen, int V, void* stream) {
     if (!seq || !head || !result || head_stride < 1) return bad(who, "bad argument (seq, head, result non-null; head_stride >= 1)");
     if (R < 1 || R > LOOKUP_MAX_R) return bad(who, "R outside [1, 32]");
     if (K < 0 || K > LOOKUP_MAX_R - 1) return bad(who, "K outside [0, 31]");
@@ -1460,9 +1523,24 @@ int rgn_lm_lookup_step(void* seq, int n, int R, const void* head, int head_strid
     if (n < 1 || L < 0 || L > n || limit < n + R) return bad(who, "0 <= L <= n, n >= 1 and n + R <= limit: the step's R tokens end inside the run");
     if (guess ? guess_len < 0 : guess_len != 0) return bad(who, "guess_len >= 0 with a guess, 0 without");
     if (((uintptr_t)seq | (uintptr_t)head | (uintptr_t)result | (uintptr_t)guess) & 7u) return bad(who, "seq, head, guess and result must be 8-byte aligned");
+    if (seen) {
+        if (V < 1 || V > PICK_MAX_V) return bad(who, "1 <= V <= 1048576 with a byte map");
+        hipLaunchKernelGGL(lm_lookup_step_mark_kernel, dim3(1), dim3(LOOKUP_T), 0, (hipStream_t)stream, (int64_t*)seq, n, R, (const int64_t*)head,
+                           head_stride, limit, K, max_ngram, (const int64_t*)guess, guess_len, L, (int64_t*)result, (uint8_t*)seen, V);
+        return check_launch("lm_lookup_step_mark_kernel");
+    }
     hipLaunchKernelGGL(lm_lookup_step_kernel, dim3(1), dim3(LOOKUP_T), 0, (hipStream_t)stream, (int64_t*)seq, n, R, (const int64_t*)head, head_stride,
                        limit, K, max_ngram, (const int64_t*)guess, guess_len, L, (int64_t*)result);
     return check_launch("lm_lookup_step_kernel");
+}
+
+int rgn_lm_lookup_step(void* seq, int n, int R, const void* head, int head_stride, int limit, int K, int max_ngram, const void* guess,
+                       int guess_len, int L, void* result, void* stream) {
+    return lookup_step("lm_lookup_step", seq, n, R, head, head_stride, limit, K, max_ngram, guess, guess_len, L, result, nullptr, 0, stream);
+}
+int rgn_lm_lookup_step_mark(void* seq, int n, int R, const void* head, int head_stride, int limit, int K, int max_ngram, const void* guess,
+                            int guess_len, int L, void* result, void* seen, int V, void* stream) {
+    return lookup_step("lm_lookup_step_mark", seq, n, R, head, head_stride, limit, K, max_ngram, guess, guess_len, L, result, seen, V, stream);
 }
 
 int rgn_lm_seen_mark(const void* ids, int n, void* seen, int V, void* stream) {
@@ -1488,7 +1566,8 @@ static void pick_allow_lds(const void* kernel, bool (&done)[64]) {
 
 static int pick(const char* who, bool rows, bool wide, const float* logits, int ldl, int B, int V, void* seen, size_t seen_stride, float penalty,
                 int sample, float temperature, int top_k, double top_p, const float* uniform, void* token_out, int token_stride,
-                float* scores_out, int lds, void* workspace, size_t workspace_bytes, void* stream) {
+                float* scores_out, int lds, void* workspace, size_t workspace_bytes, void* stream, bool verify = false,
+                const void* drafts = nullptr) {
     if (!logits || !seen || !token_out || !workspace || V < 1 || V > PICK_MAX_V)
         return bad(who, "bad argument (logits, seen, token_out, workspace non-null; 1 <= V <= 1048576)");
     if (wide ? !wide_ok(B) : !batch_ok(B)) return bad(who, wide ? "B outside [1, 32]" : "B outside [1, 8]");
@@ -1508,8 +1587,16 @@ static int pick(const char* who, bool rows, bool wide, const float* logits, int 
         if (s0 == z0) return bad(who, "scores_out may not be the logits");  // all rgn_lm_pick ever refused: its accepted set stays
     }
     if (workspace_bytes < (size_t)B * rgn_lm_pick_workspace_bytes(V)) return bad(who, "workspace smaller than B rgn_lm_pick_workspace_bytes(V)");
-    static bool set_one[64] = {}, set_rows[64] = {};
+    static bool set_one[64] = {}, set_rows[64] = {}, set_verify[64] = {};
     float* s = scores_out ? scores_out : (float*)workspace;
+    if (verify) {                                                                // one launch at every R; row 0 reads no draft
+        if (B > 1 && (!drafts || ((uintptr_t)drafts & 7u))) return bad(who, "drafts must be non-null and 8-byte aligned when R > 1");
+        pick_allow_lds((const void*)lm_pick_verify_kernel, set_verify);
+        hipLaunchKernelGGL(lm_pick_verify_kernel, dim3(B), dim3(PICK_T), PICK_LDS, (hipStream_t)stream, logits, ldl, V, (const uint8_t*)seen,
+                           (const int64_t*)drafts, penalty, sample ? 1 : 0, temperature, top_k, top_p, uniform, (int64_t*)token_out, token_stride, s,
+                           scores_out ? (size_t)lds : (size_t)V);
+        return check_launch("lm_pick_verify_kernel");
+    }
     if (B == 1) {
         pick_allow_lds((const void*)lm_pick_kernel, set_one);
         hipLaunchKernelGGL(lm_pick_kernel, dim3(1), dim3(PICK_T), PICK_LDS, (hipStream_t)stream, logits, V, (uint8_t*)seen, penalty,
@@ -1539,6 +1626,12 @@ int rgn_lm_pick_wide(const float* logits, int ldl, int B, int V, void* seen, siz
                      void* workspace, size_t workspace_bytes, void* stream) {
     return pick("lm_pick_wide", true, true, logits, ldl, B, V, seen, seen_stride, penalty, sample, temperature, top_k, top_p, uniform, token_out,
                 token_stride, scores_out, lds, workspace, workspace_bytes, stream);
+}
+int rgn_lm_pick_verify(const float* logits, int ldl, int R, int V, const void* seen, const void* drafts, float penalty, int sample,
+                       float temperature, int top_k, double top_p, const float* uniform, void* token_out, int token_stride, float* scores_out,
+                       int lds, void* workspace, size_t workspace_bytes, void* stream) {
+    return pick("lm_pick_verify", true, true, logits, ldl, R, V, const_cast<void*>(seen), (size_t)(V > 0 ? V : 0), penalty, sample, temperature, top_k,
+                top_p, uniform, token_out, token_stride, scores_out, lds, workspace, workspace_bytes, stream, true, drafts);
 }
 
 }  // extern "C"

@@ -89,6 +89,22 @@ loop of the SAME adoption gives; rejected cache rows and logits rows are overwri
 "mfma"; B > 1, sampling, a penalty and output_scores are refused by name.  `last_lookup_stats` = steps, drafted, accepted, tokens.
 Not measured: the acceptance rate on a real checkpoint (a seeded model's rate means nothing).
 
+`lookup_sampling=True` (opt-in; needs `lookup=True` and `sampling=True`; without it the refusal above stays word for word) lets that
+loop run under the decoding configuration of `sampling=True`: do_sample, temperature, top_k, top_p, repetition_penalty, `uniforms=` /
+`generator=` and `output_scores`.  The rule is the one transformers' `_assisted_decoding` applies to a candidate generator without
+logits: the processors run on row i over the ids up to and including the drafts before it, a token is picked per row, drafts are kept
+up to the first mismatch.  Here a step's head always writes its R fp32 rows; rgn_lm_pick_verify, ONE launch of one block per row, picks
+row r under the byte map seen U drafts[0, r) (the map the plain loop has there exactly when those drafts were accepted) with
+uniforms[k + r] - the uniforms are indexed by new-token position, so the result does not depend on K, on the drafts or on how many
+were accepted - and never writes the map; rgn_lm_lookup_step_mark accepts against the picks and marks the tokens the step settles.
+Every kept token, its fp32 logits row and its processed scores row are BIT FOR BIT those of the plain sampled `generate` of the same
+adoption with the same `uniforms` - not merely the same distribution.  Under the switch `prompt_lookup_num_tokens` and
+`max_matching_ngram_size` left at None take the adopted module's generation_config values (what transformers does), so a caller that
+passes no decoding argument drafts as that config says.  A configuration that is greedy as before takes the greedy lookup path launch
+for launch.  Still refused by name: B > 1, K outside the family's range, assistant_model, everything `_pick_plan` refuses.
+Not measured: the acceptance rate on a real checkpoint, and therefore any speed-up of a real thinking run; at 0 % acceptance the path
+is slower than the plain loop by construction.
+
 There is no eager fallback inside: what the kernels do not implement raises RegionEHipError before any launch, and the adapter
 (regione_amd.adapters, components.py) keeps the host module for configs `qwen25vl_refusal` names.  Activation buffers are kept for the last length
 only; every call returns freshly allocated outputs.
@@ -409,7 +425,8 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
     what = "HipQwen25VLTextEncoder"
 
     def __init__(self, module_or_state_dict, device=None, config=None, max_length: int = 4096, vision=None, weights: str = "bf16",
-                 sampling: bool = False, max_batch: int = 1, batch_sampling: bool = False, batch_kernels: str = "fma", lookup: bool = False):
+                 sampling: bool = False, max_batch: int = 1, batch_sampling: bool = False, batch_kernels: str = "fma", lookup: bool = False,
+                 lookup_sampling: bool = False):
         if weights not in WEIGHT_FORMATS:
             _refuse(self.what, f"weights={weights!r} (the layer matrices are kept as one of {WEIGHT_FORMATS})")
         if not isinstance(sampling, bool):
@@ -430,6 +447,13 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             _refuse(self.what, "batch_sampling=True without sampling=True (it is the decoding configuration of sampling=True over a batch)")
         if batch_sampling and max_batch == 1:
             _refuse(self.what, "batch_sampling=True with max_batch=1 (it needs max_batch > 1: one row takes the one-sequence pick)")
+        if not isinstance(lookup_sampling, bool):
+            _refuse(self.what, f"lookup_sampling={lookup_sampling!r} (True or False)")
+        if lookup_sampling and not lookup:
+            _refuse(self.what, "lookup_sampling=True without lookup=True (it is the speculative loop of lookup=True under a sampled pick)")
+        if lookup_sampling and not sampling:
+            _refuse(self.what, "lookup_sampling=True without sampling=True (it is the decoding configuration of sampling=True over drafted rows)")
+        self.lookup_sampling = lookup_sampling
         self.weights, self.sampling, self.max_batch, self.batch_sampling = weights, sampling, max_batch, batch_sampling
         self.batch_kernels, self.lookup, self.last_lookup_stats = batch_kernels, lookup, None
         sd, cfg, dev, mod = _source(module_or_state_dict, config, device, self.what)
@@ -779,9 +803,17 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         pad positions too).  Finished rows keep being picked; scores past a row's EOS are not meaningful.
         Under `lookup=True` one sequence also takes prompt_lookup_num_tokens=, max_matching_ngram_size= and draft_tokens=: with one of
         them the call is `_generate_lookup` (drafted tokens verified as extra rows of a step; the same sequences and logits, bit for bit),
-        without them it is this loop unchanged."""
+        without them it is this loop unchanged.
+        Under `lookup_sampling=True` that call also takes the decoding configuration of `sampling=True` (bit for bit the plain sampled
+        loop's sequences, logits and scores for the same uniforms), and prompt_lookup_num_tokens / max_matching_ngram_size left at None
+        take the module's generation_config values."""
         plan = None
         look = {k: kw.pop(k) for k in LOOKUP_ARGS if k in kw} if self.lookup else {}   # without lookup=True they are refused as before
+        if self.lookup_sampling:                                                  # transformers' rule: an argument, else the config's field
+            gc = getattr(self.module, "generation_config", None)
+            for k in LOOKUP_ARGS[:2]:
+                if look.get(k) is None and getattr(gc, k, None) is not None:
+                    look[k] = getattr(gc, k)
         self.last_lookup_stats = None                                             # of the last generate: None after a plain one
         if any(v is not None for v in look.values()):
             return self._generate_lookup(look, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, do_sample,
@@ -948,15 +980,25 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         sequence so far; `draft_tokens`: the caller's guess); the host reads its (a, k', tokens) buffer, the one copy of a step, and
         looks for EOS there.  Cache rows and logits rows of rejected drafts are overwritten by later steps.  The prefill's pick is the
         first such step with R = 1.  `last_lookup_stats`: steps (decode steps after the prefill), drafted and accepted (drafts over
-        those steps) and tokens (new tokens decoded before the EOS cut: 1 + steps + accepted)."""
+        those steps) and tokens (new tokens decoded before the EOS cut: 1 + steps + accepted).
+        Under `lookup_sampling=True`, for a configuration that is not greedy as before, the claim is against the plain SAMPLED loop
+        with the same `uniforms` (sequences, logits and processed scores): the head always writes the R fp32 rows, rgn_lm_pick_verify
+        picks row r under the byte map seen U drafts[0, r) with uniforms[k + r] and leaves the map alone, rgn_lm_lookup_step_mark
+        accepts against those picks and marks what the step settles.  The map is zeroed once and rgn_lm_seen_mark runs over the prompt
+        once; scores rows of rejected drafts are overwritten like the logits rows."""
         wide = self.batch_kernels == "mfma"
         pad_arg = kw.pop("pad_token_id", None) if self.max_batch > 1 else None
+        plan = None                                                               # a PickPlan: the step's picks are rgn_lm_pick_verify's
         if self.sampling:
             mine = {k: kw.pop(k) for k in PICK_ARGS + PICK_EXTRA if k in kw}
             eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, False, sync_every, kw)
-            if input_ids.shape[0] == 1 and not self._pick_plan(do_sample, max_new_tokens, mine, 1).greedy_as_before:
-                _refuse(self.what, "prompt_lookup_num_tokens / draft_tokens with sampling, a repetition penalty or output_scores: drafts are "
-                                   "verified against greedy search only")
+            if input_ids.shape[0] == 1:
+                plan = self._pick_plan(do_sample, max_new_tokens, mine, 1)
+                if plan.greedy_as_before:
+                    plan = None                                                   # today's greedy path, launch for launch
+                elif not self.lookup_sampling:
+                    _refuse(self.what, "prompt_lookup_num_tokens / draft_tokens with sampling, a repetition penalty or output_scores: drafts are "
+                                       "verified against greedy search only")
         else:
             eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
         if input_ids.shape[0] != 1:
@@ -1000,11 +1042,38 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         pseq, pheads, pres, pwh = seq.data_ptr(), heads.data_ptr(), res.data_ptr(), c["ws_h"].data_ptr()
         plog = logits.data_ptr() if logits is not None else None
         limit = L + T
+        scores = None
+        if plan is not None:
+            # the picks of this generate, chosen once: the head always writes the R fp32 rows, ONE rgn_lm_pick_verify turns them into the
+            # R picks (row r under seen U drafts[0, r), uniform k + r), rgn_lm_lookup_step_mark accepts against them and marks
+            ws_p = Rm * lib.rgn_lm_pick_workspace_bytes(V)
+            seen = torch.empty(V, dtype=torch.uint8, device=dev)
+            zrows = torch.empty(Rm, V, dtype=torch.float32, device=dev) if logits is None else None
+            pick_ws = torch.empty((ws_p + 3) // 4, dtype=torch.float32, device=dev)
+            scores = torch.empty(T, 1, V, dtype=torch.float32, device=dev) if plan.output_scores else None
+            uni = plan.uniforms
+            if plan.sample and uni is None:                                       # filled once, as in the plain loop: indexed by position
+                g = plan.generator
+                uni = torch.rand(T, 1, dtype=torch.float32, generator=g, device=dev if g is None else g.device).to(dev)
+            ck(lib.rgn_fill_zero(_p(seen), V, st), "rgn_fill_zero")
+            ck(lib.rgn_lm_seen_mark(ids.data_ptr(), L, _p(seen), V, st), "rgn_lm_seen_mark")
+            pen, smp, tmp, tk, tp = plan.penalty, int(plan.sample), plan.temperature, plan.top_k, plan.top_p
+            pu = uni.data_ptr() if plan.sample else None
+            pseen, ppick, pz = seen.data_ptr(), pick_ws.data_ptr(), None if zrows is None else zrows.data_ptr()
+            pscores = None if scores is None else scores.data_ptr()
 
         def settle(n, R, k):
             """The head over the R normalised rows of c["n"] (logits rows k..k + R - 1), accept + propose, the step's one host read."""
-            ck(head_rows(_p(head), pn, d, R, V, d, pheads, 1, None if plog is None else plog + 4 * V * k, V, pwh, ws_h, st), head_name)
-            ck(lib.rgn_lm_lookup_step(pseq, n, R, pheads, 1, limit, K, max_ngram, pguess, nguess, L, pres, st), "rgn_lm_lookup_step")
+            if plan is None:
+                ck(head_rows(_p(head), pn, d, R, V, d, pheads, 1, None if plog is None else plog + 4 * V * k, V, pwh, ws_h, st), head_name)
+                ck(lib.rgn_lm_lookup_step(pseq, n, R, pheads, 1, limit, K, max_ngram, pguess, nguess, L, pres, st), "rgn_lm_lookup_step")
+            else:
+                z = pz if plog is None else plog + 4 * V * k
+                ck(head_rows(_p(head), pn, d, R, V, d, pheads, 1, z, V, pwh, ws_h, st), head_name)
+                ck(lib.rgn_lm_pick_verify(z, V, R, V, pseen, pseq + 8 * n, pen, smp, tmp, tk, tp, None if pu is None else pu + 4 * k, pheads, 1,
+                                          None if pscores is None else pscores + 4 * V * k, V, ppick, ws_p, st), "rgn_lm_pick_verify")
+                ck(lib.rgn_lm_lookup_step_mark(pseq, n, R, pheads, 1, limit, K, max_ngram, pguess, nguess, L, pres, pseen, V, st),
+                   "rgn_lm_lookup_step_mark")
             out = res[:2 + R].tolist()
             return out[0], out[1], out[2:3 + out[0]]
 
@@ -1069,4 +1138,5 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         out = out.to(input_ids.device)
         if not return_dict_in_generate:
             return out
-        return QwenGenerateOutput(out, tuple(logits[j] for j in range(n_new)) if logits is not None else None, None)
+        return QwenGenerateOutput(out, tuple(logits[j] for j in range(n_new)) if logits is not None else None,
+                                  tuple(scores[j] for j in range(n_new)) if scores is not None else None)

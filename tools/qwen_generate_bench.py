@@ -63,6 +63,14 @@ through the speculative loop, whose distance from the plain step is the cost of 
 steps `last_lookup_stats` counts.  The seeded model's own acceptance rate under prompt lookup means nothing and is not reported.
 
     python tools/qwen_generate_bench.py --lookup --no-ab --out profiles/r31_qwen_lookup_bench.json
+
+`--lookup --sampling` times the same legs on `lookup=True, sampling=True, lookup_sampling=True` adoptions under the `s20` configuration
+(penalty 1.05, T 0.7, top-k 20, top-p 0.8) with fixed `uniforms`: the plain leg is the same adoption's plain SAMPLED generate, the forced
+drafts are built from its output, and every leg must reproduce its tokens.  It also times rgn_lm_pick_verify by itself at R = 1, 8, 32
+beside rgn_lm_pick_wide (`--pick-only`: only those launches, for a kernel trace).
+
+    python tools/qwen_generate_bench.py --lookup --sampling --no-ab --out profiles/r34_qwen_lookup_sampling_bench.json
+    rocprofv3 --kernel-trace --stats -d DIR -o kt -- python tools/qwen_generate_bench.py --lookup --sampling --no-ab --iters 1
 """
 import argparse
 import json
@@ -489,6 +497,52 @@ def batched_sampling(a, res):
 LOOKUP_ROWS = {"fma": (2, 4, 8), "mfma": (2, 4, 8, 16, 32)}
 
 
+def pick_verify_direct(res, rounds=20):
+    """rgn_lm_pick_verify by itself at the real vocabulary, R = 1, 8, 32 rows of z = 4 randn over a map of 300 seen ids and random drafts,
+    beside rgn_lm_pick_wide on the same rows (one map per row there): median us per launch of `rounds` event-timed launches per arm, the
+    arms alternating."""
+    from regione_amd import _lib
+    lib = _lib.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    V, R = 152064, 32
+    g = torch.Generator(device="cuda").manual_seed(7)
+    z = (4 * torch.randn(R, V, device="cuda", generator=g)).float()
+    seen = torch.zeros(R, V, dtype=torch.uint8, device="cuda")
+    ids = torch.randint(0, V, (300,), device="cuda", generator=g)
+    for b in range(R):
+        _lib.check(lib.rgn_lm_seen_mark(ids.data_ptr(), 300, seen[b].data_ptr(), V, st), "rgn_lm_seen_mark")
+    seen0 = seen.clone()
+    drafts = torch.randint(0, V, (R - 1,), device="cuda", generator=g)
+    uni = torch.rand(R, device="cuda", generator=g)
+    tok = torch.empty(R, dtype=torch.int64, device="cuda")
+    ws = torch.empty(R, V, dtype=torch.float32, device="cuda")
+    nb = lib.rgn_lm_pick_workspace_bytes(V)
+    skw = SAMPLED["s20"]
+    pen, T, k, p = skw["repetition_penalty"], skw["temperature"], skw["top_k"], skw["top_p"]
+    arms = {}
+    for B in (1, 8, 32):
+        arms[f"verify_r{B}"] = lambda B=B: lib.rgn_lm_pick_verify(z.data_ptr(), V, B, V, seen.data_ptr(), drafts.data_ptr(), pen, 1, T, k, p,
+                                                                  uni.data_ptr(), tok.data_ptr(), 1, None, V, ws.data_ptr(), B * nb, st)
+        arms[f"wide_b{B}"] = lambda B=B: lib.rgn_lm_pick_wide(z.data_ptr(), V, B, V, seen.data_ptr(), V, pen, 1, T, k, p, uni.data_ptr(),
+                                                              tok.data_ptr(), 1, None, V, ws.data_ptr(), B * nb, st)
+    ts = {name: [] for name in arms}
+    for r in range(rounds + 2):                                                  # two warm rounds
+        for name, fn in arms.items():
+            seen.copy_(seen0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            rc = fn()
+            e1.record()
+            e1.synchronize()
+            _lib.check(rc, name)
+            if r >= 2:
+                ts[name].append(e0.elapsed_time(e1) * 1e3)
+    out = {name: {"median_us": statistics.median(v), "min_us": min(v), "max_us": max(v)} for name, v in ts.items()}
+    res["pick_verify_direct"] = dict(V=V, rounds=rounds, config="s20", stat="event-timed single launches (launch overhead included), arms alternating",
+                                     **out)
+    print("pick_verify_direct", json.dumps(out), flush=True)
+
+
 def half_guess(G, K, T):
     """A guess of the T greedy tokens G of which every step accepts half of its drafts (rounded down and up in turn): the loop is
     simulated and the draft after the accepted ones is made wrong."""
@@ -504,8 +558,8 @@ def half_guess(G, K, T):
 
 
 def lookup(a, res):
-    """The `--lookup` legs: per kernel family, weight format and length, the plain greedy generate and the speculative loop under forced
-    drafts, alternating in one process."""
+    """The `--lookup` legs: per kernel family, weight format and length, the plain generate (greedy, or sampled under --sampling) and the
+    speculative loop under forced drafts, alternating in one process."""
     from transformers import Qwen2_5_VLForConditionalGeneration
     from regione_amd import qwen_text_encoder as QT
     cfg = full_size_config()
@@ -517,9 +571,28 @@ def lookup(a, res):
     res["weights"] = "both"
     g = torch.Generator().manual_seed(1)
     prompts = {L: torch.randint(0, 151000, (1, L), generator=g).cuda() for L in LENGTHS}
+    # under --sampling every generate of a leg carries the s20 configuration and the leg's uniforms (indexed by new-token position)
+    uni = {n: torch.rand(NEW, generator=torch.Generator().manual_seed(2))[:n].contiguous().cuda() for n in (1, NEW)}
+    adopt = dict(sampling=True, lookup_sampling=True) if a.sampling else {}
+    if a.sampling:
+        res["sampled_leg"] = SAMPLED["s20"]
+
+    class Sampled:
+        """The adoption with the sampled arguments of a call filled in (uniforms of the call's max_new_tokens)."""
+
+        def __init__(self, enc):
+            self.enc = enc
+
+        def generate(self, ids, max_new_tokens, **kw):
+            extra = dict(SAMPLED["s20"], uniforms=uni[max_new_tokens]) if a.sampling else {}
+            return self.enc.generate(ids, max_new_tokens=max_new_tokens, **kw, **extra)
+
+        @property
+        def last_lookup_stats(self):
+            return self.enc.last_lookup_stats
     for fmt in ("bf16", "fp8"):
         for fam in ("fma", "mfma"):
-            enc = QT.HipQwen25VLTextEncoder(mod, weights=fmt, batch_kernels=fam, lookup=True)
+            enc = Sampled(QT.HipQwen25VLTextEncoder(mod, weights=fmt, batch_kernels=fam, lookup=True, **adopt))
             for L in LENGTHS:
                 ids = prompts[L]
                 G = enc.generate(ids, max_new_tokens=NEW, eos_token_id=[])[0, L:]
@@ -581,7 +654,8 @@ def main():
     ap.add_argument("--wide", action="store_true", help="with --batch: batch_kernels=\"mfma\" at B = 1, 8, 16, 32 beside the default kernels at "
                     "B = 1, 8 (bf16 and fp8); with --sampling also the sampled legs at B = 16, 32")
     ap.add_argument("--wide-kernels", action="store_true", help="only the kernel table of the MFMA row GEMM beside the GEMV entries (--ab-out)")
-    ap.add_argument("--lookup", action="store_true", help="lookup=True adoptions under forced drafts beside their own plain greedy generate")
+    ap.add_argument("--lookup", action="store_true", help="lookup=True adoptions under forced drafts beside their own plain greedy generate; with --sampling: "
+                    "lookup_sampling=True adoptions beside their own plain sampled generate, and rgn_lm_pick_verify by itself")
     a = ap.parse_args()
     from regione_amd import build
     sha = build.csrc_hash()
@@ -589,9 +663,13 @@ def main():
            "stat": "median and min / max of warm, synchronised runs, the two sides alternating; ms per new token = (t64 - t1) / 63 of the medians",
            "model": "Qwen2.5-VL-7B language model, seeded init, text-only ids, no EOS", "hbm_bytes_per_s": HBM_BYTES_PER_S}
     if a.lookup:
-        res["stat"] = ("median and min / max of warm, synchronised runs, every leg alternating with the same adoption's plain greedy generate; "
+        res["stat"] = ("median and min / max of warm, synchronised runs, every leg alternating with the same adoption's plain "
+                       + ("sampled" if a.sampling else "greedy") + " generate; "
                        "ms per step = (t64 - t1) / steps, ms per token = (t64 - t1) / 63 of the medians")
-        lookup(a, res)
+        if a.sampling:
+            pick_verify_direct(res)
+        if not a.pick_only:
+            lookup(a, res)
         if a.out:
             with open(a.out, "w") as f:
                 json.dump(res, f, indent=1)
