@@ -21,12 +21,11 @@ buffer, the `mrope_section` selection applied once, cast to bf16 and copied in o
 
 `generate` is transformers' greedy search on the same weights (csrc/decode.hip), ONE decode loop for 1 <= B <= max_batch rows: the prefill
 above, row by row, with the k | v columns of every layer appended to the row's KV cache [layers][B][cap, 2 Hkv 128] after mRoPE
-(rgn_lm_kv_append_bf16) and the final norm on the last row only, then per new token B rows through the stack - rgn_lm_gemv_bf16_rows for the
-four projections (bias for q|k|v, the two roundings of `h + linear(a)` for the residual adds), rgn_lm_decode_attention_bf16_rows against the
-caches, the row kernels at M = B - and rgn_lm_head_argmax_rows over `lm_head` (fp32 logits, the lowest index on a tie), which writes the
-tokens into the device id row the next rgn_text_embed reads.  At B = 1 a `_rows` entry launches the one-row kernels (it is the one-row
-entry), so one sequence decodes on the GEMVs tuned for it.  New token k sits at max(prompt positions) + 1 + k on all three axes
-(`decode_position_ids`).  The loop is a `for` over `max_new_tokens`; the host reads the ids every `sync_every` tokens to look for EOS.
+(rgn_lm_kv_append_bf16) and the final norm on the last row only, then per new token the decode step of `_DecodeStep` (the step is
+described there, once) at M = B rows; this loop's middle of a layer is rgn_mrope_bf16, rgn_lm_kv_append_bf16_rows and
+rgn_lm_decode_attention_bf16_rows against the rows' caches, and the step's head writes the tokens into the device id row the next
+rgn_text_embed reads.  New token k sits at max(prompt positions) + 1 + k on all three axes (`decode_position_ids`).  The loop is a `for`
+over `max_new_tokens`; the host reads the ids every `sync_every` tokens to look for EOS.
 
 `weights="fp8"` stores the four packed matrices of every layer (q|k|v, o, gate|up, down) as OCP e4m3fn with one fp32 scale per output
 channel (ops.quantize_w8, after the concatenation: the scale is per row, so the concatenation of the parts' quantisations is the
@@ -77,10 +76,11 @@ cap = 4096, so 7.5 GB at 32 rows.  Not measured: real checkpoints.
 take transformers' `prompt_lookup_num_tokens=K` and `max_matching_ngram_size` (default 2) and the extension `draft_tokens=` (a 1-D int64
 guess of the whole continuation, new token 0 first; alone it takes the family's largest K).  The speculative loop (`_generate_lookup`;
 the plain loop is untouched and runs when neither argument is given) keeps prompt and new ids in ONE device run and carries up to K
-drafted tokens as extra rows of a step: the `_rows` / `_wide` entries at B = R = drafts + 1 (row b of those is bit for bit the one-row
-call), rgn_mrope_bf16 over R consecutive table rows, ONE rgn_lm_kv_append_bf16 of R rows, and rgn_lm_verify_attention_bf16 - R <= 8
-queries against the one cache, query r over n + r rows, K and V of a 64-key slice loaded once for all of them, row r bit for bit
-rgn_lm_decode_attention_bf16 at n + r (groups of 8 queries under "mfma").  rgn_lm_lookup_step, one block after the head, accepts the
+drafted tokens as extra rows of a step: the step of `_DecodeStep` at M = R = drafts + 1 (row b of its entries is bit for bit the one-row
+call), with its own middle: rgn_mrope_bf16 over R consecutive table rows, ONE rgn_lm_kv_append_bf16 of R rows, and
+rgn_lm_verify_attention_bf16 - R <= 8 queries against the one cache, query r over n + r rows, K and V of a 64-key slice loaded once for
+all of them, row r bit for bit rgn_lm_decode_attention_bf16 at n + r (groups of 8 queries under "mfma").  rgn_lm_lookup_step, one block
+after the head, accepts the
 drafts that equal the argmax before them (the first mismatch ends the run), writes the token after them and drafts the next step's
 rows: the rule of transformers' PromptLookupCandidateGenerator over the run so far (n-gram sizes from the largest down, the lowest
 matching window with a non-empty continuation), or the caller's guess; never past max_new_tokens.  The host reads that kernel's small
@@ -417,6 +417,102 @@ def _bound(fn, name, *args):
     return functools.partial(fn, *conv), name
 
 
+def _row_buffers(enc, M):
+    """The shapes of the activation buffers of M rows through the stack."""
+    return dict(h=(M, enc.d), n=(M, enc.d), qkv=(M, enc.qkv_cols), a=(M, enc.Hq * HEAD_DIM), ff=(M, 2 * enc.F), g=(M, enc.F))
+
+
+class _DecodeStep:
+    """The decode step of one generate, chosen once: M rows through the stack against KV caches (csrc/decode.hip).  The plain loop runs
+    it at M = B, the lookup loop at M = R = drafts + 1; row m of every entry below is bit for bit the one-row call, and at M = 1 a `_rows`
+    entry launches the one-row kernels (it is the one-row entry), so one sequence decodes on the GEMVs tuned for it.
+
+      rgn_text_embed                     the M ids picked last, read from the device id run
+      layer   rgn_rms_norm_rows          at M rows
+              linear(q|k|v) + bias       `linear` is rgn_lm_gemv_bf16_rows, rgn_lm_gemv_w8_rows under weights="fp8" (half the bytes per token
+                                         for those matrices), or under batch_kernels="mfma" rgn_lm_gemm_rows_bf16 / rgn_lm_gemm_rows_w8
+              the loop's middle          mRoPE, the append of the k | v columns to the cache(s), attention against them: the loop's own
+              linear(o)                  with the two roundings of `h + linear(a)` for the residual add
+              rgn_rms_norm_rows, linear(gate|up), rgn_swiglu_bf16, linear(down) with the residual add
+      final   rgn_rms_norm_rows          over the M rows
+      head    rgn_lm_head_argmax_rows over `lm_head` (fp32 logits, the lowest index on a tie), rgn_lm_head_argmax_wide under "mfma"
+
+    Every launch of a layer outside the middle, and the final norm, takes the same arguments at every step: `launches` converts them once
+    (`_bound`), so that a step only calls ready objects.  The embedding, the middle and the head's call (its token and logits rows move)
+    stay with the loop; the head's entry and workspace size are chosen here."""
+
+    def __init__(self, enc, lib):
+        self.enc, self.lib, self.wide, self.fp8 = enc, lib, enc.batch_kernels == "mfma", enc.weights == "fp8"
+        # the linear layer of this adoption: a weight is the leading argument(s) of its entry, (W,) or (W8, scale): `wp`
+        if self.fp8:
+            self.linear, self.linear_name = (lib.rgn_lm_gemm_rows_w8, "rgn_lm_gemm_rows_w8") if self.wide else \
+                (lib.rgn_lm_gemv_w8_rows, "rgn_lm_gemv_w8_rows")
+        else:
+            self.linear, self.linear_name = (lib.rgn_lm_gemm_rows_bf16, "rgn_lm_gemm_rows_bf16") if self.wide else \
+                (lib.rgn_lm_gemv_bf16_rows, "rgn_lm_gemv_bf16_rows")
+        self.head, self.head_name = (lib.rgn_lm_head_argmax_wide, "rgn_lm_head_argmax_wide") if self.wide else \
+            (lib.rgn_lm_head_argmax_rows, "rgn_lm_head_argmax_rows")
+
+    def wp(self, w):
+        return (w.data_ptr(), ops._wscale(w).data_ptr()) if self.fp8 else (w.data_ptr(),)
+
+    def head_workspace_bytes(self, M):
+        V = self.enc.tok.shape[0]
+        return self.lib.rgn_lm_head_wide_workspace_bytes(V, M) if self.wide else M * self.lib.rgn_lm_head_workspace_bytes(V)
+
+    def launches(self, c, M, st):
+        """([(before, after) per layer], final norm) for M rows in the buffers `c`: the bound launches before a layer's middle (rms,
+        q|k|v), those after it (o, rms, gate|up, swiglu, down) and the final norm, each a (ready call, entry name)."""
+        e, lin, name, wp = self.enc, self.linear, self.linear_name, self.wp
+        d, F, eps, qc, ad = e.d, e.F, e.eps, e.qkv_cols, e.Hq * HEAD_DIM
+        ph, pn, pqkv, pa, pff, pg = (c[k].data_ptr() for k in ("h", "n", "qkv", "a", "ff", "g"))
+        rms, swiglu = self.lib.rgn_rms_norm_rows, self.lib.rgn_swiglu_bf16
+        lp = [([_bound(rms, "rgn_rms_norm_rows", ph, d, p["ln1"].data_ptr(), pn, d, M, d, eps, st),
+                _bound(lin, name, *wp(p["wqkv"]), pn, d, p["bqkv"].data_ptr(), None, 0, pqkv, qc, M, qc, d, st)],
+               [_bound(lin, name, *wp(p["wo"]), pa, ad, None, ph, d, ph, d, M, d, ad, st),
+                _bound(rms, "rgn_rms_norm_rows", ph, d, p["ln2"].data_ptr(), pn, d, M, d, eps, st),
+                _bound(lin, name, *wp(p["wgu"]), pn, d, None, None, 0, pff, 2 * F, M, 2 * F, d, st),
+                _bound(swiglu, "rgn_swiglu_bf16", pff, 2 * F, pg, F, M, F, st),
+                _bound(lin, name, *wp(p["wdown"]), pg, F, None, ph, d, ph, d, M, d, F, st)]) for p in e.layers]
+        return lp, _bound(rms, "rgn_rms_norm_rows", ph, d, e.final_ln.data_ptr(), pn, d, M, d, eps, st)
+
+
+class _PickState:
+    """The device state of a sampled pick (a PickPlan that is not greedy as before) over the B rows of `ids` [B, L], for steps that write
+    at most M logits rows (the plain loop: M = B; the lookup loop: B = 1, M = K + 1): the byte map `seen` [B, V], zeroed once and marked
+    over each row's VALID prompt ids only (the left padding is never marked); `zrows` [M, V], where the head writes when the caller keeps
+    no logits; the pick workspace of M rows; `scores` [T, B, V] under output_scores; and the uniforms, `plan.uniforms` or torch.rand(T, B)
+    from the generator (on its device, then moved), filled before the loop: the kernels have no generator and index it by position."""
+
+    def __init__(self, lib, plan, ids, lens, T, M, V, keep_logits, st):
+        (B, L), dev, ck = ids.shape, ids.device, _lib.check
+        self.ws_1 = lib.rgn_lm_pick_workspace_bytes(V)
+        self.ws_bytes = M * self.ws_1
+        self.seen = torch.empty(B, V, dtype=torch.uint8, device=dev)
+        self.zrows = None if keep_logits else torch.empty(M, V, dtype=torch.float32, device=dev)
+        self.ws = torch.empty((self.ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
+        self.scores = torch.empty(T, B, V, dtype=torch.float32, device=dev) if plan.output_scores else None
+        uni = plan.uniforms
+        if plan.sample and uni is None:
+            g = plan.generator
+            uni = torch.rand(T, B, dtype=torch.float32, generator=g, device=dev if g is None else g.device).to(dev)
+        ck(lib.rgn_fill_zero(_p(self.seen), B * V, st), "rgn_fill_zero")
+        for b, n in enumerate(lens):
+            ck(lib.rgn_lm_seen_mark(ids.data_ptr() + 8 * (b * L + L - n), n, _p(self.seen[b]), V, st), "rgn_lm_seen_mark")
+        self.uniforms = uni                                                      # kept: the loop reads it through `pu`
+        self.pu = uni.data_ptr() if plan.sample else None
+        self.how = (plan.penalty, int(plan.sample), plan.temperature, plan.top_k, plan.top_p)
+
+
+def _generate_result(seq, n_new, logits, scores, as_dict):
+    """What a generate returns: `seq`, or under return_dict_in_generate a QwenGenerateOutput with the first n_new of the [T, B, V]
+    `logits` / `scores` rows (None: not asked for)."""
+    if not as_dict:
+        return seq
+    return QwenGenerateOutput(seq, tuple(logits[k] for k in range(n_new)) if logits is not None else None,
+                              tuple(scores[k] for k in range(n_new)) if scores is not None else None)
+
+
 class HipQwen25VLTextEncoder(_HipTextEncoder):
     """`Qwen2_5_VLForConditionalGeneration(input_ids, attention_mask, pixel_values, image_grid_thw, output_hidden_states=True)` with the
     language model on the HIP kernels.  Returns an object with `.last_hidden_state` [B, L, d] bf16 and `.hidden_states`, a ONE-element
@@ -631,8 +727,7 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         ids = input_ids.to(self.device, torch.int64).contiguous()
         tab = tables.to(self.device)                                              # the one host-to-device copy of the tables
         Lb = max(lengths)
-        t = self.buf.get(Lb, dict(h=(Lb, self.d), n=(Lb, self.d), qkv=(Lb, self.qkv_cols), a=(Lb, self.Hq * HEAD_DIM), ff=(Lb, 2 * self.F),
-                                  g=(Lb, self.F)))
+        t = self.buf.get(Lb, _row_buffers(self, Lb))
         out = torch.empty(B, L, self.d, dtype=torch.bfloat16, device=self.device)
         lib = _lib.lib()
         if min(lengths) < L:                                                      # padded positions are zero rows
@@ -771,6 +866,43 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         self.lm_head = w.detach().to(self.device, torch.bfloat16).contiguous()
         return self.lm_head
 
+    # The preparation of both decode loops, every refusal before any launch.  It comes in three calls, in this order, because the lookup
+    # loop's own refusals sit between them and which refusal a bad call gets first is behaviour.
+    def _decoding_args(self, input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw):
+        """(eos ids, the pad_token_id argument, the PICK_ARGS / PICK_EXTRA arguments or None), each split off `kw` where the adoption
+        takes it (a default adoption refuses them as before), and `_generate_args` over the rest."""
+        pad_arg = kw.pop("pad_token_id", None) if self.max_batch > 1 else None
+        if not self.sampling:                                                     # without the opt-in every refusal is what it was
+            return self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw), pad_arg, None
+        mine = {k: kw.pop(k) for k in PICK_ARGS + PICK_EXTRA if k in kw}
+        return self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, False, sync_every, kw), pad_arg, mine
+
+    def _sampled_pick(self, do_sample, max_new_tokens, mine, B):
+        """The PickPlan of a call whose pick is not the head's argmax; None without `sampling=True` and for a configuration that is
+        greedy as before, which runs the greedy launches unchanged."""
+        if mine is None:
+            return None
+        plan = self._pick_plan(do_sample, max_new_tokens, mine, B)
+        return None if plan.greedy_as_before else plan
+
+    def _prompt_inputs(self, input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids, image_embeds, T,
+                       pad_arg, eos):
+        """(ids_cpu, lens, prompt tables [2, B, L, 128], decode tables [2, B, T, 128], pad id, lm_head, image embeddings, their rows per
+        batch row, those rows as one device index) of left-padded rows; the last three are None without images."""
+        ids_cpu, lens, tables, pos = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids,
+                                                   image_embeds, {}, left=True)
+        pad = resolve_pad_token_id(pad_arg, getattr(self.module, "generation_config", None), eos)
+        new_tables = mrope_tables(self.inv_freq, decode_position_ids(pos, T), self.mrope_section)
+        head = self._adopt_lm_head()                                               # may refuse: nothing has been launched yet
+        emb = self._image_embeds(pixel_values, image_grid_thw, image_embeds)
+        rows = idx = None
+        if emb is not None:
+            if self.image_token_id is None:
+                _refuse(self.what, "the config has no image_token_id")
+            rows = image_rows_left(ids_cpu, lens, int(self.image_token_id), emb.shape[0], self.what)
+            idx = torch.cat(rows).to(self.device)
+        return ids_cpu, lens, tables, new_tables, pad, head, emb, rows, idx
+
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, pixel_values=None, image_grid_thw=None, max_new_tokens=None, eos_token_id=None,
                  do_sample=None, return_dict_in_generate=False, output_logits=False, mm_token_type_ids=None, image_embeds=None,
@@ -780,9 +912,9 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         generation_config.eos_token_id, []: no EOS); n_new is the largest cut (max_new_tokens if a row never finished) and a row that
         finished earlier holds the pad id from its cut on (`assemble_sequences`) - one row is cut, never padded.
         Each row is prefilled over its valid tokens by `_prefill_row` into its own cache at rows [0, n_b) - no padded key is ever in a
-        cache, so decode needs no mask - then every step decodes the B rows from ONE stream of the weights through the `_rows` entries of
-        csrc/decode.hip (rgn_lm_gemv_bf16_rows, or rgn_lm_gemv_w8_rows under weights="fp8"; rgn_lm_kv_append_bf16_rows;
-        rgn_lm_decode_attention_bf16_rows; the row kernels at M = B), which launch the one-row kernels at B = 1.  rgn_lm_head_argmax_rows
+        cache, so decode needs no mask - then every step is the decode step of `_DecodeStep` at M = B, the B rows from ONE stream of the
+        weights, with this loop's middle of a layer: rgn_mrope_bf16 at the step's table rows, then rgn_lm_kv_append_bf16_rows and
+        rgn_lm_decode_attention_bf16_rows over the rows' caches, in groups of at most 8 rows.  The step's head
         picks INTO the device id row the next rgn_text_embed reads (new ids [T, B] and decode RoPE tables [T, B, 128] time-major, so a
         step's rows are contiguous): no token visits the host inside a step.  The host reads the ids back every `sync_every` tokens to
         look for EOS (never without one); the result does not depend on `sync_every`.  The device keeps decoding finished rows (a fixed
@@ -807,7 +939,6 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         Under `lookup_sampling=True` that call also takes the decoding configuration of `sampling=True` (bit for bit the plain sampled
         loop's sequences, logits and scores for the same uniforms), and prompt_lookup_num_tokens / max_matching_ngram_size left at None
         take the module's generation_config values."""
-        plan = None
         look = {k: kw.pop(k) for k in LOOKUP_ARGS if k in kw} if self.lookup else {}   # without lookup=True they are refused as before
         if self.lookup_sampling:                                                  # transformers' rule: an argument, else the config's field
             gc = getattr(self.module, "generation_config", None)
@@ -818,41 +949,22 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         if any(v is not None for v in look.values()):
             return self._generate_lookup(look, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, do_sample,
                                          return_dict_in_generate, output_logits, mm_token_type_ids, image_embeds, position_ids, sync_every, kw)
-        pad_arg = kw.pop("pad_token_id", None) if self.max_batch > 1 else None    # a default adoption refuses the argument as before
-        if self.sampling:                                                         # opt-in: without it every refusal below is what it was
-            mine = {k: kw.pop(k) for k in PICK_ARGS + PICK_EXTRA if k in kw}
-            eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, False, sync_every, kw)
-            plan = self._pick_plan(do_sample, max_new_tokens, mine, input_ids.shape[0])
-            if plan.greedy_as_before:
-                plan = None
-        else:
-            eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
-        ids_cpu, lens, tables, pos = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids,
-                                                   image_embeds, {}, left=True)
-        (B, L), T = ids_cpu.shape, int(max_new_tokens)
-        pad = resolve_pad_token_id(pad_arg, getattr(self.module, "generation_config", None), eos)
-        new_tables = mrope_tables(self.inv_freq, decode_position_ids(pos, T), self.mrope_section)        # [2, B, T, 128]
-        head = self._adopt_lm_head()                                               # may refuse: nothing has been launched yet
-        emb = self._image_embeds(pixel_values, image_grid_thw, image_embeds)
-        rows = None
-        if emb is not None:
-            if self.image_token_id is None:
-                _refuse(self.what, "the config has no image_token_id")
-            rows = image_rows_left(ids_cpu, lens, int(self.image_token_id), emb.shape[0], self.what)
-            idx = torch.cat(rows).to(self.device)
+        eos, pad_arg, mine = self._decoding_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
+        plan = self._sampled_pick(do_sample, max_new_tokens, mine, input_ids.shape[0])
+        T = int(max_new_tokens)
+        ids_cpu, lens, tables, new_tables, pad, head, emb, rows, idx = self._prompt_inputs(
+            input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids, image_embeds, T, pad_arg, eos)
+        B, L = ids_cpu.shape
         lib, dev, d, V = _lib.lib(), self.device, self.d, self.tok.shape[0]
         nmax = max(lens)
         cap, kvw, nl = nmax + T, 2 * self.Hkv * HEAD_DIM, len(self.layers)
-        wide = self.batch_kernels == "mfma"                                       # the MFMA row GEMM at every B; the per-row entries in groups
+        step = _DecodeStep(self, lib)
         ws_a = B * lib.rgn_lm_decode_attention_workspace_bytes(self.Hq, cap)
-        ws_h = lib.rgn_lm_head_wide_workspace_bytes(V, B) if wide else B * lib.rgn_lm_head_workspace_bytes(V)
-        head_rows, head_name = (lib.rgn_lm_head_argmax_wide, "rgn_lm_head_argmax_wide") if wide else \
-            (lib.rgn_lm_head_argmax_rows, "rgn_lm_head_argmax_rows")
+        ws_h = step.head_workspace_bytes(B)
+        head_rows, head_name = step.head, step.head_name
         groups = [(g0, min(MAX_BATCH, B - g0)) for g0 in range(0, B, MAX_BATCH)]  # at most 8 rows per launch of a per-row entry
-        c = self.kv.get((B, cap), dict(cache=(nl, B, cap, kvw), h=(B, d), n=(B, d), qkv=(B, self.qkv_cols), a=(B, self.Hq * HEAD_DIM),
-                                       ff=(B, 2 * self.F), g=(B, self.F), ws_a=((ws_a + 1) // 2,), ws_h=((ws_h + 1) // 2,)))
-        t = self.buf.get(nmax, dict(h=(nmax, d), n=(nmax, d), qkv=(nmax, self.qkv_cols), a=(nmax, self.Hq * HEAD_DIM), ff=(nmax, 2 * self.F),
-                                    g=(nmax, self.F)))
+        c = self.kv.get((B, cap), dict(cache=(nl, B, cap, kvw), **_row_buffers(self, B), ws_a=((ws_a + 1) // 2,), ws_h=((ws_h + 1) // 2,)))
+        t = self.buf.get(nmax, _row_buffers(self, nmax))
         ids = input_ids.to(dev, torch.int64).contiguous()
         new = torch.empty(T, B, dtype=torch.int64, device=dev)                    # time-major: a step's B ids are contiguous
         logits = torch.empty(T, B, V, dtype=torch.float32, device=dev) if output_logits else None
@@ -867,23 +979,11 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
                    head_name)
         else:
             # the pick of this generate, chosen once: lm_head writes the fp32 rows, ONE rgn_lm_pick_rows turns them into the step's id row
-            ws_1 = lib.rgn_lm_pick_workspace_bytes(V)
-            pick_rows, pick_name, pick_groups = (lib.rgn_lm_pick_wide, "rgn_lm_pick_wide", [(0, B)]) if wide else \
+            pk = _PickState(lib, plan, ids, lens, T, B, V, logits is not None, st)
+            pick_rows, pick_name, pick_groups = (lib.rgn_lm_pick_wide, "rgn_lm_pick_wide", [(0, B)]) if step.wide else \
                 (lib.rgn_lm_pick_rows, "rgn_lm_pick_rows", groups)
-            ws_p = B * ws_1
-            seen = torch.empty(B, V, dtype=torch.uint8, device=dev)
-            zrows = torch.empty(B, V, dtype=torch.float32, device=dev) if logits is None else None
-            pick_ws = torch.empty((ws_p + 3) // 4, dtype=torch.float32, device=dev)
-            scores = torch.empty(T, B, V, dtype=torch.float32, device=dev) if plan.output_scores else None
-            uni = plan.uniforms
-            if plan.sample and uni is None:                                       # filled before the loop; the kernel has no generator
-                g = plan.generator
-                uni = torch.rand(T, B, dtype=torch.float32, generator=g, device=dev if g is None else g.device).to(dev)
-            ck(lib.rgn_fill_zero(_p(seen), B * V, st), "rgn_fill_zero")
-            for b, n in enumerate(lens):                                          # the row's valid ids only: the padding is never marked
-                ck(lib.rgn_lm_seen_mark(ids.data_ptr() + 8 * (b * L + L - n), n, _p(seen[b]), V, st), "rgn_lm_seen_mark")
-            pen, smp, tmp, tk, tp = plan.penalty, int(plan.sample), plan.temperature, plan.top_k, plan.top_p
-            pu = uni.data_ptr() if plan.sample else None
+            seen, zrows, pick_ws, scores, ws_1, pu = pk.seen, pk.zrows, pk.ws, pk.scores, pk.ws_1, pk.pu
+            pen, smp, tmp, tk, tp = pk.how
 
             def pick(k):
                 z = logits[k] if logits is not None else zrows
@@ -901,40 +1001,26 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             at += k
             self._rms(h[n - 1:n], self.final_ln, c["n"][b:b + 1])                 # the final norm on the last row only
         pick(0)
-        ph, pqkv, pa, pff, pg, pws = (c[k].data_ptr() for k in ("h", "qkv", "a", "ff", "g", "ws_a"))
-        # the linear layer of this adoption, picked once: a weight is the leading argument(s) of its entry, (W,) or (W8, scale)
-        if self.weights == "fp8":
-            gemv, gemv_name = (lib.rgn_lm_gemm_rows_w8, "rgn_lm_gemm_rows_w8") if wide else (lib.rgn_lm_gemv_w8_rows, "rgn_lm_gemv_w8_rows")
-            wp = lambda w: (w.data_ptr(), ops._wscale(w).data_ptr())
-        else:
-            gemv, gemv_name = (lib.rgn_lm_gemm_rows_bf16, "rgn_lm_gemm_rows_bf16") if wide else (lib.rgn_lm_gemv_bf16_rows, "rgn_lm_gemv_bf16_rows")
-            wp = lambda w: (w.data_ptr(),)
-        ptok, pfin, pcos, psin = self.tok.data_ptr(), self.final_ln.data_ptr(), ntab[0].data_ptr(), ntab[1].data_ptr()
-        Hq, Hkv, F, eps, scale, qc, ad = self.Hq, self.Hkv, self.F, self.eps, float(self.scale), self.qkv_cols, self.Hq * HEAD_DIM
+        ph, pqkv, pa, pws = (c[k].data_ptr() for k in ("h", "qkv", "a", "ws_a"))
+        ptok, pcos, psin = self.tok.data_ptr(), ntab[0].data_ptr(), ntab[1].data_ptr()
+        Hq, Hkv, scale, qc, ad = self.Hq, self.Hkv, float(self.scale), self.qkv_cols, self.Hq * HEAD_DIM
         cstride = cap * kvw
         row0, nn = (ctypes.c_int * B)(), (ctypes.c_int * B)()                     # host arrays: the entries copy them into the launch
-        # Every launch of a layer but mRoPE (its table row moves) takes the same arguments at every step: they are converted once here, so
-        # that a step only calls ready objects.  Per layer: the launches before mRoPE, and those after it.
-        rms, swiglu, append, attend = lib.rgn_rms_norm_rows, lib.rgn_swiglu_bf16, lib.rgn_lm_kv_append_bf16_rows, lib.rgn_lm_decode_attention_bf16_rows
+        # This loop's middle of a layer: mRoPE (its table row moves with the step), then per group of rows the append to the rows' caches
+        # and the attention against them over the host arrays, bound once like the step's own launches and run with those after mRoPE.
+        append, attend = lib.rgn_lm_kv_append_bf16_rows, lib.rgn_lm_decode_attention_bf16_rows
+        layers, (final_norm, final_name) = step.launches(c, B, st)
         lp = []
         ws_1a = ws_a // B                                                         # a row's attention partials: a multiple of 8 x 65 bytes
         ints = ctypes.POINTER(ctypes.c_int)
         at_row = lambda arr, g0: ctypes.cast(ctypes.byref(arr, 4 * g0), ints)     # the group's slice of a host int array
-        for i, p in enumerate(self.layers):
+        for i, (before, after) in enumerate(layers):
             pc = c["cache"][i].data_ptr()
             kv = [_bound(append, "rgn_lm_kv_append_bf16_rows", pqkv + 2 * qc * g0, qc, pc + 2 * cstride * g0, cstride, cap, at_row(row0, g0), Bg,
                          Hq, Hkv, st) for g0, Bg in groups]
             kv += [_bound(attend, "rgn_lm_decode_attention_bf16_rows", pqkv + 2 * qc * g0, qc, pc + 2 * cstride * g0, cstride, pa + 2 * ad * g0, ad,
                           at_row(nn, g0), Bg, Hq, Hkv, scale, pws + ws_1a * g0, Bg * ws_1a, st) for g0, Bg in groups]
-            lp.append(([_bound(rms, "rgn_rms_norm_rows", ph, d, p["ln1"].data_ptr(), pn, d, B, d, eps, st),
-                        _bound(gemv, gemv_name, *wp(p["wqkv"]), pn, d, p["bqkv"].data_ptr(), None, 0, pqkv, qc, B, qc, d, st)],
-                       kv +
-                       [_bound(gemv, gemv_name, *wp(p["wo"]), pa, ad, None, ph, d, ph, d, B, d, ad, st),
-                        _bound(rms, "rgn_rms_norm_rows", ph, d, p["ln2"].data_ptr(), pn, d, B, d, eps, st),
-                        _bound(gemv, gemv_name, *wp(p["wgu"]), pn, d, None, None, 0, pff, 2 * F, B, 2 * F, d, st),
-                        _bound(swiglu, "rgn_swiglu_bf16", pff, 2 * F, pg, F, B, F, st),
-                        _bound(gemv, gemv_name, *wp(p["wdown"]), pg, F, None, ph, d, ph, d, B, d, F, st)]))
-        final_norm, final_name = _bound(rms, "rgn_rms_norm_rows", ph, d, pfin, pn, d, B, d, eps, st)
+            lp.append((before, kv + after))
         mrope = functools.partial(lib.rgn_mrope_bf16, ctypes.c_void_p(pqkv), ctypes.c_int(qc))
         mtail = (ctypes.c_int(B), ctypes.c_int(Hq), ctypes.c_int(Hkv), ctypes.c_void_p(st))
         n_new = T
@@ -960,11 +1046,7 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             ck(final_norm(), final_name)
             pick(k)
         seq, n_new = assemble_sequences(ids_cpu, new[:n_new].cpu(), eos, pad)
-        seq = seq.to(input_ids.device)
-        if not return_dict_in_generate:
-            return seq
-        return QwenGenerateOutput(seq, tuple(logits[k] for k in range(n_new)) if logits is not None else None,
-                                  tuple(scores[k] for k in range(n_new)) if scores is not None else None)
+        return _generate_result(seq.to(input_ids.device), n_new, logits, scores, return_dict_in_generate)
 
     # ---- greedy generate with drafted tokens verified in one step (lookup=True; csrc/decode.hip: lm_verify_attention_kernel) ----------
     def _generate_lookup(self, look, input_ids, attention_mask, pixel_values, image_grid_thw, max_new_tokens, eos_token_id, do_sample,
@@ -972,8 +1054,8 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         """Greedy `generate` for ONE sequence whose steps carry drafted tokens: the sequences and fp32 `logits` of the plain loop of the
         same adoption, bit for bit, in fewer steps when drafts are accepted.  A step at settled length n with k' drafts runs R = k' + 1
         rows - the last settled token and the drafts, contiguous in the device id run `seq` (prompt, then new tokens) - through the
-        entries of the batched loop at B = R (row b of those has the bits of the one-row call), with two differences: rgn_mrope_bf16
-        over R consecutive table rows, and ONE rgn_lm_kv_append_bf16 of R rows at cache row n - 1 followed by
+        decode step of `_DecodeStep` at M = R (row b of its entries has the bits of the one-row call), with this loop's middle of a
+        layer: rgn_mrope_bf16 over R consecutive table rows, and ONE rgn_lm_kv_append_bf16 of R rows at cache row n - 1 followed by
         rgn_lm_verify_attention_bf16 (query r over n + r cache rows; groups of 8 queries under "mfma").  The head writes R argmaxes (and,
         with output_logits, the fp32 rows straight into logits[k : k + R]); rgn_lm_lookup_step keeps the drafts the argmaxes confirm,
         writes the token after them and drafts for the next step (`prompt_lookup_num_tokens`: transformers' n-gram lookup in the
@@ -986,48 +1068,29 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         picks row r under the byte map seen U drafts[0, r) with uniforms[k + r] and leaves the map alone, rgn_lm_lookup_step_mark
         accepts against those picks and marks what the step settles.  The map is zeroed once and rgn_lm_seen_mark runs over the prompt
         once; scores rows of rejected drafts are overwritten like the logits rows."""
-        wide = self.batch_kernels == "mfma"
-        pad_arg = kw.pop("pad_token_id", None) if self.max_batch > 1 else None
-        plan = None                                                               # a PickPlan: the step's picks are rgn_lm_pick_verify's
-        if self.sampling:
-            mine = {k: kw.pop(k) for k in PICK_ARGS + PICK_EXTRA if k in kw}
-            eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, False, sync_every, kw)
-            if input_ids.shape[0] == 1:
-                plan = self._pick_plan(do_sample, max_new_tokens, mine, 1)
-                if plan.greedy_as_before:
-                    plan = None                                                   # today's greedy path, launch for launch
-                elif not self.lookup_sampling:
-                    _refuse(self.what, "prompt_lookup_num_tokens / draft_tokens with sampling, a repetition penalty or output_scores: drafts are "
-                                       "verified against greedy search only")
-        else:
-            eos = self._generate_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
+        eos, pad_arg, mine = self._decoding_args(input_ids, attention_mask, max_new_tokens, eos_token_id, do_sample, sync_every, kw)
         if input_ids.shape[0] != 1:
             _refuse(self.what, f"prompt_lookup_num_tokens / draft_tokens with B = {input_ids.shape[0]}: drafts are verified for one sequence (B == 1)")
-        K, max_ngram, guess = lookup_plan(self.what, look, wide)
-        ids_cpu, lens, tables, pos = self._prepare(input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids,
-                                                   image_embeds, {}, left=True)
-        L, T = ids_cpu.shape[1], int(max_new_tokens)
-        if lens[0] != L:
+        plan = self._sampled_pick(do_sample, max_new_tokens, mine, 1)            # a PickPlan: the step's picks are rgn_lm_pick_verify's
+        if plan is not None and not self.lookup_sampling:                        # None: today's greedy path, launch for launch
+            _refuse(self.what, "prompt_lookup_num_tokens / draft_tokens with sampling, a repetition penalty or output_scores: drafts are "
+                               "verified against greedy search only")
+        K, max_ngram, guess = lookup_plan(self.what, look, self.batch_kernels == "mfma")
+        T = int(max_new_tokens)
+        ids_cpu, lens, tables, new_tables, pad, head, emb, _, idx = self._prompt_inputs(
+            input_ids, attention_mask, pixel_values, image_grid_thw, position_ids, mm_token_type_ids, image_embeds, T, pad_arg, eos)
+        L = ids_cpu.shape[1]
+        if lens[0] != L:                                                          # `_generate_args` takes one row with an all-ones mask only
             _refuse(self.what, "prompt_lookup_num_tokens / draft_tokens with a padded row: the id run of the lookup is the unpadded prompt")
-        pad = resolve_pad_token_id(pad_arg, getattr(self.module, "generation_config", None), eos)
-        new_tables = mrope_tables(self.inv_freq, decode_position_ids(pos, T), self.mrope_section)        # [2, 1, T, 128]
-        head = self._adopt_lm_head()                                               # may refuse: nothing has been launched yet
-        emb = self._image_embeds(pixel_values, image_grid_thw, image_embeds)
-        idx = None
-        if emb is not None:
-            if self.image_token_id is None:
-                _refuse(self.what, "the config has no image_token_id")
-            idx = image_rows_left(ids_cpu, lens, int(self.image_token_id), emb.shape[0], self.what)[0].to(self.device)
         lib, dev, d, V = _lib.lib(), self.device, self.d, self.tok.shape[0]
         Rm, cap, kvw, nl = K + 1, L + T, 2 * self.Hkv * HEAD_DIM, len(self.layers)
         groups = {R: [(g0, min(MAX_BATCH, R - g0)) for g0 in range(0, R, MAX_BATCH)] for R in range(1, Rm + 1)}
+        step = _DecodeStep(self, lib)
         ws_a = min(Rm, MAX_BATCH) * lib.rgn_lm_decode_attention_workspace_bytes(self.Hq, cap)          # the groups run one after another
-        ws_h = lib.rgn_lm_head_wide_workspace_bytes(V, Rm) if wide else Rm * lib.rgn_lm_head_workspace_bytes(V)
-        head_rows, head_name = (lib.rgn_lm_head_argmax_wide, "rgn_lm_head_argmax_wide") if wide else \
-            (lib.rgn_lm_head_argmax_rows, "rgn_lm_head_argmax_rows")
-        c = self.kv_lookup.get((Rm, cap), dict(cache=(nl, cap, kvw), h=(Rm, d), n=(Rm, d), qkv=(Rm, self.qkv_cols), a=(Rm, self.Hq * HEAD_DIM),
-                                               ff=(Rm, 2 * self.F), g=(Rm, self.F), ws_a=((ws_a + 1) // 2,), ws_h=((ws_h + 1) // 2,)))
-        t = self.buf.get(L, dict(h=(L, d), n=(L, d), qkv=(L, self.qkv_cols), a=(L, self.Hq * HEAD_DIM), ff=(L, 2 * self.F), g=(L, self.F)))
+        ws_h = step.head_workspace_bytes(Rm)
+        head_rows, head_name = step.head, step.head_name
+        c = self.kv_lookup.get((Rm, cap), dict(cache=(nl, cap, kvw), **_row_buffers(self, Rm), ws_a=((ws_a + 1) // 2,), ws_h=((ws_h + 1) // 2,)))
+        t = self.buf.get(L, _row_buffers(self, L))
         ids = input_ids.to(dev, torch.int64).contiguous()
         seq = torch.empty(L + T, dtype=torch.int64, device=dev)                   # ONE run: the prompt ids, then the new tokens
         seq[:L].copy_(ids[0])
@@ -1038,7 +1101,7 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         pguess, nguess = (gdev.data_ptr(), gdev.numel()) if gdev is not None else (None, 0)
         tab, ntab = tables.to(dev), new_tables.transpose(1, 2).contiguous().to(dev)                       # [2, 1, L, 128], [2, T, 1, 128]
         st, ck = _stream(), _lib.check
-        ph, pn, pqkv, pa, pff, pg, pws = (c[k].data_ptr() for k in ("h", "n", "qkv", "a", "ff", "g", "ws_a"))
+        ph, pn, pqkv, pa, pws = (c[k].data_ptr() for k in ("h", "n", "qkv", "a", "ws_a"))
         pseq, pheads, pres, pwh = seq.data_ptr(), heads.data_ptr(), res.data_ptr(), c["ws_h"].data_ptr()
         plog = logits.data_ptr() if logits is not None else None
         limit = L + T
@@ -1046,20 +1109,10 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         if plan is not None:
             # the picks of this generate, chosen once: the head always writes the R fp32 rows, ONE rgn_lm_pick_verify turns them into the
             # R picks (row r under seen U drafts[0, r), uniform k + r), rgn_lm_lookup_step_mark accepts against them and marks
-            ws_p = Rm * lib.rgn_lm_pick_workspace_bytes(V)
-            seen = torch.empty(V, dtype=torch.uint8, device=dev)
-            zrows = torch.empty(Rm, V, dtype=torch.float32, device=dev) if logits is None else None
-            pick_ws = torch.empty((ws_p + 3) // 4, dtype=torch.float32, device=dev)
-            scores = torch.empty(T, 1, V, dtype=torch.float32, device=dev) if plan.output_scores else None
-            uni = plan.uniforms
-            if plan.sample and uni is None:                                       # filled once, as in the plain loop: indexed by position
-                g = plan.generator
-                uni = torch.rand(T, 1, dtype=torch.float32, generator=g, device=dev if g is None else g.device).to(dev)
-            ck(lib.rgn_fill_zero(_p(seen), V, st), "rgn_fill_zero")
-            ck(lib.rgn_lm_seen_mark(ids.data_ptr(), L, _p(seen), V, st), "rgn_lm_seen_mark")
-            pen, smp, tmp, tk, tp = plan.penalty, int(plan.sample), plan.temperature, plan.top_k, plan.top_p
-            pu = uni.data_ptr() if plan.sample else None
-            pseen, ppick, pz = seen.data_ptr(), pick_ws.data_ptr(), None if zrows is None else zrows.data_ptr()
+            pk = _PickState(lib, plan, ids, lens, T, Rm, V, logits is not None, st)
+            scores, ws_p, pu = pk.scores, pk.ws_bytes, pk.pu
+            pen, smp, tmp, tk, tp = pk.how
+            pseen, ppick, pz = pk.seen.data_ptr(), pk.ws.data_ptr(), None if pk.zrows is None else pk.zrows.data_ptr()
             pscores = None if scores is None else scores.data_ptr()
 
         def settle(n, R, k):
@@ -1080,36 +1133,26 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
         h, _ = self._prefill_row(t, ids[0], L, tab[0, 0], tab[1, 0], emb, idx, cache=c["cache"])
         self._rms(h[L - 1:L], self.final_ln, c["n"][0:1])                         # the final norm on the last row only
         _, kd, new = settle(L, 1, 0)                                              # the prefill's pick: a step of one row, nothing to accept
-        if self.weights == "fp8":
-            gemv, gemv_name = (lib.rgn_lm_gemm_rows_w8, "rgn_lm_gemm_rows_w8") if wide else (lib.rgn_lm_gemv_w8_rows, "rgn_lm_gemv_w8_rows")
-            wp = lambda w: (w.data_ptr(), ops._wscale(w).data_ptr())
-        else:
-            gemv, gemv_name = (lib.rgn_lm_gemm_rows_bf16, "rgn_lm_gemm_rows_bf16") if wide else (lib.rgn_lm_gemv_bf16_rows, "rgn_lm_gemv_bf16_rows")
-            wp = lambda w: (w.data_ptr(),)
-        ptok, pfin, pcos, psin = self.tok.data_ptr(), self.final_ln.data_ptr(), ntab[0].data_ptr(), ntab[1].data_ptr()
-        Hq, Hkv, F, eps, scale, qc, ad = self.Hq, self.Hkv, self.F, self.eps, float(self.scale), self.qkv_cols, self.Hq * HEAD_DIM
-        rms, swiglu = lib.rgn_rms_norm_rows, lib.rgn_swiglu_bf16
+        ptok, pcos, psin = self.tok.data_ptr(), ntab[0].data_ptr(), ntab[1].data_ptr()
+        Hq, Hkv, scale, qc, ad = self.Hq, self.Hkv, float(self.scale), self.qkv_cols, self.Hq * HEAD_DIM
         I, P, Fl = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
         plans = {}
 
         def plan_for(R):
-            """The launches of a step of R rows, built once: per layer those before mRoPE, the three whose arguments move with the step
-            (mRoPE's table rows, the append's cache row, each verify group's n0: leading arguments bound, the tail ready) and the rest."""
+            """The launches of a step of R rows, built once: per layer the step's own before mRoPE, this loop's middle - the three whose
+            arguments move with the step (mRoPE's table rows, the append's cache row, each verify group's n0: leading arguments bound, the
+            tail ready) - and the step's own after it."""
+            layers, final = step.launches(c, R, st)
             lp = []
-            for i, p in enumerate(self.layers):
+            for i, (before, after) in enumerate(layers):
                 pc = c["cache"][i].data_ptr()
                 lp.append((
-                    [_bound(rms, "rgn_rms_norm_rows", ph, d, p["ln1"].data_ptr(), pn, d, R, d, eps, st),
-                     _bound(gemv, gemv_name, *wp(p["wqkv"]), pn, d, p["bqkv"].data_ptr(), None, 0, pqkv, qc, R, qc, d, st)],
+                    before,
                     functools.partial(lib.rgn_lm_kv_append_bf16, P(pqkv), I(qc), P(pc), I(cap)),
                     [(functools.partial(lib.rgn_lm_verify_attention_bf16, P(pqkv + 2 * qc * g0), I(qc), P(pc), P(pa + 2 * ad * g0), I(ad)), g0,
                       (I(Rg), I(Hq), I(Hkv), Fl(scale), P(pws), ctypes.c_size_t(ws_a), P(st))) for g0, Rg in groups[R]],
-                    [_bound(gemv, gemv_name, *wp(p["wo"]), pa, ad, None, ph, d, ph, d, R, d, ad, st),
-                     _bound(rms, "rgn_rms_norm_rows", ph, d, p["ln2"].data_ptr(), pn, d, R, d, eps, st),
-                     _bound(gemv, gemv_name, *wp(p["wgu"]), pn, d, None, None, 0, pff, 2 * F, R, 2 * F, d, st),
-                     _bound(swiglu, "rgn_swiglu_bf16", pff, 2 * F, pg, F, R, F, st),
-                     _bound(gemv, gemv_name, *wp(p["wdown"]), pg, F, None, ph, d, ph, d, R, d, F, st)]))
-            return lp, _bound(rms, "rgn_rms_norm_rows", ph, d, pfin, pn, d, R, d, eps, st), (I(R), I(Hq), I(Hkv), P(st))
+                    after))
+            return lp, final, (I(R), I(Hq), I(Hkv), P(st))
 
         mrope = functools.partial(lib.rgn_mrope_bf16, P(pqkv), I(qc))
         k, steps, drafted, accepted = 1, 0, 0, 0                                   # k new tokens are settled
@@ -1135,8 +1178,4 @@ class HipQwen25VLTextEncoder(_HipTextEncoder):
             new += toks
         self.last_lookup_stats = dict(steps=steps, drafted=drafted, accepted=accepted, tokens=len(new))
         out, n_new = assemble_sequences(ids_cpu, torch.tensor(new, dtype=torch.int64).view(-1, 1), eos, pad)
-        out = out.to(input_ids.device)
-        if not return_dict_in_generate:
-            return out
-        return QwenGenerateOutput(out, tuple(logits[j] for j in range(n_new)) if logits is not None else None,
-                                  tuple(scores[j] for j in range(n_new)) if scores is not None else None)
+        return _generate_result(out.to(input_ids.device), n_new, logits, scores, return_dict_in_generate)

@@ -27,10 +27,7 @@ pytestmark = pytest.mark.gpu
 _p, _stream = ops._p, ops._stream
 BATCHES = (1, 2, 3, 5, 8)
 SENTINEL = -7.0
-
-
-def _gen(seed):
-    return torch.Generator(device="cuda").manual_seed(seed)
+_gen, _cuda, _kernel_names = QB.gen, QB.cuda, QB.kernel_names
 
 
 def _ints(v):
@@ -275,13 +272,6 @@ def test_a_key_60_above_the_rest_returns_its_value_row_bit_for_bit_in_a_differen
 NEW = 12
 
 
-def _cuda(single):
-    kw = dict(input_ids=single.input_ids.cuda(), attention_mask=single.attention_mask.cuda())
-    if single.image_grid_thw is not None:
-        kw.update(image_grid_thw=single.image_grid_thw.cuda(), mm_token_type_ids=(kw["input_ids"] == HQ.IMAGE).int())
-    return kw
-
-
 @functools.lru_cache(maxsize=None)
 def _run(weights):
     """One batched generate (twice) and the B = 1 generate of every unpadded row, shared by the tests below."""
@@ -372,16 +362,6 @@ def test_one_row_under_max_batch_is_the_default_adoption(weights):
     got = s["hip"].generate(**kw, max_new_tokens=NEW, return_dict_in_generate=True, output_logits=True)
     assert torch.equal(got.sequences, s["alone"][1].sequences)
     assert all(torch.equal(a, b) for a, b in zip(got.logits, s["alone"][1].logits))
-
-
-def _kernel_names(fn):
-    from torch.profiler import ProfilerActivity, profile
-    fn()                                                                         # warm: buffers, lm_head, the pick's LDS attribute
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return [e.name for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")]
 
 
 def test_one_row_under_max_batch_launches_the_one_row_kernels():

@@ -168,15 +168,7 @@ PENALISED = dict(do_sample=False, repetition_penalty=1.1)
 FULL = dict(max_new_tokens=NEW, return_dict_in_generate=True, output_logits=True)
 
 
-def _gen(seed):
-    return torch.Generator(device="cuda").manual_seed(seed)
-
-
-def _cuda(single):
-    kw = dict(input_ids=single.input_ids.cuda(), attention_mask=single.attention_mask.cuda())
-    if single.image_grid_thw is not None:
-        kw.update(image_grid_thw=single.image_grid_thw.cuda(), mm_token_type_ids=(kw["input_ids"] == HQ.IMAGE).int())
-    return kw
+_gen, _cuda, _kernels = QB.gen, QB.cuda, QB.kernels
 
 
 @functools.lru_cache(maxsize=None)
@@ -289,16 +281,6 @@ def test_the_greedy_batch_and_the_default_adoption_keep_their_bits(weights):
     got = s["hip"].generate(**s["alone_kw"][1], **FULL, **SAMPLED, uniforms=s["uni"][:, 1].contiguous(), output_scores=True)
     want = s["alone_sampled"][1]
     assert torch.equal(got.sequences, want.sequences) and all(torch.equal(x, y) for x, y in zip(got.scores, want.scores))
-
-
-def _kernels(fn):
-    from torch.profiler import ProfilerActivity, profile
-    fn()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    return out, [e.name for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")]
 
 
 def test_a_warm_sampled_batch_dispatches_only_library_kernels_one_rows_pick_per_step_and_a_greedy_batch_none():

@@ -214,26 +214,7 @@ def test_the_clamp_leaves_room_for_the_steps_own_token():
 # ---- generate ---------------------------------------------------------------------------------------------------------------------------
 NEW = 12
 KS = {"fma": (1, 3, 7), "mfma": (1, 3, 7, 15, 31)}
-
-
-@functools.lru_cache(maxsize=None)
-def _module():
-    torch.manual_seed(0)
-    return HQ.tiny_qwen25vl(layers=2).cuda()
-
-
-@functools.lru_cache(maxsize=None)
-def _prompts():
-    """The image prompt (25 tokens) and the repetitive text prompt (63 tokens: its cache crosses 64 rows while decoding)."""
-    out = []
-    for i, s in enumerate(QB.rows(QB.PROMPTS[:2])):
-        kw = dict(input_ids=s.input_ids.cuda(), attention_mask=s.attention_mask.cuda())
-        if s.image_grid_thw is not None:
-            g = torch.Generator(device="cuda").manual_seed(11)
-            kw.update(image_grid_thw=s.image_grid_thw.cuda(), mm_token_type_ids=(kw["input_ids"] == HQ.IMAGE).int(),
-                      image_embeds=torch.randn(4, 256, device="cuda", generator=g).bfloat16())
-        out.append(kw)
-    return out
+_module, _prompts, _corrupt = QB.module, QB.prompts, QB.corrupt
 
 
 def _full(T, **kw):
@@ -244,12 +225,6 @@ def _same(got, want, what):
     assert torch.equal(got.sequences, want.sequences), (what, "sequences")
     assert len(got.logits) == len(want.logits), (what, "n_new")
     assert torch.equal(torch.cat(got.logits), torch.cat(want.logits)), (what, "logits")
-
-
-def _corrupt(G, every):
-    g = G.clone()
-    g[every - 1::every] = (g[every - 1::every] + 1) % HQ.VOCAB
-    return g
 
 
 @functools.lru_cache(maxsize=None)

@@ -26,26 +26,7 @@ KS = {"fma": (1, 3, 7), "mfma": (1, 3, 7, 15, 31)}
 SAMPLED = dict(do_sample=True, temperature=0.7, top_k=20, top_p=0.8, repetition_penalty=1.05)
 PENALISED = dict(do_sample=False, repetition_penalty=1.3)
 ADOPTIONS = [(w, k) for w in ("bf16", "fp8") for k in ("fma", "mfma")]
-
-
-@functools.lru_cache(maxsize=None)
-def _module():
-    torch.manual_seed(0)
-    return HQ.tiny_qwen25vl(layers=2).cuda()
-
-
-@functools.lru_cache(maxsize=None)
-def _prompts():
-    """The image prompt (25 tokens) and the repetitive text prompt (63 tokens: its cache crosses 64 rows while decoding)."""
-    out = []
-    for s in QB.rows(QB.PROMPTS[:2]):
-        kw = dict(input_ids=s.input_ids.cuda(), attention_mask=s.attention_mask.cuda())
-        if s.image_grid_thw is not None:
-            g = torch.Generator(device="cuda").manual_seed(11)
-            kw.update(image_grid_thw=s.image_grid_thw.cuda(), mm_token_type_ids=(kw["input_ids"] == HQ.IMAGE).int(),
-                      image_embeds=torch.randn(4, 256, device="cuda", generator=g).bfloat16())
-        out.append(kw)
-    return out
+_module, _prompts, _corrupt = QB.module, QB.prompts, QB.corrupt
 
 
 @functools.lru_cache(maxsize=None)
@@ -72,12 +53,6 @@ def _same(got, want, what):
     assert len(got.logits) == len(want.logits) and len(got.scores) == len(want.scores), (what, "n_new")
     assert torch.equal(_bits(got.logits), _bits(want.logits)), (what, "logits")
     assert torch.equal(_bits(got.scores), _bits(want.scores)), (what, "scores")
-
-
-def _corrupt(G, every):
-    g = G.clone()
-    g[every - 1::every] = (g[every - 1::every] + 1) % HQ.VOCAB
-    return g
 
 
 @functools.lru_cache(maxsize=None)

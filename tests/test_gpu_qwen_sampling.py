@@ -33,11 +33,13 @@ transformers = pytest.importorskip("transformers")
 
 import host_qwen_text_pipeline as HQ  # noqa: E402
 import lm_pick_model as PM  # noqa: E402
+import qwen_batch_model as QB  # noqa: E402
 from regione_amd import _lib, ops  # noqa: E402
 from regione_amd import qwen_text_encoder as QT  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 _p, _stream = ops._p, ops._stream
+_kernels = QB.kernels
 
 VS = [1, 1000, 1024, 152064]
 CONFIGS = [(1.05, 1e-6, 0, 1.0), (1.05, 0.1, 1, 0.001), (1.0, 0.7, 20, 0.8), (1.1, 1.0, 0, 0.9), (1.0, 1.3, 50, 1.0), (1.2, 0.7, 0, 0.95)]
@@ -360,16 +362,6 @@ def test_the_eos_cut_of_a_sampled_generate_does_not_depend_on_sync_every():
         assert len(res.scores) == j + 1 and res.logits is None
         assert all(torch.equal(x, y) for x, y in zip(res.scores, s["sampled"].scores))
     assert tried >= 1, "no run produced a token that first occurs at a new index >= 2"
-
-
-def _kernels(fn):
-    from torch.profiler import ProfilerActivity, profile
-    fn()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    return out, [e.name for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")]
 
 
 def test_a_warm_sampled_generate_dispatches_only_libregione_hip_kernels_and_the_default_path_launches_no_pick():

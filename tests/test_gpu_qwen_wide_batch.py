@@ -27,21 +27,7 @@ FULL = dict(max_new_tokens=NEW, return_dict_in_generate=True, output_logits=True
 SAMPLED = dict(do_sample=True, temperature=0.7, top_k=20, top_p=0.8, repetition_penalty=1.1)
 
 
-def _gen(seed):
-    return torch.Generator(device="cuda").manual_seed(seed)
-
-
-def _cuda(single):
-    kw = dict(input_ids=single.input_ids.cuda(), attention_mask=single.attention_mask.cuda())
-    if single.image_grid_thw is not None:
-        kw.update(image_grid_thw=single.image_grid_thw.cuda(), mm_token_type_ids=(kw["input_ids"] == HQ.IMAGE).int())
-    return kw
-
-
-@functools.lru_cache(maxsize=None)
-def _module():
-    torch.manual_seed(0)
-    return HQ.tiny_qwen25vl(layers=2).cuda()
+_gen, _cuda, _module, _kernel_names = QB.gen, QB.cuda, QB.module, QB.kernel_names
 
 
 @functools.lru_cache(maxsize=None)
@@ -254,16 +240,6 @@ def test_against_the_fma_adoption_step_0_logits_are_within_twice_the_bound_and_c
 
 
 # ---- what runs ----------------------------------------------------------------------------------------------------------------------------
-def _kernel_names(fn):
-    from torch.profiler import ProfilerActivity, profile
-    fn()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return [e.name for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")]
-
-
 def test_a_sampled_wide_step_is_one_pick_launch():
     hip = QT.HipQwen25VLTextEncoder(_module(), sampling=True, max_batch=32, batch_sampling=True, batch_kernels="mfma")
     kw, _ = _batch(tuple(range(20)))
